@@ -1,8 +1,14 @@
 """Benchmark of the stereo hot path (BASELINE.json metric) on 1..N MI355X GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs
+is given, and prints the result line.  --full adds everything else the benchmark measures after
+the timed region: the per-kernel HIP-event table and the roofline (single-stream steps of their
+own), the streaming probe, the HBM-only k_paths launch and the CPU baseline (the oracle on host
+cores, built -O3 -march=native there); the --no-* switches take single ones out of a --full run.
 
 A step = one pass of the hot path over one batch of synthetic rectified pairs already resident
 in HBM: StereoSGBM::compute (prefilter, BT cost, block sum, path aggregation, WTA/uniqueness/
@@ -297,10 +303,62 @@ def parse_args(argv=None):
                          "disparities in one collective (every frame is gathered)")
     ap.add_argument("--inject-failure", default=None, metavar="RANK:STEP",
                     help="test hook: rank RANK's step STEP raises SDR_ERR_ARG (failure-path tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what the headline figure does not need: "
+                         "the per-kernel table and roofline, the streaming probe, the HBM-only launch "
+                         "and the CPU baseline (each has its own --no-* switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (the arrays "
+                         "its caller receives) as DIR/<name>.npy, float32 or float64, at most "
+                         "64 MB in all (a fixed seeded sample of larger outputs; DIR/outputs.json "
+                         "says which)")
     a = ap.parse_args(argv)
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.in_flight_timing and not a.full:
+        ap.error("--in-flight-timing belongs to the per-kernel report: add --full")
+    if not a.full:
+        # a plain run does only what the headline figure needs
+        a.no_kernel_timing = a.no_cpu_baseline = True
     return a
+
+
+DUMP_BUDGET = 60 * 1000 * 1000  # bytes of .npy payload a --dump-outputs run may write in all
+
+
+def dump_outputs(dirpath, arrays, rank=0, budget=DUMP_BUDGET):
+    """Writes {name: tensor or array} as dirpath/<name>.npy (rank r > 0: <name>_rank<r>.npy):
+    integers and float32 as float32 (int16 disparities are exact in it), float64 as float64.
+    Within the budget every array is written whole; beyond it the large ones are cut to a sorted
+    sample of flat element indices from a fixed seed (numpy's PCG64, the same from run to run and
+    build to build), each in proportion to its size.  outputs.json lists shapes and samples."""
+    import torch
+
+    os.makedirs(dirpath, exist_ok=True)
+    items = []
+    for name, v in arrays.items():
+        t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))
+        t = t if t.dtype == torch.float64 else t.to(torch.float32)
+        items.append((name, t.contiguous()))
+    total = sum(t.numel() * t.element_size() for _, t in items)
+    small = 1 << 20  # arrays below 1 MiB are always written whole
+    big = sum(t.numel() * t.element_size() for _, t in items if t.numel() * t.element_size() > small)
+    frac = 1.0 if total <= budget else max(0.0, (budget - (total - big)) / big)
+    manifest = {}
+    for n, (name, t) in enumerate(items):
+        nbytes = t.numel() * t.element_size()
+        entry = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""), "sampled": False}
+        if frac < 1.0 and nbytes > small:
+            k = int(t.numel() * frac)
+            idx = np.sort(np.random.default_rng(20240 + n).integers(0, t.numel(), size=k, dtype=np.int64))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            entry.update(sampled=True, sample=f"{k} flat elements: sorted(default_rng({20240 + n})."
+                                              f"integers(0, {entry['shape']} elements, {k}))")
+        fname = name if rank == 0 else f"{name}_rank{rank}"
+        np.save(os.path.join(dirpath, fname + ".npy"), t.cpu().numpy())
+        manifest[fname] = entry
+    with open(os.path.join(dirpath, "outputs.json" if rank == 0 else f"outputs_rank{rank}.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
 
 
 def main():
@@ -452,6 +510,7 @@ def main():
                        for _ in range(world)] for _ in range(2)] for _ in range(ns)]
     works = [[None, None] for _ in range(ns)]
     failure = {"code": 0, "err": None}  # this rank's first failed step (reported at the next check)
+    last_out = {"d": None, "k": 0}  # the newest step's returned tensor and its stream slot (--dump-outputs)
     inject = tuple(int(v) for v in a.inject_failure.split(":")) if a.inject_failure else None
     from stereo_depth_ruler_amd._lib import SDRError
 
@@ -473,6 +532,7 @@ def main():
                 if inject is not None and inject == (rank, i):
                     raise SDRError(-1, f"injected failure at rank {rank} step {i}")
                 res = run(j, k, slot) if out is None else run(j, k, slot, out=out)
+                last_out["d"], last_out["k"] = res, k
             except Exception as e:  # noqa: BLE001 -- any failed step is reported to every rank
                 if not dist_on:
                     raise
@@ -543,6 +603,20 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if a.dump_outputs:
+        # what the last timed step's caller received (nothing has run on these buffers since)
+        lk = last_out["k"]
+        if kind == "sgbm":
+            outs = {"disparity": last_out["d"], "xyz": xyz[lk]}
+        elif kind == "live":
+            outs = {"filtered_disparity": pipes[lk].filtered, "disparity": pipes[lk].disp,
+                    "depth": pipes[lk].depth}
+        else:
+            pc = pipes[lk]
+            outs = {"disparity": pc.disp, "xyz": pc.xyz, "points": pc.points,
+                    "voxel_counts": np.asarray(pc.counts, np.float64),
+                    "voxel_points": torch.cat([pc.filtered[f, :pc.counts[f]] for f in range(batch)])}
+        dump_outputs(a.dump_outputs, outs, rank)
     ranks = None
     if dist_on:
         # every rank's own wall time (host-side exchange), then the max over ranks

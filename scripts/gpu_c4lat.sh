@@ -7,7 +7,7 @@ TAG=${1:-c4lat}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/$TAG
 mkdir -p "$O"
-timeout -k 10 200 python3 bench.py --config c4 --streams 1 --steps 200 --warmup 20 --no-cpu-baseline > "$O/c4.s1.json" 2> "$O/c4.s1.err"
+timeout -k 10 200 python3 bench.py --config c4 --streams 1 --steps 200 --warmup 20 --full --no-cpu-baseline > "$O/c4.s1.json" 2> "$O/c4.s1.err"
 python3 -c "import json; d=json.load(open('$O/c4.s1.json')); print('c4 streams 1', d['fps'], 'fps', d['ms_per_step'], 'ms/frame')"
 timeout -k 10 200 python3 bench.py --config c4 --streams 3 --steps 200 --warmup 20 --no-cpu-baseline --no-kernel-timing > "$O/c4.s3.json" 2> "$O/c4.s3.err"
 python3 -c "import json; d=json.load(open('$O/c4.s3.json')); print('c4 streams 3', d['fps'], 'fps', d['ms_per_step'], 'ms/step')"

@@ -11,9 +11,9 @@ prof() {  # name, bench args
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$n -o run -- \
       python3 bench.py "$@" > $O/prof_$n.json 2> $O/prof_$n.err
 }
-timeout -k 10 400 python -u bench.py --steps 200 --warmup 20 > $O/c2_cpu.json 2> $O/c2_cpu.err &&
+timeout -k 10 400 python -u bench.py --full --steps 200 --warmup 20 > $O/c2_cpu.json 2> $O/c2_cpu.err &&
 timeout -k 10 300 python -m torch.distributed.run --nnodes 1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-    --master-port 29517 bench.py --dist-world1 --steps 100 --warmup 10 --no-cpu-baseline \
+    --master-port 29517 bench.py --full --dist-world1 --steps 100 --warmup 10 --no-cpu-baseline \
     > $O/c2_dist_world1.json 2> $O/c2_dist_world1.err &&
 prof c2 --steps 60 --warmup 10 --no-cpu-baseline &&
 prof c2s1 --steps 60 --warmup 10 --no-cpu-baseline --streams 1 &&

@@ -14,10 +14,10 @@ prof() {  # name, bench args
 timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 240 --timeout-method thread > $O/tests.log 2>&1 &&
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 &&
 timeout -k 10 1500 bash scripts/gpu_bench_all.sh r6_final/bench cpu > $O/bench_all.log 2>&1 &&
-timeout -k 10 300 python -u bench.py --config c4 --steps 200 --warmup 20 --streams 1 --no-cpu-baseline \
+timeout -k 10 300 python -u bench.py --full --config c4 --steps 200 --warmup 20 --streams 1 --no-cpu-baseline \
     > $O/c4s1.json 2> $O/c4s1.err &&
 timeout -k 10 300 python -m torch.distributed.run --nnodes 1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-    --master-port 29517 bench.py --dist-world1 --steps 200 --warmup 20 --no-cpu-baseline \
+    --master-port 29517 bench.py --full --dist-world1 --steps 200 --warmup 20 --no-cpu-baseline \
     > $O/c2_dist_world1.json 2> $O/c2_dist_world1.err &&
 prof c2s1 --steps 60 --warmup 10 --no-cpu-baseline --streams 1 --no-stream-probe &&
 prof c3 --config c3 --steps 6 --warmup 2 --streams 1 --iso-steps 2 --no-cpu-baseline --no-stream-probe &&

@@ -7,11 +7,11 @@ O=gpurun_out/${1:-r6_lrjob}
 mkdir -p $O
 timeout -k 10 600 python -u -m pytest tests/test_gpu_wls.py tests/test_gpu_rectify.py tests/test_gpu_parity.py tests/test_gpu_display.py tests/test_gpu_configs.py -m gpu -q -x \
     --timeout 240 --timeout-method thread > $O/tests.log 2>&1 &&
-timeout -k 10 200 python -u bench.py --config c4 --steps 200 --warmup 20 --streams 1 --no-cpu-baseline --no-stream-probe \
+timeout -k 10 200 python -u bench.py --full --config c4 --steps 200 --warmup 20 --streams 1 --no-cpu-baseline --no-stream-probe \
     > $O/c4s1_lrjob.json 2> $O/c4s1_lrjob.err &&
-SDR_FGS_LRJOB=0 timeout -k 10 200 python -u bench.py --config c4 --steps 200 --warmup 20 --streams 1 --no-cpu-baseline \
+SDR_FGS_LRJOB=0 timeout -k 10 200 python -u bench.py --full --config c4 --steps 200 --warmup 20 --streams 1 --no-cpu-baseline \
     --no-stream-probe > $O/c4s1_th.json 2> $O/c4s1_th.err &&
-timeout -k 10 200 python -u bench.py --config c4 --steps 200 --warmup 20 --streams 1 --no-cpu-baseline --no-stream-probe \
+timeout -k 10 200 python -u bench.py --full --config c4 --steps 200 --warmup 20 --streams 1 --no-cpu-baseline --no-stream-probe \
     > $O/c4s1_lrjob2.json 2> $O/c4s1_lrjob2.err &&
-timeout -k 10 200 python -u bench.py --config c4 --no-cpu-baseline --no-stream-probe > $O/c4.json 2> $O/c4.err
+timeout -k 10 200 python -u bench.py --full --config c4 --no-cpu-baseline --no-stream-probe > $O/c4.json 2> $O/c4.err
 echo lrjob-done

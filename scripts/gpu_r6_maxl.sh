@@ -7,7 +7,7 @@ O=gpurun_out/${1:-r6_maxl}
 mkdir -p $O
 for rep in 1 2; do
   for m in ${MS:-16 8}; do
-    SDR_FGS_LR_MAXL=$m timeout -k 10 200 python -u bench.py --config c4 --steps 200 --warmup 20 --streams 1 \
+    SDR_FGS_LR_MAXL=$m timeout -k 10 200 python -u bench.py --full --config c4 --steps 200 --warmup 20 --streams 1 \
         --no-cpu-baseline --no-stream-probe > $O/c4s1_m${m}_$rep.json 2> $O/c4s1_m${m}_$rep.err || exit 1
   done
 done

@@ -11,9 +11,9 @@ timeout -k 10 700 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_ad
 for rep in 1 2; do
   for v in prod base; do
     lib=$L/libsdr.so; [ "$v" != prod ] && lib=$L/libsdr-$v.so
-    SDR_BENCH_LIB=$lib timeout -k 10 200 python -u bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-stream-probe \
+    SDR_BENCH_LIB=$lib timeout -k 10 200 python -u bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-stream-probe \
         > $O/c2_${v}_$rep.json 2> $O/c2_${v}_$rep.err || exit 1
-    SDR_BENCH_LIB=$lib timeout -k 10 200 python -u bench.py --config c4 --steps 200 --warmup 20 --streams 1 \
+    SDR_BENCH_LIB=$lib timeout -k 10 200 python -u bench.py --full --config c4 --steps 200 --warmup 20 --streams 1 \
         --no-cpu-baseline --no-stream-probe > $O/c4s1_${v}_$rep.json 2> $O/c4s1_${v}_$rep.err || exit 1
     SDR_BENCH_LIB=$lib timeout -k 10 200 python -u bench.py --config c4 --steps 200 --warmup 20 \
         --no-cpu-baseline --no-stream-probe --no-kernel-timing > $O/c4_${v}_$rep.json 2> $O/c4_${v}_$rep.err || exit 1

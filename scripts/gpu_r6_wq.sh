@@ -11,9 +11,9 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_sweep.py tests/test_gpu_con
 for rep in 1 2; do
   for v in prod base; do
     lib=$L/libsdr.so; [ "$v" != prod ] && lib=$L/libsdr-$v.so
-    SDR_BENCH_LIB=$lib timeout -k 10 200 python -u bench.py --config c3 --steps 60 --warmup 6 --no-cpu-baseline \
+    SDR_BENCH_LIB=$lib timeout -k 10 200 python -u bench.py --full --config c3 --steps 60 --warmup 6 --no-cpu-baseline \
         --no-stream-probe > $O/c3_${v}_$rep.json 2> $O/c3_${v}_$rep.err || exit 1
-    SDR_BENCH_LIB=$lib timeout -k 10 200 python -u bench.py --config c5 --steps 60 --warmup 6 --no-cpu-baseline \
+    SDR_BENCH_LIB=$lib timeout -k 10 200 python -u bench.py --full --config c5 --steps 60 --warmup 6 --no-cpu-baseline \
         --no-stream-probe > $O/c5_${v}_$rep.json 2> $O/c5_${v}_$rep.err || exit 1
   done
 done

@@ -10,7 +10,7 @@ timeout -k 10 400 python -u -m pytest -x -v --timeout 200 --timeout-method threa
     tests/test_gpu_sweep.py::test_sweep_timeout_reported_by_next_call \
     tests/test_gpu_cloud.py::test_pcd_write_pipeline tests/test_gpu_wls.py::test_fgs_reciprocal_exact_every_mantissa \
     > $O/tests_new.log 2>&1 &&
-timeout -k 10 300 python -u bench.py --steps 200 --warmup 20 > $O/c2.json 2> $O/c2.err &&
-timeout -k 10 300 python -u bench.py --config c4 --steps 200 --warmup 20 --streams 1 --no-cpu-baseline \
+timeout -k 10 300 python -u bench.py --full --steps 200 --warmup 20 > $O/c2.json 2> $O/c2.err &&
+timeout -k 10 300 python -u bench.py --full --config c4 --steps 200 --warmup 20 --streams 1 --no-cpu-baseline \
     > $O/c4s1.json 2> $O/c4s1.err
 echo r6a-done

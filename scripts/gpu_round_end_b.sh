@@ -10,11 +10,11 @@ prof() {  # name, bench args
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$n -o run -- \
       python3 bench.py "$@" > $O/prof_$n.json 2> $O/prof_$n.err
 }
-prof c2 --steps 60 --warmup 10 --no-cpu-baseline &&
-prof c2s1 --steps 60 --warmup 10 --no-cpu-baseline --streams 1 &&
-prof c3 --config c3 --steps 6 --warmup 2 --streams 1 --iso-steps 2 --no-cpu-baseline &&
-prof c4s1 --config c4 --steps 60 --warmup 10 --streams 1 --no-cpu-baseline &&
-prof c5 --config c5 --steps 6 --warmup 2 --streams 1 --iso-steps 2 --no-cpu-baseline &&
+prof c2 --steps 60 --warmup 10 --full --no-cpu-baseline &&
+prof c2s1 --steps 60 --warmup 10 --full --no-cpu-baseline --streams 1 &&
+prof c3 --config c3 --steps 6 --warmup 2 --streams 1 --iso-steps 2 --full --no-cpu-baseline &&
+prof c4s1 --config c4 --steps 60 --warmup 10 --streams 1 --full --no-cpu-baseline &&
+prof c5 --config c5 --steps 6 --warmup 2 --streams 1 --iso-steps 2 --full --no-cpu-baseline &&
 for grp in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 240 rocprofv3 --pmc $grp --output-format csv -d $O/pmc_c3_$grp -o run -- \
       python3 bench.py --config c3 --steps 3 --warmup 1 --streams 1 --iso-steps 1 --no-cpu-baseline \

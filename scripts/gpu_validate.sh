@@ -10,5 +10,5 @@ timeout -k 10 600 python3 -u -m pytest tests -m gpu -q --timeout 120 --timeout-m
 tail -1 "$O/gputests.log"
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$O/smoke.log" 2>&1 || { tail -20 "$O/smoke.log"; exit 1; }
 tail -1 "$O/smoke.log"
-timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench.json" 2> "$O/bench.err"
+timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$O/bench.json" 2> "$O/bench.err"
 python3 -c "import json; d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]); print('bench', d['fps'], 'fps', d['value'], 'Mpix/s', d['roofline']['frac'])"

@@ -155,3 +155,35 @@ def test_c5_batch8_as_benched(oracle):
         assert np.array_equal(u32(xyz[i]), u32(rx)), f"frame {i}: xyz differs from the oracle"
     pipe.close()
     one.close()
+
+
+def test_bench_plain_run_dumps_last_step(oracle, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` times exactly K steps,
+    measures nothing beside them (roofline, kernels and cpu_baseline stay null) and writes what
+    its last timed step computed: with 4 resident frames, step W + K - 1 = 3 is the pair of seed 3,
+    whose disparity and XYZ equal the oracle's bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "outputs"
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3",
+                          "--warmup", "1", "--frames", "4", "--dump-outputs", str(out_dir)],
+                         cwd=root, capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["roofline"] is None and line["kernels"] is None and line["cpu_baseline"] is None
+    assert sorted(os.listdir(out_dir)) == ["disparity.npy", "outputs.json", "xyz.npy"]
+    disp, xyz = np.load(out_dir / "disparity.npy"), np.load(out_dir / "xyz.npy")
+    assert disp.dtype == np.float32 and xyz.dtype == np.float32
+    assert disp.shape == (1, 720, 1280) and xyz.shape == (1, 720, 1280, 3)
+    args = (0, 128, 5, 600, 2400, 1, 63, 12, 200, 2, sdr.MODE_SGBM)
+    L, R, _ = S.make_pair(720, 1280, 128, seed=3)
+    ref = oracle.sgbm_compute(L, R, oracle.make_params(*args))
+    assert np.array_equal(disp[0], ref.astype(np.float32)), f"{(disp[0] != ref).sum()} px differ"
+    assert np.array_equal(u32(xyz[0]), u32(oracle.reproject(oracle.disp_to_float(ref), S.REFERENCE_Q, True)))
