@@ -84,6 +84,30 @@ int sdr_sgbm_create(const sdr_sgbm_params* p, int device, sdr_sgbm** out);
 int sdr_sgbm_destroy(sdr_sgbm* h);
 int sdr_sgbm_set_params(sdr_sgbm* h, const sdr_sgbm_params* p);
 int sdr_sgbm_get_params(const sdr_sgbm* h, sdr_sgbm_params* p);
+
+/* The matching cost of a handle (not part of sdr_sgbm_params, whose layout is fixed): a new handle
+ * uses SDR_COST_BT, OpenCV's Birchfield-Tomasi cost on the Sobel-prefiltered and raw images.
+ *
+ * SDR_COST_CENSUS_9X7 is this project's own definition (OpenCV has no census cost):
+ *   - Descriptor T(y, x) of an 8-bit single-channel H x W image I, a 62-bit value in a uint64:
+ *     bit k (k = 0 the LSB) is 1 iff I(clamp(y+dy, 0, H-1), clamp(x+dx, 0, W-1)) < I(y, x)
+ *     (strict <, replicated border), k counting the offsets (dy, dx) in row-major order over
+ *     dy = -3..3, dx = -4..4 with the centre (0, 0) skipped; bits 62 and 63 are 0.  The transform
+ *     reads raw intensities: no Sobel prefilter, preFilterCap is ignored.
+ *   - Pixel cost pc(y, x, d) = popcount(T_left(y, x) XOR T_right(y, x - d)), in [0, 62], for the
+ *     same matched columns and disparities as the BT cost.
+ *   - Cost volume: C = P2 + the blockSize x blockSize box sum of pc with the BT path's border
+ *     rules (blockSize defaulting stays OpenCV's); everything after C is unchanged.
+ *   - Cost domain: 2*P2 + 62*blockSize^2 <= 32767, else SDR_ERR_LIMIT (the BT bound, which depends
+ *     on preFilterCap, does not apply).  A census block cost is at most 62*blockSize^2, so P1 / P2
+ *     scaled for BT are large for it.
+ *   - Limits, each refused loudly: 3-channel input (SDR_ERR_TYPE), effective blockSize > 11 and
+ *     numDisparities > 256 (SDR_ERR_LIMIT).
+ * Any strictly increasing intensity change of one image leaves the census disparity unchanged.
+ * The paired class-path launch needs equal cost types; matchers that differ run unpaired. */
+enum { SDR_COST_BT = 0, SDR_COST_CENSUS_9X7 = 1 };
+int sdr_sgbm_set_cost(sdr_sgbm* h, int cost); /* SDR_ERR_ARG on a null handle or an unknown value */
+int sdr_sgbm_get_cost(const sdr_sgbm* h);     /* SDR_COST_*, or a negative status on a null handle */
 /* HIP stream (hipStream_t) the handle launches on (NULL = the HIP null stream, e.g. torch's
  * default stream); a new handle uses a stream of its own, restored by sdr_sgbm_reset_stream.
  * Changing the stream orders the handle's earlier work before the new stream's.
@@ -398,6 +422,11 @@ int sdr_depth_coverage(sdr_display* h, const float* xyz, int width, int height, 
 size_t sdr_sgbm_scratch_bytes(const sdr_sgbm_params* p, int width, int height, int nframes);
 size_t sdr_sgbm_scratch_bytes_cn(const sdr_sgbm_params* p, int width, int height, int channels,
                                  int nframes);
+/* sdr_sgbm_scratch_bytes_cn for a handle of cost type `cost` (SDR_COST_*; host-only): 0, with
+ * sdr_last_error() saying why, when compute would refuse.  The census descriptors live in the BT
+ * operand planes' buffers, so the figure does not depend on the cost type. */
+size_t sdr_sgbm_scratch_bytes_ex(const sdr_sgbm_params* p, int cost, int width, int height,
+                                 int channels, int nframes);
 
 /* Timing with HIP events on the handle's stream.  level 1: per-stage timing of the last compute
  * (sdr_sgbm_last_timing: cost volume / path aggregation / LR+median+speckle, ms).  level 2 also
@@ -456,7 +485,9 @@ int sdr_stream_probe_ex(int device, size_t bytes, int iters, double* gbs3);
  * fused WTA pass), 5 = the right view's WTA keys [F][H][W] u32: (minS << 16 | 0xffff - x) of the
  * winning left pixel x (matched column) per right-view column, 0xffffffff where none (not built
  * when the LR check cannot fire), 6 = MODE_SGBM_3WAY's stripe-start cost rows [F][stripes][rows][W1][D]
- * s16 (rows = the largest stripe's count); stage 1 holds values only in the matched columns. */
+ * s16 (rows = the largest stripe's count); stage 1 holds values only in the matched columns,
+ * 7 = the census descriptors [F][2][H][W] u64 (index 0: the frame's left-role image, 1: its
+ * right-role image; an error when the last compute used SDR_COST_BT). */
 int sdr_sgbm_debug_stage(const sdr_sgbm* h, int stage, void* host_dst, size_t bytes);
 
 /* Page-locked host memory (the role of cv::cuda::HostMem): host buffers from sdr_host_alloc that

@@ -193,6 +193,8 @@ class StereoSGBM {
 public:
     enum { MODE_SGBM = SDR_MODE_SGBM, MODE_HH = SDR_MODE_HH, MODE_SGBM_3WAY = SDR_MODE_SGBM_3WAY,
            MODE_HH4 = SDR_MODE_HH4 };
+    // the matching cost (sdr.h): OpenCV's Birchfield-Tomasi cost, or the 9x7 census Hamming cost
+    enum { COST_BT = SDR_COST_BT, COST_CENSUS = SDR_COST_CENSUS_9X7 };
 
     static Ptr<StereoSGBM> create(int minDisparity = 0, int numDisparities = 16, int blockSize = 3,
                                   int P1 = 0, int P2 = 0, int disp12MaxDiff = 0, int preFilterCap = 0,
@@ -265,6 +267,12 @@ public:
     void setSpeckleRange(int v) { p_.speckleRange = v; push(); }
     int getMode() const { return p_.mode; }
     void setMode(int v) { p_.mode = v; push(); }
+    int getCostType() const {
+        const int c = sdr_sgbm_get_cost(h_);
+        if (c < 0) check(c);
+        return c;
+    }
+    void setCostType(int v) { check(sdr_sgbm_set_cost(h_, v)); }
 
     const sdr_sgbm_params& params() const { return p_; }
     sdr_sgbm* handle() const { return h_; }
@@ -315,7 +323,9 @@ namespace ximgproc {
 inline Ptr<StereoSGBM> createRightMatcher(const Ptr<StereoSGBM>& left) {
     sdr_sgbm_params r;
     sdr_right_matcher_params(&left->params(), &r);
-    return StereoSGBM::create(r, left->device());
+    Ptr<StereoSGBM> right = StereoSGBM::create(r, left->device());
+    right->setCostType(left->getCostType());
+    return right;
 }
 
 // cv::ximgproc::DisparityWLSFilter (stereo_disparity.cpp:11-13,31,36)
@@ -431,11 +441,13 @@ private:
 // class StereoDisparity (reference stereo_vision/include/stereo_disparity.hpp:8-24)
 class StereoDisparity {
 public:
-    explicit StereoDisparity(const Mat& Q_matrix, int device = 0) : Q(Q_matrix.clone()) {
+    explicit StereoDisparity(const Mat& Q_matrix, int device = 0, int cost = StereoSGBM::COST_BT)
+        : Q(Q_matrix.clone()) {
         // stereo_disparity.cpp:5-9: StereoSGBM::create(0, 80, 5, 8*5*5*3, 32*5*5*3, 1, 63, 12, 200, 2, 3WAY)
         matcher = StereoSGBM::create(0, 80, 5, 8 * 5 * 5 * 3, 32 * 5 * 5 * 3, 1, 63, 12, 200, 2,
                                      StereoSGBM::MODE_SGBM_3WAY, device);
-        right_matcher = ximgproc::createRightMatcher(matcher);          // :10
+        matcher->setCostType(cost);
+        right_matcher = ximgproc::createRightMatcher(matcher);          // :10 (copies the cost type)
         wls_filter = ximgproc::createDisparityWLSFilter(matcher);       // :11
         wls_filter->setLambda(8000.0);                                   // :12
         wls_filter->setSigmaColor(1.1);                                  // :13

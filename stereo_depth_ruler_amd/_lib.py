@@ -74,6 +74,8 @@ SIGNATURES = [
     ("sdr_sgbm_destroy", _i, [_vp]),
     ("sdr_sgbm_set_params", _i, [_vp, _PP]),
     ("sdr_sgbm_get_params", _i, [_vp, _PP]),
+    ("sdr_sgbm_set_cost", _i, [_vp, _i]),
+    ("sdr_sgbm_get_cost", _i, [_vp]),
     ("sdr_sgbm_set_stream", _i, [_vp, _vp]),
     ("sdr_sgbm_set_stream_ex", _i, [_vp, _vp, _i]),
     ("sdr_sgbm_reset_stream", _i, [_vp]),
@@ -149,6 +151,7 @@ SIGNATURES = [
     ("sdr_depth_coverage", _i, [_vp, _vp, _i, _i, _i, _c.POINTER(_c.c_double)]),
     ("sdr_sgbm_scratch_bytes", _sz, [_PP, _i, _i, _i]),
     ("sdr_sgbm_scratch_bytes_cn", _sz, [_PP, _i, _i, _i, _i]),
+    ("sdr_sgbm_scratch_bytes_ex", _sz, [_PP, _i, _i, _i, _i, _i]),
     ("sdr_sgbm_enable_timing", _i, [_vp, _i]),
     ("sdr_sgbm_last_timing", _i, [_vp, _c.POINTER(_c.c_float), _c.POINTER(_c.c_float),
                                   _c.POINTER(_c.c_float)]),

@@ -41,10 +41,13 @@ struct Eff {
     sdr::Geometry g;
     int mode, uniq, uniq_simd, disp12MaxDiff, ftzero, nstripes, invalid;
     int speckle_ws, speckle_diff, blockSize;
+    int cost;  // SDR_COST_*
 };
 
 // OpenCV's parameter defaulting (stereosgbm.cpp computeDisparitySGBM / SGBM3WayMainLoop ctor).
-int make_eff(const sdr_sgbm_params& p, int W, int H, Eff* e) {
+int make_eff(const sdr_sgbm_params& p, int W, int H, Eff* e, int cost = SDR_COST_BT) {
+    if (cost != SDR_COST_BT && cost != SDR_COST_CENSUS_9X7) return fail(SDR_ERR_ARG, "unknown cost type");
+    e->cost = cost;
     if (p.numDisparities <= 0 || p.numDisparities % 16 != 0)
         return fail(SDR_ERR_NUMDISP, "numDisparities must be positive and divisible by 16");
     if (p.numDisparities > 512) return fail(SDR_ERR_LIMIT, "numDisparities > 512 is not supported");
@@ -87,6 +90,12 @@ int make_eff(const sdr_sgbm_params& p, int W, int H, Eff* e) {
     // (minLp <= C) must fit a short.  Past it OpenCV's SIMD build wraps (short)delta0 and
     // saturates C while its scalar build computes them in int, so the reference's output is not
     // defined by the algorithm alone; the engine refuses instead of picking one of the two.
+    if (cost == SDR_COST_CENSUS_9X7) {
+        // the census pixel cost is a Hamming distance of 62-bit descriptors, whatever preFilterCap
+        if (2L * g.P2 + 62L * (2 * g.SW2 + 1) * (2 * g.SH2 + 1) > 32767)
+            return fail(SDR_ERR_LIMIT, "2*P2 + 62*blockSize^2 exceeds the int16 cost range");
+        return SDR_OK;
+    }
     // the largest pixel cost: BT of the prefiltered channel (values in [0, min(2*ftzero, 255)],
     // the uchar clip table) + BT of the raw one >> 2
     const long bmax = (long)(std::min(2 * e->ftzero, 255) + 63) * (2 * g.SW2 + 1) * (2 * g.SH2 + 1);
@@ -114,6 +123,11 @@ int check_frame(const Eff& e) {
     if ((size_t)g.H * g.W * 24 > (size_t)INT32_MAX)
         return fail(SDR_ERR_SIZE, "frame too large: the right image's cost planes span more than 2 GiB");
     if (!sdr::cost_supported(g)) return fail(SDR_ERR_ARG, "unsupported block shape");
+    if (e.cost == SDR_COST_CENSUS_9X7) {
+        // the shapes the BT cost sends to the two-pass launch_cost_generic
+        if (g.SH2 > 5) return fail(SDR_ERR_LIMIT, "the census cost supports blockSize <= 11");
+        if (g.D > 256) return fail(SDR_ERR_LIMIT, "the census cost supports numDisparities <= 256");
+    }
     return SDR_OK;
 }
 
@@ -122,6 +136,7 @@ int check_frame(const Eff& e) {
 int check_channels(const Eff& e, int cn) {
     if (cn != 1 && cn != 3) return fail(SDR_ERR_TYPE, "images must have 1 or 3 channels");
     if (cn == 1) return SDR_OK;
+    if (e.cost == SDR_COST_CENSUS_9X7) return fail(SDR_ERR_TYPE, "the census cost takes single-channel images");
     const sdr::Geometry& g = e.g;
     const long bmax = (long)cn * (std::min(2 * e.ftzero, 255) + 63) * (2 * g.SW2 + 1) * (2 * g.SH2 + 1);
     if (2L * g.P2 + bmax > 32767)
@@ -352,6 +367,9 @@ size_t stage_bytes(size_t n) { return (n + 255) & ~(size_t)255; }
 
 struct sdr_sgbm {
     sdr_sgbm_params p{};
+    int cost = SDR_COST_BT;  // SDR_COST_* (sdr_sgbm_set_cost)
+    // the census descriptors of the last compute (debug stage 7): bytes in planesR, 0 after a BT one
+    size_t census_bytes = 0;
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t own_stream = nullptr;
@@ -570,12 +588,13 @@ static bool can_pair(const Eff& a, const Eff& b) {
     return a.g.W1 == b.g.W1 && a.g.W1 > 0 && a.g.D == b.g.D && a.g.SW2 == b.g.SW2 && a.g.P1 == b.g.P1 &&
            a.g.P2 == b.g.P2 && a.mode == b.mode && a.uniq == b.uniq && a.uniq_simd == b.uniq_simd &&
            a.disp12MaxDiff == b.disp12MaxDiff && a.ftzero == b.ftzero && a.nstripes == b.nstripes &&
-           a.speckle_ws == 0 && b.speckle_ws == 0 && a.blockSize == b.blockSize;
+           a.speckle_ws == 0 && b.speckle_ws == 0 && a.blockSize == b.blockSize && a.cost == b.cost;
 }
 
 static int enqueue_compute(sdr_sgbm* h, const uint8_t* L, const uint8_t* R, int W, int H,
                            size_t stride, size_t fstride, int F, int16_t* out, int* out_min,
-                           int16_t** final_disp, int cn = 1, const sdr_sgbm_params* pair = nullptr) {
+                           int16_t** final_disp, int cn = 1, const sdr_sgbm_params* pair = nullptr,
+                           int pair_cost = SDR_COST_BT) {
     // a batch of an earlier call whose sweep wait gave up (its frames were written as INVALID):
     // reported here, by the next call, if no sdr_sgbm_last_status has reported it yet.  The
     // host copy is refreshed asynchronously after every sweep batch, so this check never waits
@@ -588,18 +607,20 @@ static int enqueue_compute(sdr_sgbm* h, const uint8_t* L, const uint8_t* R, int 
     }
     SDR_HIP(begin_call(h));
     Eff e;
-    int rc = make_eff(h->p, W, H, &e);
+    int rc = make_eff(h->p, W, H, &e, h->cost);
     if (rc) return rc;
     if ((rc = check_channels(e, cn))) return rc;
     if (pair) {
         Eff eb;
-        if ((rc = make_eff(*pair, W, H, &eb))) return rc;
+        if ((rc = make_eff(*pair, W, H, &eb, pair_cost))) return rc;
         if (!can_pair(e, eb) || (F & 1)) return fail(SDR_ERR_ARG, "matchers cannot be paired");
         e.g.split = F / 2;
         e.g.minDb = eb.g.minD;
         e.g.minX1b = eb.g.minX1;
     }
     h->lr_skipped = false;
+    h->census_bytes = 0;
+    const bool census = e.cost == SDR_COST_CENSUS_9X7;
     const sdr::Geometry& g = e.g;
     hipStream_t st = h->stream;
     const size_t px = (size_t)W * H;
@@ -700,7 +721,19 @@ static int enqueue_compute(sdr_sgbm* h, const uint8_t* L, const uint8_t* R, int 
     h->lr_frames = F;
     h->lr_d12 = e.disp12MaxDiff;
     uint32_t* d2 = h->lr_skipped ? nullptr : (uint32_t*)h->keys2.p;
-    { KTimer kt(h, SDR_KERNEL_PREFILTER); sdr::launch_prefilter(L, R, stride, fstride, W, H, F, e.ftzero, pl, st, g.split, d2); }
+    if (census) {
+        // the descriptors [F][2][H][W] take 16 of planesR's 24 bytes a pixel
+        uint64_t* desc = (uint64_t*)h->planesR.p;
+        pl.L = (uint32_t*)desc;
+        pl.R = desc + px;
+        pl.fstrideL = pl.fstrideR = 2 * px;
+        h->census_bytes = (size_t)F * 2 * px * 8;
+        KTimer kt(h, SDR_KERNEL_PREFILTER);
+        sdr::launch_census(L, R, stride, fstride, W, H, F, desc, st, g.split, d2);
+    } else {
+        KTimer kt(h, SDR_KERNEL_PREFILTER);
+        sdr::launch_prefilter(L, R, stride, fstride, W, H, F, e.ftzero, pl, st, g.split, d2);
+    }
 
     sdr::CostArgs ca{};
     ca.pl = pl;
@@ -733,7 +766,8 @@ static int enqueue_compute(sdr_sgbm* h, const uint8_t* L, const uint8_t* R, int 
         KTimer kt(h, SDR_KERNEL_COST);
         // blockSize 13..17 (within the int16 domain) or D > 256: the two-pass cost through the
         // idle L records
-        if (g.SH2 > 5 || g.D > 256) sdr::launch_cost_generic(g, ca, F, (uint32_t*)h->Lr.p, st);
+        if (census) sdr::launch_cost_census(g, ca, F, st);
+        else if (g.SH2 > 5 || g.D > 256) sdr::launch_cost_generic(g, ca, F, (uint32_t*)h->Lr.p, st);
         else sdr::launch_cost(g, ca, F, st);
     }
     if (h->timing) SDR_HIP(hipEventRecord(h->ev[1], st));
@@ -983,6 +1017,15 @@ int sdr_sgbm_get_params(const sdr_sgbm* h, sdr_sgbm_params* p) {
     return SDR_OK;
 }
 
+int sdr_sgbm_set_cost(sdr_sgbm* h, int cost) {
+    if (!h) return fail(SDR_ERR_ARG, "null handle");
+    if (cost != SDR_COST_BT && cost != SDR_COST_CENSUS_9X7) return fail(SDR_ERR_ARG, "unknown cost type");
+    h->cost = cost;
+    return SDR_OK;
+}
+
+int sdr_sgbm_get_cost(const sdr_sgbm* h) { return h ? h->cost : fail(SDR_ERR_ARG, "null handle"); }
+
 int sdr_sgbm_set_stream(sdr_sgbm* h, void* stream) {
     if (!h) return fail(SDR_ERR_ARG, "null handle");
     (void)hipSetDevice(h->device);
@@ -1031,9 +1074,14 @@ size_t sdr_sgbm_scratch_bytes(const sdr_sgbm_params* p, int width, int height, i
 
 size_t sdr_sgbm_scratch_bytes_cn(const sdr_sgbm_params* p, int width, int height, int channels,
                                  int nframes) {
+    return sdr_sgbm_scratch_bytes_ex(p, SDR_COST_BT, width, height, channels, nframes);
+}
+
+size_t sdr_sgbm_scratch_bytes_ex(const sdr_sgbm_params* p, int cost, int width, int height, int channels,
+                                 int nframes) {
     if (!p) return 0;
     Eff e;
-    if (make_eff(*p, width, height, &e) || check_channels(e, channels) || check_frame(e)) return 0;
+    if (make_eff(*p, width, height, &e, cost) || check_channels(e, channels) || check_frame(e)) return 0;
     std::vector<Stripe> st;
     return scratch_bytes(e, std::max(nframes, 1), &st, channels);
 }
@@ -1042,7 +1090,7 @@ size_t sdr_sgbm_scratch_bytes_cn(const sdr_sgbm_params* p, int width, int height
 // anything (an error return then leaves no DMA in flight from the staging buffer).
 static int precheck(const sdr_sgbm* h, int W, int H, int cn) {
     Eff e;
-    int rc = make_eff(h->p, W, H, &e);
+    int rc = make_eff(h->p, W, H, &e, h->cost);
     if (rc) return rc;
     if ((rc = check_channels(e, cn))) return rc;
     return e.g.W1 > 0 ? check_frame(e) : SDR_OK;
@@ -1365,11 +1413,12 @@ static int class_enqueue(sdr_sgbm* left, sdr_sgbm* right, sdr_wls* wls, const ui
     bool paired = false;
     if (right) {
         Eff el, er;
-        paired = make_eff(left->p, w2, h2, &el) == SDR_OK && make_eff(right->p, w2, h2, &er) == SDR_OK &&
+        paired = make_eff(left->p, w2, h2, &el, left->cost) == SDR_OK &&
+                 make_eff(right->p, w2, h2, &er, right->cost) == SDR_OK &&
                  can_pair(el, er);
     }
     if (paired) {
-        if ((rc = enqueue_compute(left, sl, sr, w2, h2, w2, px2, 2 * F, dl, nullptr, &fin, 1, &right->p)))
+        if ((rc = enqueue_compute(left, sl, sr, w2, h2, w2, px2, 2 * F, dl, nullptr, &fin, 1, &right->p, right->cost)))
             return rc;
     } else if (right) {
         if (!left->side) {
@@ -1529,8 +1578,10 @@ int sdr_sgbm_debug_stage(const sdr_sgbm* h, int stage, void* dst, size_t bytes) 
     if (!h || !dst) return fail(SDR_ERR_ARG, "null argument");
     const Buf* b = stage == 0 ? &h->C : stage == 1 ? &h->draw : stage == 2 ? &h->dlr
                  : stage == 3 ? &h->dfin : stage == 4 ? &h->Lr : stage == 5 ? &h->keys2
-                 : stage == 6 ? &h->Caux : nullptr;
+                 : stage == 6 ? &h->Caux : stage == 7 ? &h->planesR : nullptr;
     if (!b) return fail(SDR_ERR_ARG, "bad stage");
+    if (stage == 7 && !h->census_bytes) return fail(SDR_ERR_ARG, "the last compute did not use the census cost");
+    if (stage == 7 && bytes > h->census_bytes) return fail(SDR_ERR_ARG, "stage buffer smaller than requested");
     // front slack (the L records' is P-1 times C's)
     const size_t skip = stage == 0 ? h->path_slack * 2 : stage == 4 ? h->path_lslack * 2
                       : stage == 6 ? h->aux_slack * 2 : 0;

@@ -254,6 +254,16 @@ void launch_cost(const Geometry& g, const CostArgs& a, int F, hipStream_t st);
 size_t cost_generic_scratch_bytes(const Geometry& g, int F);
 void launch_cost_generic(const Geometry& g, const CostArgs& a, int F, uint32_t* h1, hipStream_t st);
 void launch_cost_cn3(const Geometry& g, const CostArgs& a, int F, hipStream_t st);  // pl.cn == 3
+// ---- census matching cost (sdr_census.hip; the definition: sdr.h SDR_COST_CENSUS_9X7) ----
+// 9x7 census descriptors of both images of F frames, desc u64 [F][2][H][W] (index 0: the frame's
+// left-role image, 1: its right-role image; frames >= split take the images swapped); d2fill as
+// launch_prefilter's
+void launch_census(const uint8_t* L, const uint8_t* R, size_t stride, size_t fstride, int W, int H,
+                   int F, uint64_t* desc, hipStream_t st, int split = 1 << 30, uint32_t* d2fill = nullptr);
+// launch_cost with the Hamming distance of the descriptors as the pixel cost (SH2 <= 5, D <= 256):
+// a.pl.L / a.pl.R are the left-role / right-role descriptor planes, u64 [H][W] a frame, frames
+// pl.fstrideL / pl.fstrideR u64 elements apart
+void launch_cost_census(const Geometry& g, const CostArgs& a, int F, hipStream_t st);
 void launch_paths(const Geometry& g, const PathLaunch& pl, int F, hipStream_t st);
 void launch_median3(const int16_t* src, int16_t* dst, int W, int H, int F, hipStream_t st);
 // median of the LR-checked map (computed per tile from the WTA map and the right-view keys)

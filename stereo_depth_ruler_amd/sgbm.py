@@ -30,6 +30,8 @@ except Exception:  # pragma: no cover
 
 MODE_SGBM, MODE_HH, MODE_SGBM_3WAY, MODE_HH4 = 0, 1, 2, 3
 UNIQ_AUTO, UNIQ_SCALAR, UNIQ_SIMD = 0, 1, 2
+# SDR_COST_* (include/sdr/sdr.h): OpenCV's Birchfield-Tomasi cost, or the 9x7 census Hamming cost
+COST_BT, COST_CENSUS = 0, 1
 # SDR_KERNEL_* (include/sdr/sdr.h)
 (KERNEL_PREFILTER, KERNEL_COST, KERNEL_PATHS, KERNEL_WTA_LR, KERNEL_MEDIAN, KERNEL_SPECKLE,
  KERNEL_REPROJECT, KERNEL_LR_CHECK, KERNEL_SWEEP, KERNEL_WLS_PREP, KERNEL_FGS, KERNEL_WLS_FINAL,
@@ -66,6 +68,13 @@ def set_handle_stream(h, device_index: int, stream=None):
     check(lib().sdr_sgbm_set_stream_ex(h, ctypes.c_void_p(s.cuda_stream), flags))
 
 
+def check_cost(v: int) -> int:
+    """A cost type returned by the engine (negative: a status)."""
+    if v < 0:
+        check(v)
+    return v
+
+
 def _Q(Q) -> ctypes.Array:
     q = np.ascontiguousarray(np.asarray(Q, dtype=np.float64).reshape(16))
     return (ctypes.c_double * 16)(*q.tolist())
@@ -77,22 +86,25 @@ class StereoSGBM:
     MODE_SGBM_3WAY = MODE_SGBM_3WAY
     MODE_HH4 = MODE_HH4
 
-    def __init__(self, params: SgbmParams, device: int = 0):
+    def __init__(self, params: SgbmParams, device: int = 0, cost: int = COST_BT):
         self._p = SgbmParams()
         ctypes.pointer(self._p)[0] = params
         self._device = int(device)
         h = ctypes.c_void_p()
         check(lib().sdr_sgbm_create(ctypes.byref(self._p), self._device, ctypes.byref(h)))
         self._h = h
+        if cost != COST_BT:
+            self.setCostType(cost)
 
     @classmethod
     def create(cls, minDisparity=0, numDisparities=16, blockSize=3, P1=0, P2=0, disp12MaxDiff=0,
                preFilterCap=0, uniquenessRatio=0, speckleWindowSize=0, speckleRange=0,
-               mode=MODE_SGBM, *, device=0, nstripes=4, uniq_rule=UNIQ_AUTO) -> "StereoSGBM":
-        """cv::StereoSGBM::create with OpenCV's defaults."""
+               mode=MODE_SGBM, *, device=0, nstripes=4, uniq_rule=UNIQ_AUTO, cost=COST_BT) -> "StereoSGBM":
+        """cv::StereoSGBM::create with OpenCV's defaults; cost: COST_BT (OpenCV's) or COST_CENSUS
+        (the 9x7 census Hamming cost, sdr.h SDR_COST_CENSUS_9X7)."""
         p = SgbmParams(minDisparity, numDisparities, blockSize, P1, P2, disp12MaxDiff, preFilterCap,
                        uniquenessRatio, speckleWindowSize, speckleRange, mode, nstripes, uniq_rule)
-        return cls(p, device)
+        return cls(p, device, cost)
 
     # ---- lifetime ----
     def close(self):
@@ -138,6 +150,14 @@ class StereoSGBM:
     def setSpeckleRange(self, v): self._set("speckleRange", v)
     def getMode(self): return self._p.mode
     def setMode(self, v): self._set("mode", v)
+
+    def getCostType(self):
+        """COST_BT or COST_CENSUS (sdr_sgbm_get_cost)."""
+        return check_cost(lib().sdr_sgbm_get_cost(self._h))
+
+    def setCostType(self, v):
+        """The matching cost of the following computes (sdr_sgbm_set_cost); parameters stay."""
+        check(lib().sdr_sgbm_set_cost(self._h, int(v)))
 
     # ---- compute ----
     def compute(self, left, right, disp=None):
@@ -260,7 +280,7 @@ class StereoSGBM:
 
     def debug_stage(self, stage: int, shape, dtype):
         """Copy an internal buffer of the last compute (0 C, 1 raw WTA, 2 LR, 3 final, 4 path costs,
-        5 disp2 keys)."""
+        5 disp2 keys, 6 3WAY stripe-start cost rows, 7 census descriptors)."""
         out = np.empty(shape, dtype)
         check(lib().sdr_sgbm_debug_stage(self._h, int(stage), out.ctypes.data, out.nbytes))
         return out
@@ -313,7 +333,7 @@ def createRightMatcher(matcher_left: StereoSGBM) -> StereoSGBM:
     """cv::ximgproc::createRightMatcher for an SGBM matcher."""
     r = SgbmParams()
     lib().sdr_right_matcher_params(ctypes.byref(matcher_left._p), ctypes.byref(r))
-    return StereoSGBM(r, matcher_left._device)
+    return StereoSGBM(r, matcher_left._device, matcher_left.getCostType())
 
 
 def reprojectImageTo3D(disparity, Q, handleMissingValues=False):

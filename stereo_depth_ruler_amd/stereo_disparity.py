@@ -18,7 +18,7 @@ import numpy as np
 
 from ._lib import SDRError, check, lib
 from .display import Display
-from .sgbm import MODE_SGBM_3WAY, StereoSGBM, _is_cuda, createRightMatcher, reprojectImageTo3D, torch
+from .sgbm import COST_BT, MODE_SGBM_3WAY, StereoSGBM, _is_cuda, createRightMatcher, reprojectImageTo3D, torch
 from .ximgproc import createDisparityWLSFilter
 
 
@@ -32,13 +32,13 @@ class StereoDisparity:
     _zrange_dev = {}
     _zrange_owner = None  # None: _zrange_host is current; else the device index holding it
 
-    def __init__(self, Q_matrix, device: int = 0):
+    def __init__(self, Q_matrix, device: int = 0, cost: int = COST_BT):
         self._device = int(device)
         self.Q = np.asarray(Q_matrix, dtype=np.float64).reshape(4, 4).copy()
         # stereo_disparity.cpp:5-9
         self.matcher = StereoSGBM.create(0, 80, 5, 8 * 5 * 5 * 3, 32 * 5 * 5 * 3, 1, 63, 12, 200, 2,
-                                         MODE_SGBM_3WAY, device=device)
-        self.right_matcher = createRightMatcher(self.matcher)  # :10
+                                         MODE_SGBM_3WAY, device=device, cost=cost)
+        self.right_matcher = createRightMatcher(self.matcher)  # :10 (copies the cost type)
         # :11 -- also switches the left matcher to disp12MaxDiff 1e6, speckle 0, uniqueness 0
         self.wls_filter = createDisparityWLSFilter(self.matcher)
         self.wls_filter.setLambda(8000.0)  # :12
