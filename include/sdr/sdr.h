@@ -415,6 +415,108 @@ int sdr_disparity_overlay(sdr_display* h, const uint8_t* vis, const uint8_t* lef
  * reference's: the handle's EMA history and range state are untouched. */
 int sdr_depth_coverage(sdr_display* h, const float* xyz, int width, int height, int col0, double* pct);
 
+/* ---- the ruler: StereoDisplayer::onMouseMeasure (stereo_displayer.cpp:24-63) and save_csvFile
+ * (:74-102) ----
+ * A measurement is the 3-D distance between two pixels of a frame.  sdr_measure_xyz* is the
+ * reference's own: it reads the computeDepth map at the two pixels and takes cv::norm of the Vec3f
+ * difference.  sdr_measure_disp* measures from the disparity map instead and is robust to holes:
+ *   - Sample at (x, y): the window [y-r, y+r] x [x-r, x+r] clipped to the image, in row-major
+ *     order.  A value d is valid iff it is finite, d > min_disp (strict) and, with a confidence
+ *     map, conf >= conf_min (a NaN confidence is invalid).  With n valid values, n < min_count
+ *     makes the sample invalid (disparity and XYZ NaN); otherwise d_med is the LOWER median,
+ *     element (n-1)/2 of the valid values in ascending order (a value of the window, never an
+ *     average), XYZ = reprojectImageTo3D's pixel formula at (x, y, d_med) with handleMissing off,
+ *     and the sample is valid iff X, Y and Z are finite (an endpoint that fails only this test
+ *     keeps its d_med and XYZ in the record, with its valid flag off).  radius 0 with min_count 1 gives the pixel
+ *     of reprojectImageTo3D bit for bit.  int16 disparities are read as (float)v * 0.0625f.
+ *   - Segment walk: n = max(|x1-x0|, |y1-y0|) + 1 samples, sample i at x0 + rdiv(i*(x1-x0), n-1),
+ *     y likewise, rdiv(a, b) = floor((2a + b) / (2b)); samples 0 and n-1 are the endpoints P0, P1.
+ *     Ties round up, towards +x / +y, not away from P0: the walk from P1 to P0 visits the same
+ *     pixels in reverse (rdiv(a - m*d, m) = rdiv(a, m) - d), so swapping the endpoints only swaps
+ *     p0 / p1 in the record, but the walk of a mirrored segment is not the mirror image.
+ *   - distance: the Vec3f difference per component in float, squares summed in double in x, y, z
+ *     order, double sqrt (cv::norm); NaN unless both endpoints are valid.
+ *   - profile = 1: every sample of the walk is evaluated: path_samples = n, path_valid the valid
+ *     ones, max_gap the longest run of invalid samples, z_min / z_max over valid samples (NaN with
+ *     none), max_dz the largest |Z_i - Z_prev| (float) over consecutive valid samples, invalid
+ *     ones skipped (NaN with fewer than two).  d_profile (nullable) is float [K][profile_cap][4]:
+ *     rows i < min(n, profile_cap) receive {X, Y, Z, d_med} (four NaNs for an invalid sample),
+ *     other rows stay untouched.  A buffer with profile_cap == 0 has no rows and counts as no
+ *     buffer (SDR_MEAS_PROFILE_TRUNCATED is not set).  profile = 0: the three counts are 0 and the
+ *     three floats NaN.
+ *   - A segment whose frame is outside [0, F) or with an endpoint outside the image: flag
+ *     SDR_MEAS_OUT_OF_RANGE, both points invalid, every float field NaN, nothing read.
+ *   - Every NaN the ruler computes (XYZ, distance) is written as the canonical quiet NaN
+ *     (0x7fc00000, 0x7ff8000000000000): the sign and payload of a computed NaN differ between
+ *     machines.  d_med is a value of the window and finite.
+ *   - XYZ-map mode: p0 / p1 are the map's values as read (their bits, NaNs included), d0 = d1 = NaN, n0 = n1 = 1, distance
+ *     as above without a validity gate (inf or NaN where the reference prints that); flag bits 0
+ *     and 1 say whether each point is finite; no window, no profile. */
+typedef struct sdr_segment {
+    int32_t frame, x0, y0, x1, y1;
+} sdr_segment;
+
+typedef struct sdr_ruler_params {
+    int32_t radius;      /* window radius r, 0..4 */
+    int32_t min_count;   /* >= 1 */
+    float min_disp;      /* valid iff d > min_disp */
+    float conf_min;      /* valid iff conf >= conf_min (with a confidence map) */
+    int32_t profile;     /* 0 / 1 */
+    int32_t profile_cap; /* rows per segment of d_profile */
+} sdr_ruler_params;
+
+enum {
+    SDR_MEAS_P0_VALID = 1, SDR_MEAS_P1_VALID = 2, SDR_MEAS_OUT_OF_RANGE = 4,
+    SDR_MEAS_PROFILE_TRUNCATED = 8 /* n > profile_cap with a profile buffer */
+};
+
+typedef struct sdr_measurement { /* 80 bytes */
+    float p0[3], p1[3];  /* XYZ of the endpoints */
+    float d0, d1;        /* their median disparities (px) */
+    double distance;
+    int32_t n0, n1;      /* valid values in each endpoint's window */
+    int32_t path_samples, path_valid, max_gap;
+    float z_min, z_max, max_dz;
+    uint32_t flags;      /* SDR_MEAS_* */
+    int32_t reserved;    /* 0 */
+} sdr_measurement;
+
+enum { SDR_DISP_F32 = 0, SDR_DISP_S16 = 1 };
+
+/* {0, 1, -1.0f, 0.0f, 0, 0}: the reference's single-pixel lookup on a minDisparity-0 matcher */
+void sdr_ruler_params_default(sdr_ruler_params* p);
+/* K segments on device maps, asynchronous on `stream`: d_disp [F][H][W] of disp_type (float px or
+ * int16 1/16 px), rows `stride` and frames `frame_stride` ELEMENTS apart; d_conf (nullable) dense
+ * float [F][H][W]; d_segs K sdr_segment; d_out K sdr_measurement; d_profile nullable.  K == 0 is
+ * SDR_OK with no launch.  Arguments are checked on the host before any device call. */
+int sdr_measure_disp_device(const void* d_disp, int disp_type, size_t stride, size_t frame_stride,
+                            int width, int height, int nframes, const float* d_conf,
+                            const double Q[16], const sdr_ruler_params* params,
+                            const sdr_segment* d_segs, int K, sdr_measurement* d_out,
+                            float* d_profile, void* stream);
+/* d_xyz [F][H][W][3] float, rows xyz_stride and frames xyz_frame_stride ELEMENTS apart. */
+int sdr_measure_xyz_device(const float* d_xyz, size_t xyz_stride, size_t xyz_frame_stride, int width,
+                           int height, int nframes, const sdr_segment* d_segs, int K,
+                           sdr_measurement* d_out, void* stream);
+/* Host-pointer versions (synchronous; per-thread persistent device buffers as sdr_reproject).  The
+ * host checks the arguments, not the segments' coordinates: a segment outside the maps is refused
+ * per segment by the kernel (SDR_MEAS_OUT_OF_RANGE), exactly as in the device versions. */
+int sdr_measure_disp(const void* disp, int disp_type, size_t stride, size_t frame_stride, int width,
+                     int height, int nframes, const float* conf, const double Q[16],
+                     const sdr_ruler_params* params, const sdr_segment* segs, int K,
+                     sdr_measurement* out, float* profile);
+int sdr_measure_xyz(const float* xyz, size_t xyz_stride, size_t xyz_frame_stride, int width,
+                    int height, int nframes, const sdr_segment* segs, int K, sdr_measurement* out);
+/* save_csvFile (stereo_displayer.cpp:74-102), byte for byte, of n records: with_header the line
+ * "Image, First_point,   Second_point, Distance\n", then per record
+ * "%d, [%d, %d],    [%d, %d], %.5f cm   \n" of image_index[i], the endpoints and distance / 10.
+ * segs[i] holds record i's endpoints (its frame is ignored).  Returns the byte length (without a
+ * terminator), writing the text and a terminator when buf != NULL (cap too small: SDR_ERR_ARG).
+ * Pure host code. */
+int sdr_measurements_csv(const int* image_index, const sdr_segment* segs,
+                         const sdr_measurement* records, int n, int with_header, char* buf,
+                         size_t cap);
+
 /* Bytes of device scratch the handle holds for the given frame shape (for capacity planning);
  * 0 when compute would refuse the shape or parameters.  sdr_sgbm_scratch_bytes is the CV_8UC1
  * figure, sdr_sgbm_scratch_bytes_cn takes the channel count (1 or 3: colour input holds three

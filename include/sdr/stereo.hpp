@@ -11,6 +11,8 @@
 //       stereo_vision/include/stereo_disparity.hpp:8-24
 //   sdr::Display                                             <- show_disparityMap / show_depthMap,
 //       the displayer's JET overlay and depth_coverage (stereo_displayer.cpp:105-118,164-173)
+//   sdr::Ruler / sdr::MeasurementLog                         <- onMouseMeasure / save_csvFile
+//       stereo_displayer.cpp:24-63,74-102
 //
 // sdr::Mat is a minimal owning image (rows, cols, OpenCV type code, row step) so that callers
 // can switch from cv::Mat without OpenCV present; when OpenCV is available, wrap cv::Mat data
@@ -19,7 +21,9 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -438,6 +442,108 @@ private:
     sdr_display* h_ = nullptr;
 };
 
+// The ruler: StereoDisplayer::onMouseMeasure (stereo_displayer.cpp:24-63) and save_csvFile (:74-102).
+using Measurement = sdr_measurement;
+struct Point {
+    int x = 0, y = 0;
+};
+
+class Ruler {
+public:
+    explicit Ruler(const Mat& Q_matrix, int radius = 0, int min_count = 1, float min_disp = -1.0f,
+                   float conf_min = 0.0f, bool profile = false) {
+        q_of(Q_matrix, q_);
+        sdr_ruler_params_default(&p_);
+        p_.radius = radius;
+        p_.min_count = min_count;
+        p_.min_disp = min_disp;
+        p_.conf_min = conf_min;
+        p_.profile = profile ? 1 : 0;
+    }
+    const sdr_ruler_params& params() const { return p_; }
+
+    // K segments on one disparity map (CV_32F in px, or CV_16S in 1/16 px) with an optional
+    // continuous CV_32F confidence map; profile (optional, with profile = true): rows of
+    // {X, Y, Z, d_med}, `cap` a segment, NaN where nothing is written
+    std::vector<Measurement> measure(const Mat& disparity, const std::vector<sdr_segment>& segs,
+                                     const Mat* conf = nullptr, std::vector<float>* profile = nullptr,
+                                     int cap = 0) const {
+        if (disparity.type != CV_32FC1 && disparity.type != CV_16SC1)
+            throw Exception(SDR_ERR_TYPE, "measure expects a CV_32F or CV_16S disparity");
+        const size_t es = elem_size(disparity.type);
+        if (conf && (conf->type != CV_32FC1 || conf->rows != disparity.rows || conf->cols != disparity.cols ||
+                     conf->step != (size_t)conf->cols * 4))
+            throw Exception(SDR_ERR_TYPE, "conf must be a continuous CV_32F map of the disparity's size");
+        std::vector<Measurement> out(segs.size());
+        sdr_ruler_params p = p_;
+        float* prof = nullptr;
+        if (profile && p.profile) {
+            p.profile_cap = cap;
+            profile->assign(segs.size() * (size_t)cap * 4, std::numeric_limits<float>::quiet_NaN());
+            prof = profile->empty() ? nullptr : profile->data();
+        }
+        check(sdr_measure_disp(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16,
+                               disparity.step / es, disparity.step / es * disparity.rows, disparity.cols,
+                               disparity.rows, 1, conf ? conf->ptr<float>(0) : nullptr, q_, &p,
+                               segs.empty() ? nullptr : segs.data(), (int)segs.size(),
+                               out.empty() ? nullptr : out.data(), prof));
+        return out;
+    }
+    Measurement measure(const Mat& disparity, Point a, Point b, const Mat* conf = nullptr) const {
+        return measure(disparity, {sdr_segment{0, a.x, a.y, b.x, b.y}}, conf)[0];
+    }
+    // the reference's own measurement on a computeDepth map (CV_32FC3)
+    std::vector<Measurement> measure_xyz(const Mat& depth, const std::vector<sdr_segment>& segs) const {
+        if (depth.type != CV_32FC3) throw Exception(SDR_ERR_TYPE, "measure_xyz expects a CV_32FC3 map");
+        std::vector<Measurement> out(segs.size());
+        check(sdr_measure_xyz(depth.ptr<float>(0), depth.step / 4, depth.step / 4 * depth.rows, depth.cols,
+                              depth.rows, 1, segs.empty() ? nullptr : segs.data(), (int)segs.size(),
+                              out.empty() ? nullptr : out.data()));
+        return out;
+    }
+    Measurement measure_xyz(const Mat& depth, Point a, Point b) const {
+        return measure_xyz(depth, {sdr_segment{0, a.x, a.y, b.x, b.y}})[0];
+    }
+
+private:
+    double q_[16];
+    sdr_ruler_params p_;
+};
+
+// measurement_record + save_csvFile: the reference's file, byte for byte
+class MeasurementLog {
+public:
+    void add(int image_index, const Measurement& rec, Point a, Point b) {
+        idx_.push_back(image_index);
+        segs_.push_back(sdr_segment{0, a.x, a.y, b.x, b.y});
+        recs_.push_back(rec);
+    }
+    size_t size() const { return recs_.size(); }
+    std::string to_csv(bool header = true) const {
+        const int n = (int)recs_.size();
+        const int len = sdr_measurements_csv(idx_.data(), segs_.data(), recs_.data(), n, header, nullptr, 0);
+        if (len < 0) check(len);
+        std::string s((size_t)len + 1, '\0');
+        const int rc = sdr_measurements_csv(idx_.data(), segs_.data(), recs_.data(), n, header, &s[0], s.size());
+        if (rc < 0) check(rc);
+        s.resize((size_t)len);
+        return s;
+    }
+    // appends (std::ios::app), the header included, as the reference does at every save
+    void save_csv(const std::string& path, bool header = true) const {
+        const std::string s = to_csv(header);
+        FILE* f = std::fopen(path.c_str(), "ab");
+        if (!f) throw Exception(SDR_ERR_ARG, "cannot open " + path);
+        const bool ok = std::fwrite(s.data(), 1, s.size(), f) == s.size();
+        if (std::fclose(f) != 0 || !ok) throw Exception(SDR_ERR_DEVICE, "write failed: " + path);
+    }
+
+private:
+    std::vector<int> idx_;
+    std::vector<sdr_segment> segs_;
+    std::vector<Measurement> recs_;
+};
+
 // class StereoDisparity (reference stereo_vision/include/stereo_disparity.hpp:8-24)
 class StereoDisparity {
 public:
@@ -469,6 +575,14 @@ public:
         Mat depth;
         reprojectImageTo3D(disparity, depth, Q);
         return depth;
+    }
+    // a Ruler with this object's Q that treats the matcher's invalid value (minDisparity - 1) as a hole
+    Ruler ruler(int radius = 0, int min_count = 1, float conf_min = 0.0f, bool profile = false) const {
+        return Ruler(Q, radius, min_count, (float)(matcher->getMinDisparity() - 1), conf_min, profile);
+    }
+    // onMouseMeasure (stereo_displayer.cpp:24-63) between two pixels of computeDisparity's map
+    Measurement measure(const Mat& disparity, Point a, Point b, int radius = 0, int min_count = 1) const {
+        return ruler(radius, min_count).measure(disparity, a, b);
     }
     const Ptr<StereoSGBM> get_matcher() const { return matcher; }
     const Mat& getConfidenceMap() const { return conf_map; }  // wls_filter->getConfidenceMap() (:36)

@@ -13,6 +13,7 @@ from .display import COLORMAP_JET, COLORMAP_TURBO, Display, colormap_lut  # noqa
 from .ximgproc import (  # noqa: F401
     DisparityWLSFilter, createDisparityWLSFilter, fastGlobalSmootherFilter,
 )
+from .ruler import MEASUREMENT_DTYPE, MeasurementLog, Ruler  # noqa: F401
 from .stereo_disparity import StereoDisparity  # noqa: F401
 
 __all__ = [
@@ -21,4 +22,5 @@ __all__ = [
     "MODE_SGBM", "MODE_HH", "MODE_SGBM_3WAY", "MODE_HH4", "WlsParams", "DisparityWLSFilter",
     "createDisparityWLSFilter", "fastGlobalSmootherFilter", "StereoDisparity", "Display",
     "colormap_lut", "COLORMAP_JET", "COLORMAP_TURBO", "host_empty", "COST_BT", "COST_CENSUS",
+    "Ruler", "MeasurementLog", "MEASUREMENT_DTYPE",
 ]

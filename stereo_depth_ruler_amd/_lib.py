@@ -49,6 +49,31 @@ class WlsParams(ctypes.Structure):
 FGS_PCR, FGS_THOMAS = 0, 1  # SDR_FGS_* (sdr_wls_params.fgs_solver)
 
 
+class Segment(ctypes.Structure):
+    """sdr_segment."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("frame", "x0", "y0", "x1", "y1")]
+
+
+class RulerParams(ctypes.Structure):
+    """sdr_ruler_params."""
+    _fields_ = [("radius", ctypes.c_int32), ("min_count", ctypes.c_int32),
+                ("min_disp", ctypes.c_float), ("conf_min", ctypes.c_float),
+                ("profile", ctypes.c_int32), ("profile_cap", ctypes.c_int32)]
+
+
+class Measurement(ctypes.Structure):
+    """sdr_measurement (80 bytes)."""
+    _fields_ = [("p0", ctypes.c_float * 3), ("p1", ctypes.c_float * 3), ("d0", ctypes.c_float),
+                ("d1", ctypes.c_float), ("distance", ctypes.c_double), ("n0", ctypes.c_int32),
+                ("n1", ctypes.c_int32), ("path_samples", ctypes.c_int32),
+                ("path_valid", ctypes.c_int32), ("max_gap", ctypes.c_int32),
+                ("z_min", ctypes.c_float), ("z_max", ctypes.c_float), ("max_dz", ctypes.c_float),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_int32)]
+
+
+DISP_F32, DISP_S16 = 0, 1  # SDR_DISP_*
+
+
 _lib = None
 _path = LIB_PATH
 
@@ -162,6 +187,14 @@ SIGNATURES = [
     ("sdr_stream_probe", _i, [_i, _sz, _i, _c.POINTER(_c.c_double)]),
     ("sdr_stream_probe_ex", _i, [_i, _sz, _i, _c.POINTER(_c.c_double)]),
     ("sdr_sgbm_debug_knob", _i, [_vp, _i, _i]),
+    ("sdr_ruler_params_default", None, [_c.POINTER(RulerParams)]),
+    ("sdr_measure_disp_device", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _c.POINTER(_c.c_double),
+                                     _c.POINTER(RulerParams), _vp, _i, _vp, _vp, _vp]),
+    ("sdr_measure_xyz_device", _i, [_vp, _sz, _sz, _i, _i, _i, _vp, _i, _vp, _vp]),
+    ("sdr_measure_disp", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _c.POINTER(_c.c_double),
+                              _c.POINTER(RulerParams), _vp, _i, _vp, _vp]),
+    ("sdr_measure_xyz", _i, [_vp, _sz, _sz, _i, _i, _i, _vp, _i, _vp]),
+    ("sdr_measurements_csv", _i, [_vp, _vp, _vp, _i, _i, _vp, _sz]),
     ("sdr_build_id", _c.c_char_p, []),
     ("sdr_last_error", _c.c_char_p, []),
     ("sdr_abi_version", _i, []),

@@ -5,6 +5,7 @@
   (BGR2GRAY, INTER_AREA 0.5x, left 3WAY + right matcher, WLS, /16) -> computeDepth, and with
   ``display=True`` the loop's display outputs (show_depthMap, show_disparityMap, the JET overlay
   on the half-size rectified left view; :164-173), frames of a batch in order through the EMAs.
+  With ``ruler=`` the loop's two-point measurement (onMouseMeasure, :24-63) runs on the same stream.
 * ``CloudEmit`` -- point_cloud/src/pcd_write.cpp:81-130 (``save_and_display_pointcloud``):
   side-by-side BGR frame -> split -> BGR2GRAY -> StereoSGBM::compute -> /16 ->
   reprojectImageTo3D(handleMissing) -> convertCVMatToPCL(left) -> VoxelGrid.
@@ -21,6 +22,7 @@ import numpy as np
 
 from ._lib import check, lib
 from .display import Display
+from .ruler import Ruler
 from .sgbm import MODE_SGBM_3WAY, StereoSGBM, _Q, createRightMatcher, set_handle_stream, torch
 from .ximgproc import createDisparityWLSFilter
 
@@ -32,7 +34,10 @@ def _vp(x):
 class LiveLoop:
     """The reference app's per-frame loop on one device (see module docstring)."""
 
-    def __init__(self, rectifier, Q, batch: int, device: int = 0, args=None, display: bool = False):
+    def __init__(self, rectifier, Q, batch: int, device: int = 0, args=None, display: bool = False,
+                 ruler=None):
+        """ruler (opt-in): a Ruler, or a dict of Ruler keywords (Q and min_disp = minDisparity - 1
+        are filled in): the loop then also keeps the WLS confidence map and gains measure()."""
         self.rect = rectifier
         self.W, self.H = rectifier.W, rectifier.H
         self.Q = np.asarray(Q, np.float64)
@@ -53,6 +58,15 @@ class LiveLoop:
         self.filtered = torch.empty((batch, h2, w2), dtype=torch.int16, **z)
         self.depth = torch.empty((batch, h2, w2, 3), dtype=torch.float32, **z)  # computeDepth()
         self.display = Display(device) if display else None
+        self.ruler, self.conf = None, None
+        if ruler is not None:
+            if not isinstance(ruler, Ruler):
+                kw = dict(ruler)
+                kw.setdefault("min_disp", float(self.left.getMinDisparity() - 1))
+                kw.setdefault("device", device)
+                ruler = Ruler(self.Q, **kw)
+            self.ruler = ruler
+            self.conf = torch.empty((batch, h2, w2), dtype=torch.float32, **z)  # getConfidenceMap()
         if display:
             self.left_rect = torch.empty((batch, self.H, self.W, 3), dtype=torch.uint8, **z)
             self.vis = torch.empty((batch, h2, w2), dtype=torch.uint8, **z)           # show_disparityMap
@@ -83,7 +97,9 @@ class LiveLoop:
         check(L.sdr_stereo_class_depth_device(self.left._h, self.right._h, self.wls._h,
                                               self.small_l.data_ptr(), self.small_r.data_ptr(),
                                               self.w2, self.h2, self.batch, self.disp.data_ptr(),
-                                              self.filtered.data_ptr(), None, _Q(self.Q),
+                                              self.filtered.data_ptr(),
+                                              self.conf.data_ptr() if self.conf is not None else None,
+                                              _Q(self.Q),
                                               self.depth.data_ptr()))
         if disp_on:  # stereo_displayer.cpp:164-173
             d, F, w2, h2 = self.display, self.batch, self.w2, self.h2
@@ -96,6 +112,16 @@ class LiveLoop:
                                                  self.W * 3, self.W * 3 * self.H, w2, h2, F, None, None,
                                                  self.overlay.data_ptr()))
         return self.filtered
+
+    def measure(self, segments, stream, profile_cap=None, profile_out=None):
+        """onMouseMeasure (stereo_displayer.cpp:24-63) on the frames the last enqueue left in
+        `disp`, with their confidence map, enqueued on `stream` (the stream of that enqueue: no
+        synchronise in between, host segments included).  Returns Ruler.measure_device's
+        (records, profile) tensors; profile_cap / profile_out as there."""
+        if self.ruler is None:
+            raise RuntimeError("LiveLoop was built without ruler=")
+        return self.ruler.measure_device(self.disp, segments, conf=self.conf, stream=stream,
+                                         profile_cap=profile_cap, profile_out=profile_out)
 
     def close(self):
         for o in (self.left, self.right, self.wls, self.display):

@@ -1,0 +1,313 @@
+"""The ruler: the reference's two-point measurement (StereoDisplayer::onMouseMeasure,
+stereo_vision/src/stereo_displayer.cpp:24-63) and its CSV log (save_csvFile, :74-102) on the HIP
+engine (csrc/sdr_ruler.hip; the definition is in include/sdr/sdr.h).
+
+* ``Ruler.measure_xyz(depth_map, segments)`` is the reference's own: the computeDepth map read at
+  the two pixels, ``cv::norm`` of the difference.
+* ``Ruler.measure(disparity, segments, conf=None)`` measures from the disparity map: each endpoint
+  is the lower median of the valid disparities in a (2r+1)^2 window, reprojected through Q; with
+  ``profile=True`` every pixel of the segment is sampled and the record reports the depth profile
+  (valid samples, longest hole, Z range, largest Z step), which shows whether both endpoints lie on
+  one surface.  ``radius=0, min_count=1`` equals the reference's lookup on finite pixels.
+
+A segment is ``(frame, x0, y0, x1, y1)`` (or ``(x0, y0, x1, y1)`` on frame 0), in pixels of the
+map.  The walk rounds ties towards +x / +y: from P1 to P0 it visits the same pixels in reverse, so
+a record does not depend on the direction (but for p0 / p1), while the walk of a mirrored segment is
+not the mirror image.
+
+numpy inputs go through the synchronous host ABI; torch CUDA tensors stay on the device.
+"""
+from __future__ import annotations
+
+import contextlib
+import ctypes
+
+import numpy as np
+
+from ._lib import DISP_F32, DISP_S16, RulerParams, SDRError, check, lib
+from .sgbm import _Q, _is_cuda, torch
+
+MEASUREMENT_DTYPE = np.dtype([
+    ("p0", "<f4", (3,)), ("p1", "<f4", (3,)), ("d0", "<f4"), ("d1", "<f4"), ("distance", "<f8"),
+    ("n0", "<i4"), ("n1", "<i4"), ("path_samples", "<i4"), ("path_valid", "<i4"),
+    ("max_gap", "<i4"), ("z_min", "<f4"), ("z_max", "<f4"), ("max_dz", "<f4"), ("flags", "<u4"),
+    ("reserved", "<i4")])
+assert MEASUREMENT_DTYPE.itemsize == 80
+
+# sdr_measurement.flags (SDR_MEAS_*)
+P0_VALID, P1_VALID, OUT_OF_RANGE, PROFILE_TRUNCATED = 1, 2, 4, 8
+
+
+def as_segments(segments) -> np.ndarray:
+    """(K, 5) int32 {frame, x0, y0, x1, y1} from (K, 5) / (K, 4) / a single 4- or 5-tuple."""
+    s = np.asarray(segments)
+    if s.size == 0:
+        return np.zeros((0, 5), np.int32)
+    if s.ndim == 1:
+        s = s[None, :]
+    if s.ndim != 2 or s.shape[1] not in (4, 5):
+        raise SDRError(-1, "segments must be (K, 5) {frame, x0, y0, x1, y1} or (K, 4) {x0, y0, x1, y1}")
+    if s.shape[1] == 4:
+        s = np.concatenate([np.zeros((s.shape[0], 1), s.dtype), s], axis=1)
+    return np.ascontiguousarray(s, dtype=np.int32)
+
+
+def _frames3(a, what):
+    """a as (F, H, W)."""
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3:
+        raise SDRError(-1, f"{what} must be (H, W) or (F, H, W)")
+    return a
+
+
+def _on_device(index: int):
+    """The host-pointer calls run on the thread's current device: make it `index` for the call."""
+    if torch is not None and torch.cuda.is_available():
+        return torch.cuda.device(index)
+    return contextlib.nullcontext()
+
+
+class _SegmentStaging:
+    """Host segments reach the device without a wait on the stream: a ring of page-locked slots,
+    each copied from with a non-blocking transfer on the measurement's stream and guarded by an
+    event recorded behind that transfer.  A slot is reused only after its event has completed,
+    which the host waits for only when `slots` uploads are still in flight."""
+
+    def __init__(self, slots: int = 8):
+        self._ring = [None] * slots
+        self._next = 0
+
+    def upload(self, host: np.ndarray, dev, stream):
+        K = host.shape[0]
+        if K == 0:
+            return torch.empty((0, 5), dtype=torch.int32, device=dev)
+        i = self._next
+        self._next = (i + 1) % len(self._ring)
+        slot = self._ring[i]
+        if slot is not None:
+            slot[1].synchronize()  # the slot's last transfer has left the buffer
+        if slot is None or slot[0].shape[0] < K:
+            slot = (torch.empty((max(K, 64), 5), dtype=torch.int32, pin_memory=True), torch.cuda.Event())
+            self._ring[i] = slot
+        buf, ev = slot
+        buf[:K].copy_(torch.from_numpy(host))
+        with torch.cuda.stream(stream):
+            out = buf[:K].to(dev, non_blocking=True)
+            ev.record(stream)
+        return out
+
+
+def _records(buf: np.ndarray) -> np.ndarray:
+    return buf.reshape(-1).view(MEASUREMENT_DTYPE)
+
+
+class Ruler:
+    def __init__(self, Q, radius: int = 0, min_count: int = 1, min_disp: float = -1.0,
+                 conf_min: float = 0.0, profile: bool = False, device: int = 0):
+        self.Q = np.asarray(Q, dtype=np.float64).reshape(4, 4).copy()
+        self.radius, self.min_count = int(radius), int(min_count)
+        self.min_disp, self.conf_min = float(min_disp), float(conf_min)
+        self.profile = bool(profile)
+        self.device = int(device)
+        self._staging = {}  # device index -> _SegmentStaging
+
+    def _upload_segments(self, host: np.ndarray, dev, stream):
+        st = self._staging.get(dev.index)
+        if st is None:
+            st = self._staging[dev.index] = _SegmentStaging()
+        return st.upload(host, dev, stream)
+
+    def _params(self, cap: int) -> RulerParams:
+        return RulerParams(self.radius, self.min_count, self.min_disp, self.conf_min,
+                           int(self.profile), int(cap))
+
+    # ---- disparity mode ----
+    def measure(self, disparity, segments, conf=None):
+        """Records (a MEASUREMENT_DTYPE array of K), and with profile=True also the profile,
+        float32 (K, cap, 4) rows {X, Y, Z, d_med} (NaN rows: invalid samples and rows past a
+        segment's samples), cap the longest segment's sample count."""
+        if _is_cuda(disparity):
+            rec, prof = self.measure_device(disparity, segments, conf)
+            out = _records(rec.cpu().numpy())
+            return (out, prof.cpu().numpy()) if self.profile else out
+        d = np.asarray(disparity)
+        if d.dtype not in (np.float32, np.int16):
+            raise SDRError(-5, "disparity must be float32 (px) or int16 (1/16 px)")
+        d = _frames3(d, "disparity")
+        if d.strides[2] != d.itemsize or d.strides[1] % d.itemsize or d.strides[0] % d.itemsize \
+                or min(d.strides) <= 0:
+            d = np.ascontiguousarray(d)
+        F, H, W = d.shape
+        c = None
+        if conf is not None:
+            c = np.ascontiguousarray(_frames3(np.asarray(conf, dtype=np.float32), "conf"))
+            if c.shape != d.shape:
+                raise SDRError(-1, "conf must have the disparity's shape")
+        segs = as_segments(segments)
+        K = segs.shape[0]
+        cap = self._cap(segs, W, H, F)
+        rec = np.zeros(K, MEASUREMENT_DTYPE)
+        prof = np.full((K, cap, 4), np.nan, np.float32) if self.profile else None
+        p = self._params(cap)
+        rs = d.strides[1] // d.itemsize
+        with _on_device(self.device):
+            rc = lib().sdr_measure_disp(
+                d.ctypes.data, DISP_F32 if d.dtype == np.float32 else DISP_S16, rs,
+                rs * H if F == 1 else d.strides[0] // d.itemsize, W, H, F,
+                c.ctypes.data if c is not None else None, _Q(self.Q), ctypes.byref(p),
+                segs.ctypes.data if K else None, K, rec.ctypes.data if K else None,
+                prof.ctypes.data if prof is not None and prof.size else None)
+        check(rc)
+        return (rec, prof) if self.profile else rec
+
+    @staticmethod
+    def _cap(segs: np.ndarray, W: int, H: int, F: int) -> int:
+        """Samples of the longest in-range segment."""
+        if segs.shape[0] == 0:
+            return 0
+        f, x0, y0, x1, y1 = segs.T.astype(np.int64)
+        ok = (f >= 0) & (f < F) & (x0 >= 0) & (x0 < W) & (x1 >= 0) & (x1 < W) & \
+             (y0 >= 0) & (y0 < H) & (y1 >= 0) & (y1 < H)
+        n = np.maximum(np.abs(x1 - x0), np.abs(y1 - y0)) + 1
+        return int(n[ok].max()) if ok.any() else 0
+
+    def measure_device(self, disparity, segments, conf=None, stream=None, profile_cap=None,
+                       profile_out=None):
+        """Enqueues the measurement of a CUDA disparity tensor (H, W) / (F, H, W), float32 or
+        int16 with unit stride along W, on `stream` (default: the current stream) and returns
+        (records, profile) without synchronising: records is a uint8 tensor (K, 80) (view its
+        host copy as MEASUREMENT_DTYPE), profile a float32 tensor (K, cap, 4) or None.
+        segments: host (K, 5) / (K, 4), uploaded through page-locked staging by a non-blocking
+        copy on `stream` (the host does not wait for the stream's earlier work), or a CUDA int32
+        tensor (K, 5) (then profile_cap defaults to max(W, H)).  profile_cap: rows a segment of the profile (0: the record's profile fields
+        only).  profile_out: a (K, cap, 4) tensor to write the profile into."""
+        d = disparity
+        if not _is_cuda(d) or d.dtype not in (torch.float32, torch.int16):
+            raise SDRError(-5, "measure_device expects a CUDA float32 or int16 tensor")
+        if d.dim() == 2:
+            d = d.unsqueeze(0)
+        if d.dim() != 3:
+            raise SDRError(-1, "disparity must be (H, W) or (F, H, W)")
+        F, H, W = d.shape
+        dev = d.device
+        s = stream if stream is not None else torch.cuda.current_stream(dev.index)
+        with torch.cuda.stream(s):
+            if d.stride(2) != 1 or d.stride(1) < W or d.stride(0) < d.stride(1):
+                d = d.contiguous()  # on `s`, ahead of the kernel
+            if conf is not None:
+                if not _is_cuda(conf) or conf.dtype != torch.float32 or conf.numel() != d.numel():
+                    raise SDRError(-5, "conf must be a CUDA float32 tensor of the disparity's shape")
+                conf = conf.contiguous()
+            if _is_cuda(segments):
+                if segments.dtype != torch.int32 or segments.dim() != 2 or segments.shape[1] != 5:
+                    raise SDRError(-5, "device segments must be an int32 tensor (K, 5)")
+                segs = segments.contiguous()
+                cap = max(W, H)
+            else:
+                host = as_segments(segments)
+                cap = self._cap(host, W, H, F)
+                segs = self._upload_segments(host, dev, s)
+            K = segs.shape[0]
+            if profile_cap is not None:
+                cap = int(profile_cap)
+            rec = torch.empty((K, 80), dtype=torch.uint8, device=dev)
+            prof = None
+            if self.profile:
+                if profile_out is not None:
+                    if (not _is_cuda(profile_out) or profile_out.dtype != torch.float32
+                            or not profile_out.is_contiguous() or profile_out.dim() != 3
+                            or profile_out.shape[0] != K or profile_out.shape[2] != 4):
+                        raise SDRError(-5, "profile_out must be a contiguous CUDA float32 tensor (K, cap, 4)")
+                    prof, cap = profile_out, profile_out.shape[1]
+                else:
+                    prof = torch.full((K, cap, 4), float("nan"), dtype=torch.float32, device=dev)
+            p = self._params(cap)
+            check(lib().sdr_measure_disp_device(
+                d.data_ptr(), DISP_F32 if d.dtype == torch.float32 else DISP_S16, d.stride(1),
+                d.stride(1) * H if F == 1 else d.stride(0), W, H, F,
+                conf.data_ptr() if conf is not None else None, _Q(self.Q), ctypes.byref(p),
+                segs.data_ptr() if K else None, K, rec.data_ptr() if K else None,
+                prof.data_ptr() if prof is not None and prof.numel() else None,
+                ctypes.c_void_p(s.cuda_stream)))
+        return rec, prof
+
+    # ---- XYZ-map mode (the reference's measurement) ----
+    def measure_xyz(self, depth_map, segments):
+        """onMouseMeasure on a computeDepth map (H, W, 3) / (F, H, W, 3): records of K."""
+        segs = as_segments(segments)
+        K = segs.shape[0]
+        if _is_cuda(depth_map):
+            x = depth_map
+            if x.dtype != torch.float32 or x.shape[-1] != 3 or x.dim() not in (3, 4):
+                raise SDRError(-5, "depth_map must be float32 (H, W, 3) or (F, H, W, 3)")
+            x = x.contiguous()
+            if x.dim() == 3:
+                x = x.unsqueeze(0)
+            F, H, W, _ = x.shape
+            st = torch.cuda.current_stream(x.device.index)
+            sd = self._upload_segments(segs, x.device, st)
+            rec = torch.empty((K, 80), dtype=torch.uint8, device=x.device)
+            check(lib().sdr_measure_xyz_device(x.data_ptr(), W * 3, W * H * 3, W, H, F,
+                                               sd.data_ptr() if K else None, K,
+                                               rec.data_ptr() if K else None,
+                                               ctypes.c_void_p(st.cuda_stream)))
+            return _records(rec.cpu().numpy())
+        x = np.asarray(depth_map)
+        if x.dtype != np.float32 or x.shape[-1] != 3 or x.ndim not in (3, 4):
+            raise SDRError(-5, "depth_map must be float32 (H, W, 3) or (F, H, W, 3)")
+        x = np.ascontiguousarray(x)
+        if x.ndim == 3:
+            x = x[None]
+        F, H, W, _ = x.shape
+        rec = np.zeros(K, MEASUREMENT_DTYPE)
+        with _on_device(self.device):
+            rc = lib().sdr_measure_xyz(x.ctypes.data, W * 3, W * H * 3, W, H, F,
+                                       segs.ctypes.data if K else None, K,
+                                       rec.ctypes.data if K else None)
+        check(rc)
+        return rec
+
+
+class MeasurementLog:
+    """The reference's measurement_record list and save_csvFile (stereo_displayer.cpp:52, 74-102).
+    A record carries 3-D points only, so add() also takes the segment's pixels."""
+
+    def __init__(self):
+        self.image_index = []
+        self.segments = []
+        self.records = []
+
+    def __len__(self):
+        return len(self.records)
+
+    def add(self, image_index: int, rec, segment):
+        """rec: one MEASUREMENT_DTYPE record; segment: (x0, y0, x1, y1) or (frame, x0, ...)."""
+        seg = as_segments(segment)
+        r = np.asarray(rec, dtype=MEASUREMENT_DTYPE).reshape(-1)
+        if seg.shape[0] != 1 or r.shape[0] != 1:
+            raise SDRError(-1, "add() takes one record and one segment")
+        self.image_index.append(int(image_index))
+        self.segments.append(seg[0])
+        self.records.append(r[0])
+
+    def to_csv(self, header: bool = True) -> str:
+        n = len(self.records)
+        idx = np.asarray(self.image_index, dtype=np.int32).reshape(n)
+        segs = np.ascontiguousarray(np.asarray(self.segments, dtype=np.int32).reshape(n, 5))
+        recs = np.asarray(self.records, dtype=MEASUREMENT_DTYPE).reshape(n)
+        args = (idx.ctypes.data if n else None, segs.ctypes.data if n else None,
+                recs.ctypes.data if n else None, n, int(bool(header)))
+        size = lib().sdr_measurements_csv(*args, None, 0)
+        if size < 0:
+            check(size)
+        buf = ctypes.create_string_buffer(size + 1)
+        size = lib().sdr_measurements_csv(*args, buf, size + 1)
+        if size < 0:
+            check(size)
+        return buf.raw[:size].decode()
+
+    def save_csv(self, path, header: bool = True):
+        """Appends (std::ios::app, as the reference does; it writes the header at every save)."""
+        with open(path, "ab") as f:
+            f.write(self.to_csv(header).encode())

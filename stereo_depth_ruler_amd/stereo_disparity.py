@@ -6,6 +6,7 @@ cvtColor(BGR2GRAY) -> resize(0.5, INTER_AREA) -> left SGBM (3WAY, d=80) and righ
 DisparityWLSFilter (lambda 8000, sigma 1.1) -> /16, all on the GPU (sdr_stereo_class_compute).
 computeDepth(disparity): reprojectImageTo3D(disparity, Q) (stereo_disparity.cpp:76-80), with the
 reference's quirk of a half-res disparity against the full-res Q kept as is.
+ruler(**kw): the live loop's two-point measurement (stereo_displayer.cpp:24-63) on the disparity map.
 show_disparityMap / show_depthMap (stereo_disparity.cpp:42-73, 83-124): the display maps with their
 EMA state (prev_vis / prev_depth_vis per object; the depth-range smoothing state is shared by all
 objects, as the reference's function-static doubles are), on the GPU (csrc/sdr_display.hip).
@@ -18,6 +19,7 @@ import numpy as np
 
 from ._lib import SDRError, check, lib
 from .display import Display
+from .ruler import Ruler
 from .sgbm import COST_BT, MODE_SGBM_3WAY, StereoSGBM, _is_cuda, createRightMatcher, reprojectImageTo3D, torch
 from .ximgproc import createDisparityWLSFilter
 
@@ -74,6 +76,13 @@ class StereoDisparity:
 
     def get_matcher(self) -> StereoSGBM:
         return self.matcher
+
+    def ruler(self, **kw) -> Ruler:
+        """A Ruler (the reference's onMouseMeasure, stereo_displayer.cpp:24-63) with this object's
+        Q that treats the matcher's invalid value, minDisparity - 1, as a hole."""
+        kw.setdefault("min_disp", float(self.matcher.getMinDisparity() - 1))
+        kw.setdefault("device", self._device)
+        return Ruler(self.Q, **kw)
 
     def _disp(self) -> Display:
         if self._display is None:
