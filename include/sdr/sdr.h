@@ -279,6 +279,39 @@ int sdr_fgs_filter_device(const uint8_t* d_guide, size_t guide_stride, int width
  * lambda > 2^100 so that its pivots stay below 2^126). Synchronous. */
 int sdr_fgs_rcp_selftest(int e, unsigned int* mismatches);
 
+/* Which kernel a filter's FGS launches take (host-only when cus != 0): the launchers' own
+ * dispatch code, environment knobs (SDR_FGS_LR, SDR_FGS_LRJOB, SDR_FGS_LR_MAXL) included, so a
+ * test can assert the instantiation a shape reaches.  `lines` is the lines a workgroup: the
+ * template argument L of k_fgs_lr, a job's L in k_fgs_lrjob, LPB of k_fgs_th, and for k_fgs_pcr the
+ * short lines sharing a workgroup. */
+enum {
+    SDR_FGS_KERNEL_NONE = 0,  /* no such launch (SDR_FGS_PCR has no coefficient jobs) */
+    SDR_FGS_KERNEL_LR = 1,    /* k_fgs_lr<lines> */
+    SDR_FGS_KERNEL_LRJOB = 2, /* k_fgs_lrjob, this job on `lines` lines a workgroup */
+    SDR_FGS_KERNEL_TH = 3,    /* k_fgs_th<two right-hand sides, lines> */
+    SDR_FGS_KERNEL_PCR = 4    /* k_fgs_pcr */
+};
+typedef struct sdr_fgs_launch {
+    int32_t kernel; /* SDR_FGS_KERNEL_* */
+    int32_t lines;
+} sdr_fgs_launch;
+typedef struct sdr_fgs_plan {
+    sdr_fgs_launch row_pass, col_pass; /* the passes along the rows (lines of `width` samples) and
+                                          along the columns */
+    sdr_fgs_launch row_job, col_job;   /* their coefficient jobs, in the filter's first job launch
+                                          (the jobs of its first 8 passes) */
+    int32_t cus;                       /* the compute units the plan holds for (SDR_FGS_THOMAS) */
+    int32_t reserved;
+} sdr_fgs_plan;
+/* The plan of one filter call on width x height lines (the WLS filter: its ROI), nframes frames
+ * a launch (sdr_fgs_filter_device: 1), nimg = 1 or 2 right-hand sides solved together (the WLS
+ * filter: 2; sdr_fgs_filter_device solves a stack in pairs and a left-over image alone), num_iter
+ * iterations (the job launch holds min(2 * num_iter, 8) jobs, which k_fgs_th's choice depends on).
+ * cus = 0 asks the current device for its compute units; any other value keeps the call off the
+ * GPU.  SDR_ERR_SIZE where SDR_FGS_PCR would refuse the size. */
+int sdr_fgs_plan_query(int width, int height, int nframes, int nimg, int num_iter, int solver,
+                       int cus, sdr_fgs_plan* out);
+
 /* ---- ingest in front of the path: StereoRectifier + SBS split ----
  * cv::initUndistortRectifyMap(K, dist, R, P, size, CV_16SC2, map1, map2)   stereo_rectifier.cpp:7-11
  * computed on the device (f64, OpenCV's scalar loop): map1 int16 [H][W][2], map2 uint16 [H][W]

@@ -49,6 +49,34 @@ class WlsParams(ctypes.Structure):
 FGS_PCR, FGS_THOMAS = 0, 1  # SDR_FGS_* (sdr_wls_params.fgs_solver)
 
 
+FGS_KERNELS = {0: "none", 1: "lr", 2: "lrjob", 3: "th", 4: "pcr"}  # SDR_FGS_KERNEL_*
+
+
+class FgsLaunch(ctypes.Structure):
+    """sdr_fgs_launch: the kernel family and its lines a workgroup."""
+    _fields_ = [("kernel", ctypes.c_int32), ("lines", ctypes.c_int32)]
+
+    def as_tuple(self):
+        return FGS_KERNELS[self.kernel], self.lines
+
+
+class FgsPlan(ctypes.Structure):
+    """sdr_fgs_plan (sdr_fgs_plan_query)."""
+    _fields_ = [("row_pass", FgsLaunch), ("col_pass", FgsLaunch), ("row_job", FgsLaunch),
+                ("col_job", FgsLaunch), ("cus", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+def fgs_plan(w, h, nframes=1, nimg=2, num_iter=3, solver=FGS_THOMAS, cus=0):
+    """The kernels an FGS call on w x h takes, as {"row_pass": (family, lines), "col_pass": ...,
+    "row_job": ..., "col_job": ..., "cus": n}; cus = 0 asks the current device."""
+    p = FgsPlan()
+    check(lib().sdr_fgs_plan_query(int(w), int(h), int(nframes), int(nimg), int(num_iter),
+                                   int(solver), int(cus), ctypes.byref(p)))
+    plan = {k: getattr(p, k).as_tuple() for k in ("row_pass", "col_pass", "row_job", "col_job")}
+    plan["cus"] = p.cus
+    return plan
+
+
 class Segment(ctypes.Structure):
     """sdr_segment."""
     _fields_ = [(n, ctypes.c_int32) for n in ("frame", "x0", "y0", "x1", "y1")]
@@ -160,6 +188,7 @@ SIGNATURES = [
     ("sdr_fgs_filter_device", _i, [_vp, _sz, _i, _i, _c.c_double, _c.c_double, _c.c_double, _i,
                                    _vp, _i, _i, _vp]),
     ("sdr_fgs_rcp_selftest", _i, [_i, _c.POINTER(_c.c_uint)]),
+    ("sdr_fgs_plan_query", _i, [_i, _i, _i, _i, _i, _i, _i, _c.POINTER(FgsPlan)]),
     ("sdr_colormap_lut", _i, [_i, _vp]),
     ("sdr_display_create", _i, [_i, _c.POINTER(_vp)]),
     ("sdr_display_destroy", _i, [_vp]),

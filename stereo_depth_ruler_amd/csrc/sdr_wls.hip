@@ -13,13 +13,13 @@
 //   k_wls_conf     left discontinuity (inline) + discontinuity-aware LR check -> confidence
 //                  x255 (full map for getConfidenceMap) and the two FGS inputs conf*d, conf,
 //                  compacted to the ROI
-//   k_fgs_pcr      one FGS pass (rows or columns), the default solver (SDR_FGS_PCR): every line's
+//   k_fgs_pcr      one FGS pass (rows or columns), the opt-in solver (SDR_FGS_PCR): every line's
 //                  tridiagonal system solved by parallel cyclic reduction in LDS, a 256-thread
 //                  workgroup per line (or per G short lines), both right-hand sides at once, the
 //                  diagonal carried as the row sum (oracle/wls_oracle.c fgs_line_pcr: every term
 //                  non-negative, ~200x closer to the exact solution than the sequential sweep);
 //                  rows and columns are both read in place from the row-major images
-//   k_fgs_sweep    one FGS pass with the sequential solver (SDR_FGS_THOMAS, ximgproc's own
+//   k_fgs_sweep    one FGS pass with the sequential solver (SDR_FGS_THOMAS, the default: ximgproc's own
 //                  elimination order, bit-exact with oracle/wls_oracle.c fgs_line): lane = line
 //                  over k-major data, PF samples loaded ahead in registers; one lane per line
 //                  leaves the chip nearly idle (6-9 waves at 640x360: ~112 us per pass)
@@ -522,7 +522,10 @@ __device__ __forceinline__ void th_write_job_phase(const FgsCoefJob& J, size_t f
                 t = t || (fabsf(x) < tiny && x != 0.0f && c * CH + j <= last && l0 + l < J.nl);
             }
         }
-        if (lane == 0) *(int*)(orow + kThFlags + (c & 1) * 4) = __builtin_amdgcn_ballot_w64(t) != 0;
+        // (the vote before the branch: inside it only lane 0 would take part, and the flag would
+        // see 16 of the chunk's 1024 weights)
+        const bool any = __builtin_amdgcn_ballot_w64(t) != 0;
+        if (lane == 0) *(int*)(orow + kThFlags + (c & 1) * 4) = any;
     };
     th_barrier();
     if (nch > 0) flag(0);
@@ -1825,12 +1828,21 @@ static void launch_fgs_th_lpb(const dim3& grid, const FgsThArgs& a, bool two, hi
     else hipLaunchKernelGGL((k_fgs_th<false, LPB>), grid, dim3(256), 0, st, a);
 }
 
-// One k_fgs_th launch: the pass (a.nl lines; none when !pass) or its jobs, with the fewest lines
-// a workgroup (LPB) whose workgroups still all fit on the chip at once (one a CU: the LDS ring),
+// The dispatch decisions of the sequential solver's three launchers, as pure host functions: the
+// launchers below and sdr_fgs_plan_query (the tests' view of which instantiation a shape reaches)
+// run the same code, environment knobs included.
+
+// pass p of a filter: a row pass (even p: the image's rows are the lines) or a column pass
+static void fgs_pass_shape(int p, int w, int h, int* nl, int* n) {
+    const bool rows = (p & 1) == 0;
+    *nl = rows ? h : w;
+    *n = rows ? w : h;
+}
+
+// k_fgs_th's lines a workgroup for the pass (a.nl lines; none when !pass) or its jobs: the fewest
+// (LPB) whose workgroups still all fit on a chip of `cus` CUs at once (one a CU: the LDS ring),
 // so that every chain runs on a CU's memory pipeline shared with as few lines as possible.
-static void launch_fgs_th(FgsThArgs a, bool pass, bool two, int F, hipStream_t st) {
-    const int cus = device_cus();
-    int lpb = 64;
+static int fgs_th_lpb(const FgsThArgs& a, bool pass, int F, int cus) {
 #ifdef SDR_TH_FORCE_LPB
     for (int c : {SDR_TH_FORCE_LPB}) {
 #else
@@ -1838,11 +1850,55 @@ static void launch_fgs_th(FgsThArgs a, bool pass, bool two, int F, hipStream_t s
 #endif
         int blocks = pass ? (a.nl + c - 1) / c : 0;
         for (int j = 0; j < a.njobs; j++) blocks += (a.job[j].nl + c - 1) / c;
-        if ((long long)blocks * F <= cus) {
-            lpb = c;
-            break;
-        }
+        if ((long long)blocks * F <= cus) return c;
     }
+    return 64;
+}
+
+// k_fgs_lr's lines a workgroup for a pass of lines of n samples: the largest L of 16, 8, 4, 2
+// (at most SDR_FGS_LR_MAXL) whose lines fit in LDS, n <= 6 * 1024 / L; 0: take k_fgs_th (one
+// right-hand side, longer lines, SDR_FGS_LR=0).
+static int fgs_lr_lines(int n, bool two) {
+    static const bool off = getenv("SDR_FGS_LR") && atoi(getenv("SDR_FGS_LR")) == 0;  // A/B knob
+    if (!two || off) return 0;
+    // at most 8 lines a workgroup by default (profiles/r6_fgs_lr_maxl.txt, C4): the 360-sample
+    // column passes on 16 lines ran ~15 % slower a sample than the row passes on 8 (the four rows'
+    // reads of 16 distinct lines conflict in LDS); capped at 8, one stream 0.4195 -> 0.413 ms with
+    // 6 frames in flight unchanged within noise; at 4, one stream 0.4123 ms but 6 frames in flight
+    // 4128 -> 3948 fps (a workgroup of ~147 KiB LDS per CU, 4x as many)
+    static const int maxl = getenv("SDR_FGS_LR_MAXL") ? atoi(getenv("SDR_FGS_LR_MAXL")) : 8;  // A/B knob
+    for (int L : {16, 8, 4, 2})
+        if (L <= maxl && n <= kLrChunks * 1024 / L) return L;
+    return 0;
+}
+
+// k_fgs_lrjob's plan for the jobs of c: each job's lines a workgroup (job.lpb: the largest L of
+// 16, 8, 4 whose lines fit in LDS, n <= 6 * 1024 / L) and workgroups (job.blocks); returns the
+// launch's workgroups a frame, or 0 when any job's lines do not fit (or SDR_FGS_LRJOB=0): then
+// every job of the launch takes k_fgs_th.
+static int fgs_lrjob_plan(FgsThArgs& c) {
+    static const bool off = getenv("SDR_FGS_LRJOB") && atoi(getenv("SDR_FGS_LRJOB")) == 0;  // A/B knob
+    if (off || c.njobs <= 0) return 0;
+    int blocks = 0;
+    for (int j = 0; j < c.njobs; j++) {
+        FgsCoefJob& J = c.job[j];
+        J.lpb = 0;
+        for (int L : {16, 8, 4})  // (2 lines: the weights' 8-byte rows are not whole DMA pieces)
+            if (J.n <= kLrChunks * 1024 / L) {
+                J.lpb = L;
+                break;
+            }
+        if (!J.lpb) return 0;
+        J.blocks = (J.nl + J.lpb - 1) / J.lpb;
+        blocks += J.blocks;
+    }
+    return blocks;
+}
+
+// One k_fgs_th launch: the pass (a.nl lines; none when !pass) or its jobs, fgs_th_lpb lines a
+// workgroup.
+static void launch_fgs_th(FgsThArgs a, bool pass, bool two, int F, hipStream_t st) {
+    const int lpb = fgs_th_lpb(a, pass, F, device_cus());
     a.main_blocks = pass ? (a.nl + lpb - 1) / lpb : 0;
     int blocks = a.main_blocks;
     for (int j = 0; j < a.njobs; j++) blocks += a.job[j].blocks = (a.job[j].nl + lpb - 1) / lpb;
@@ -1863,57 +1919,36 @@ static void launch_fgs_th(FgsThArgs a, bool pass, bool two, int F, hipStream_t s
     else launch_fgs_th_lpb<64>(grid, a, two, st);
 }
 
-// One k_fgs_lr launch when the pass's lines fit in LDS (two right-hand sides, n <= 6 * 1024 / L
-// for some L of 16, 8, 4, 2 lines a workgroup: the largest that fits); false: take k_fgs_th.
+// One k_fgs_lr launch when the pass's lines fit in LDS (fgs_lr_lines); false: take k_fgs_th.
 static bool launch_fgs_lr(FgsThArgs a, bool two, int F, hipStream_t st) {
-    static const bool off = getenv("SDR_FGS_LR") && atoi(getenv("SDR_FGS_LR")) == 0;  // A/B knob
-    if (!two || off) return false;
+    const int L = fgs_lr_lines(a.n, two);
+    if (!L) return false;
 #ifdef SDR_TH_STAMPS
     static int slot = 0;
     a.dbg = slot++ & 15;
 #else
     a.dbg = -1;
 #endif
-    // at most 8 lines a workgroup by default (profiles/r6_fgs_lr_maxl.txt, C4): the 360-sample
-    // column passes on 16 lines ran ~15 % slower a sample than the row passes on 8 (the four rows'
-    // reads of 16 distinct lines conflict in LDS); capped at 8, one stream 0.4195 -> 0.413 ms with
-    // 6 frames in flight unchanged within noise; at 4, one stream 0.4123 ms but 6 frames in flight
-    // 4128 -> 3948 fps (a workgroup of ~147 KiB LDS per CU, 4x as many)
-    static const int maxl = getenv("SDR_FGS_LR_MAXL") ? atoi(getenv("SDR_FGS_LR_MAXL")) : 8;  // A/B knob
-    for (int L : {16, 8, 4, 2}) {
-        if (L > maxl || a.n > kLrChunks * 1024 / L) continue;
-        const dim3 grid((a.nl + L - 1) / L, F);
-        if (L == 16) hipLaunchKernelGGL(k_fgs_lr<16>, grid, dim3(256), 0, st, a);
-        else if (L == 8) hipLaunchKernelGGL(k_fgs_lr<8>, grid, dim3(256), 0, st, a);
-        else if (L == 4) hipLaunchKernelGGL(k_fgs_lr<4>, grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_fgs_lr<2>, grid, dim3(256), 0, st, a);
-        return true;
-    }
-    return false;
+    const dim3 grid((a.nl + L - 1) / L, F);
+    if (L == 16) hipLaunchKernelGGL(k_fgs_lr<16>, grid, dim3(256), 0, st, a);
+    else if (L == 8) hipLaunchKernelGGL(k_fgs_lr<8>, grid, dim3(256), 0, st, a);
+    else if (L == 4) hipLaunchKernelGGL(k_fgs_lr<4>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_fgs_lr<2>, grid, dim3(256), 0, st, a);
+    return true;
 }
 
-// One k_fgs_lrjob launch for the jobs of c when every job's lines fit in LDS (n <= 6 * 1024 / L
-// for L of 16, 8, 4 lines a workgroup: the largest that fits, per job); false: take k_fgs_th.
+// One k_fgs_lrjob launch for the jobs of c when every job's lines fit in LDS (fgs_lrjob_plan);
+// false: take k_fgs_th.
 static bool launch_fgs_lrjob(FgsThArgs c, int F, hipStream_t st) {
-    static const bool off = getenv("SDR_FGS_LRJOB") && atoi(getenv("SDR_FGS_LRJOB")) == 0;  // A/B knob
-    if (off || c.njobs <= 0) return false;
-    int blocks = 0;
-    for (int j = 0; j < c.njobs; j++) {
-        FgsCoefJob& J = c.job[j];
-        J.lpb = 0;
-        for (int L : {16, 8, 4})  // (2 lines: the weights' 8-byte rows are not whole DMA pieces)
-            if (J.n <= kLrChunks * 1024 / L) {
-                J.lpb = L;
-                break;
-            }
-        if (!J.lpb) return false;
-        J.blocks = (J.nl + J.lpb - 1) / J.lpb;
-        blocks += J.blocks;
-    }
+    const int blocks = fgs_lrjob_plan(c);
+    if (!blocks) return false;
     c.main_blocks = 0;
     hipLaunchKernelGGL(k_fgs_lrjob, dim3(blocks, F), dim3(256), 0, st, c);
     return true;
 }
+
+// k_fgs_pcr's lines a workgroup: short lines share one, up to 1024 samples together
+static int pcr_lines(int n, int nlines) { return std::max(1, std::min(nlines, 1024 / n)); }
 
 // k_fgs_pcr instance for G*n samples per block: one equation per thread up to 1024 samples
 // (T = the samples rounded up to whole waves), 2 or 4 per thread of 1024 beyond
@@ -1923,7 +1958,7 @@ static int launch_pcr(float* U0, float* U1, const float* Cw, int w, int h, int F
     const int n = rows ? w : h, nlines = rows ? h : w;
     if (n > kPcrMaxN) return -1;
     // short lines: G per block so that a block holds up to 1024 samples
-    const int G = std::max(1, std::min(nlines, 1024 / n));
+    const int G = pcr_lines(n, nlines);
     const int N = G * n;
     // (one equation per thread: 2 or 4 per thread at 640x360 measured 12.8 -> 15.0 / 16.8 us a pass)
     const int ept = N <= 1024 ? 1 : N <= 2048 ? 2 : 4;
@@ -1994,8 +2029,7 @@ static int launch_fgs(const uint8_t* guide, size_t gstride, size_t gfstride, con
         auto pass_args = [&](int p) {
             FgsThArgs a{};
             const bool rows = (p & 1) == 0;
-            a.nl = rows ? h : w;
-            a.n = rows ? w : h;
+            fgs_pass_shape(p, w, h, &a.nl, &a.n);
             a.st = rows ? hp : wp;
             a.onp = rows ? wp : hp;
             a.fs = fsp;
@@ -2464,6 +2498,48 @@ int sdr_fgs_filter_device(const uint8_t* d_guide, size_t gstride, int w, int h, 
     WLS_HIP(sdr::scratch_free(scr, st));
     // the host LUT vector dies here: wait for its upload before returning
     WLS_HIP(hipStreamSynchronize(st));
+    return SDR_OK;
+}
+
+int sdr_fgs_plan_query(int w, int h, int nframes, int nimg, int num_iter, int solver, int cus,
+                       sdr_fgs_plan* out) {
+    if (!out) return sdr::set_error(SDR_ERR_ARG, "null argument");
+    if (w <= 0 || h <= 0 || nframes <= 0 || num_iter < 1 || cus < 0 || (nimg != 1 && nimg != 2))
+        return sdr::set_error(SDR_ERR_ARG, "bad size, nimg other than 1 or 2, num_iter < 1 or cus < 0");
+    if (solver != SDR_FGS_PCR && solver != SDR_FGS_THOMAS)
+        return sdr::set_error(SDR_ERR_ARG, "solver must be SDR_FGS_PCR or SDR_FGS_THOMAS");
+    *out = sdr_fgs_plan{};
+    if (solver == SDR_FGS_PCR) {
+        if (w > sdr::kPcrMaxN || h > sdr::kPcrMaxN)
+            return sdr::set_error(SDR_ERR_SIZE, "SDR_FGS_PCR solves lines of at most 4096 samples");
+        out->row_pass = {SDR_FGS_KERNEL_PCR, sdr::pcr_lines(w, h)};
+        out->col_pass = {SDR_FGS_KERNEL_PCR, sdr::pcr_lines(h, w)};
+        return SDR_OK;
+    }
+    if (!cus) cus = sdr::device_cus();
+    out->cus = cus;
+    const bool two = nimg == 2;
+    // the first launch of coefficient jobs, as launch_fgs builds it (job p: pass p's lines)
+    sdr::FgsThArgs c{};
+    for (int p = 0; p < 2 * num_iter && c.njobs < sdr::kFgsMaxJobs; p++) {
+        sdr::FgsCoefJob& j = c.job[c.njobs++];
+        sdr::fgs_pass_shape(p, w, h, &j.nl, &j.n);
+    }
+    sdr_fgs_launch* jobs[2] = {&out->row_job, &out->col_job};
+    if (sdr::fgs_lrjob_plan(c)) {
+        for (int p = 0; p < 2; p++) *jobs[p] = {SDR_FGS_KERNEL_LRJOB, c.job[p].lpb};
+    } else {
+        const int lpb = sdr::fgs_th_lpb(c, false, nframes, cus);
+        for (int p = 0; p < 2; p++) *jobs[p] = {SDR_FGS_KERNEL_TH, lpb};
+    }
+    sdr_fgs_launch* passes[2] = {&out->row_pass, &out->col_pass};
+    for (int p = 0; p < 2; p++) {
+        sdr::FgsThArgs a{};
+        sdr::fgs_pass_shape(p, w, h, &a.nl, &a.n);
+        const int L = sdr::fgs_lr_lines(a.n, two);
+        if (L) *passes[p] = {SDR_FGS_KERNEL_LR, L};
+        else *passes[p] = {SDR_FGS_KERNEL_TH, sdr::fgs_th_lpb(a, true, nframes, cus)};
+    }
     return SDR_OK;
 }
 

@@ -21,34 +21,16 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import stereo_depth_ruler_amd as sdr  # noqa: E402
-from stereo_depth_ruler_amd import synthetic as S  # noqa: E402
-from stereo_depth_ruler_amd.ximgproc import (  # noqa: E402
-    DisparityWLSFilter, createDisparityWLSFilter, fastGlobalSmootherFilter)
-from stereo_depth_ruler_amd._lib import FGS_PCR, FGS_THOMAS, WlsParams  # noqa: E402
+from stereo_depth_ruler_amd.ximgproc import createDisparityWLSFilter, fastGlobalSmootherFilter  # noqa: E402
+from stereo_depth_ruler_amd._lib import FGS_PCR, FGS_THOMAS  # noqa: E402
+
+from fgs_cases import bits, hyp_case, make_filter, sgbm_pair_maps  # noqa: E402
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _gpu():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def wls_from_oracle_params(q) -> DisparityWLSFilter:
-    """A device filter with exactly the oracle's parameters (ROI given as offsets)."""
-    p = WlsParams(q.lambda_, q.sigma_color, q.lrc_thresh, q.depth_disc_radius, q.roll_off,
-                  q.lambda_attenuation, q.num_iter, q.roi_x, 0, q.roi_y, 0, q.min_disp, q.fgs_solver)
-    return p
-
-
-def make_filter(q, W, H):
-    p = wls_from_oracle_params(q)
-    p.right_offset = W - q.roi_x - q.roi_w
-    p.bottom_offset = H - q.roi_y - q.roi_h
-    return DisparityWLSFilter(p)
 
 
 SOLVERS = [FGS_PCR, FGS_THOMAS]
@@ -100,16 +82,6 @@ def test_pcr_line_limit():
     with pytest.raises(sdr.SDRError):
         fastGlobalSmootherFilter(g, x, 8000.0, 1.1, solver=FGS_PCR)
     assert np.allclose(fastGlobalSmootherFilter(g, x, 8000.0, 1.1, solver=FGS_THOMAS), 1.0, rtol=1e-3)
-
-
-def sgbm_pair_maps(oracle, h, w, numD, seed, minD=0):
-    """Left / right disparity maps produced by the oracle SGBM on a synthetic pair, the way the
-    class path produces them (left matcher WLS-mutated, right matcher from createRightMatcher)."""
-    L, R, _ = S.make_pair(h, w, numD, seed=seed)
-    dl = oracle.sgbm_compute(L, R, oracle.make_params(minD, numD, 5, 600, 2400, 1000000, 63, 0, 0, 2, 2))
-    dr = oracle.sgbm_compute(R, L, oracle.make_params(-(minD + numD) + 1, numD, 5, 600, 2400, 1000000,
-                                                      63, 0, 0, 2, 2))
-    return L, dl, dr
 
 
 @pytest.mark.parametrize("solver", SOLVERS)
@@ -265,31 +237,6 @@ def test_wls_wide_roi_fallback(oracle):
         f.filter(dl, g, dr)
 
 
-def _hyp_case(oracle, rng, W, H, guide, lam, sigma):
-    """A WLS input of the verdict's hypothesis space: flat, binary-edge, noise
-    or scene guides; block-constant disparities with 10 % invalid pixels (a sparse confidence map)
-    for the synthetic guides, the matcher pair of a synthetic frame for `scene`."""
-    D = 80
-    if guide == "scene":
-        L, dl, dr = sgbm_pair_maps(oracle, H, W, D, int(rng.integers(1 << 30)))
-        g = L
-    else:
-        if guide == "flat":
-            g = np.full((H, W), int(rng.integers(0, 256)), np.uint8)
-        elif guide == "edge":
-            g = np.zeros((H, W), np.uint8)
-            g[:, int(rng.integers(1, W)):] = 255
-            g[int(rng.integers(1, H)):, :] ^= 255
-        else:
-            g = rng.integers(0, 256, (H, W), dtype=np.uint8)
-        blocks = rng.integers(0, D * 16, ((H + 7) // 8, (W + 7) // 8))
-        dl = np.repeat(np.repeat(blocks, 8, 0), 8, 1)[:H, :W].astype(np.int16)
-        dl[rng.random((H, W)) < 0.1] = -16
-        dr = -np.clip(dl, 0, None).astype(np.int16)
-    q = oracle.wls_params_for_sgbm(0, D, 5, W, H, lam, sigma)
-    return g, dl, dr, q
-
-
 def test_default_solver_hypothesis(oracle):
     """The default filter (createDisparityWLSFilter's parameters, SDR_FGS_THOMAS) bit-exact with the
     oracle's sequential restatement over random shapes up to 4096-sample rows and columns, lambda in
@@ -315,7 +262,7 @@ def test_default_solver_hypothesis(oracle):
         if guide == "scene" and (W < 100 or H < 8):
             guide = "noise"  # the matcher needs columns past numDisparities
         rng = np.random.default_rng(seed)
-        g, dl, dr, q = _hyp_case(oracle, rng, W, H, guide, float(np.exp(loglam)), sigma)
+        g, dl, dr, q = hyp_case(oracle, rng, W, H, guide, float(np.exp(loglam)), sigma)
         assert q.fgs_solver == FGS_THOMAS  # the oracle's default is ximgproc's order
         ref = oracle.wls_filter(dl, dr, g, q)
         f = make_filter(q, W, H)
