@@ -615,14 +615,25 @@ int sdr_stream_probe_ex(int device, size_t bytes, int iters, double* gbs3);
 /* Diagnostics: synchronously copy an internal buffer of the last compute to host memory.
  * stage 0 = cost volume C [F][H][W1][D] s16, 1 = WTA disparity before the LR check [F][H][W] s16,
  * 2 = after the LR check (computed from stages 1 and 5 on request: the pipeline's median computes
- * it per tile and never writes it), 3 = final (median + speckle), 4 = path costs L
- * [P-1][F][H][W1][D] s16 (every direction but top-to-bottom, whose L is consumed on chip by the
- * fused WTA pass), 5 = the right view's WTA keys [F][H][W] u32: (minS << 16 | 0xffff - x) of the
+ * it per tile and never writes it), 3 = final (median + speckle), 4 = the raw bytes of the path-cost
+ * records (every direction but top-to-bottom, whose L is consumed on chip by the fused WTA pass;
+ * the formats below), 5 = the right view's WTA keys [F][H][W] u32: (minS << 16 | 0xffff - x) of the
  * winning left pixel x (matched column) per right-view column, 0xffffffff where none (not built
  * when the LR check cannot fire), 6 = MODE_SGBM_3WAY's stripe-start cost rows [F][stripes][rows][W1][D]
  * s16 (rows = the largest stripe's count); stage 1 holds values only in the matched columns,
  * 7 = the census descriptors [F][2][H][W] u64 (index 0: the frame's left-role image, 1: its
- * right-role image; an error when the last compute used SDR_COST_BT). */
+ * right-role image; an error when the last compute used SDR_COST_BT).
+ *
+ * Stage 4, the path-cost records, pixel-interleaved in the summation order E, W, [N,] SE, SW[, NE,
+ * NW] (R = P-1 directions; frames R*H*W1*D*2 bytes apart in either format):
+ *  - int16: [F][H][W1][R][D] s16, the path costs L themselves.
+ *  - 12-bit (the default where it applies: P2 <= 4095, numDisparities = 128, MODE_SGBM, MODE_HH4 or
+ *    unbatched MODE_HH, and launches that run one chain a wave; SDR_PATH_REC=16 in the environment
+ *    when the handle is created forces int16): [F][H][W1][R][D/8] groups of 12 bytes, e = C - L
+ *    (0 <= e <= P2) of 8 consecutive disparities d0..d0+7.  As three little-endian u32 w0, w1, w2:
+ *    e[d0+2j] = w_j & 0xfff and e[d0+2j+1] = (w_j >> 16) & 0xfff for j = 0..2; e[d0+6] =
+ *    (w0 >> 12 & 0xf) | (w1 >> 12 & 0xf) << 4 | (w2 >> 12 & 0xf) << 8, and e[d0+7] the same from
+ *    bits 28..31.  A pixel's R records take R*D*3/2 bytes; the rest of a frame's span is unused. */
 int sdr_sgbm_debug_stage(const sdr_sgbm* h, int stage, void* host_dst, size_t bytes);
 
 /* Page-locked host memory (the role of cv::cuda::HostMem): host buffers from sdr_host_alloc that

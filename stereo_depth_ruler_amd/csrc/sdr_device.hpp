@@ -164,6 +164,11 @@ __device__ __forceinline__ Regs<K> load_buf(Rsrc r, uint32_t vofs, uint32_t sofs
         const auto t = __builtin_amdgcn_raw_buffer_load_b64(r, vofs, sofs, AUX);
         v.r[0] = t[0];
         v.r[1] = t[1];
+    } else if constexpr (K == 3) {
+        const auto t = __builtin_amdgcn_raw_buffer_load_b96(r, vofs, sofs, AUX);
+        v.r[0] = t[0];
+        v.r[1] = t[1];
+        v.r[2] = t[2];
     } else {
         static_assert(K % 4 == 0, "K = 1, 2 or a multiple of 4");
 #pragma unroll
@@ -193,6 +198,25 @@ __device__ __forceinline__ void store_buf_nt(Rsrc r, uint32_t vofs, uint32_t sof
                                                                v.r[4 * j + 3]},
                 r, vofs + 16 * j, sofs, AUX);
     }
+}
+
+// 12-bit path-cost records (PathLaunch::rec12; the layout: sdr.h, sdr_sgbm_debug_stage).  A record
+// holds e = C - L, 0 <= e <= P2 <= 4095, of a pixel's disparities in one direction.  Eight
+// consecutive disparities -- the packed pairs p0..p3 of a quad of producer lanes, the four words of
+// one consumer lane -- take three dwords: dword j is p_j with nibble j of each of p3's halves in
+// the free top nibble of its own halves.  Packing is one quad broadcast and three ops a lane,
+// unpacking nine ops for four words.
+constexpr int kDppQuadLane3 = 0xFF;  // quad_perm [3,3,3,3]
+__device__ __forceinline__ uint32_t rec12_pack(uint32_t p, int lane) {
+    const uint32_t p3 = dpp_mov<kDppQuadLane3>(p);
+    return p | (((p3 >> (4 * (lane & 3))) & 0x000f000fu) << 12);  // lane 3 of a quad stores nothing
+}
+__device__ __forceinline__ Regs<4> rec12_unpack(const Regs<3>& w) {
+    Regs<4> p;
+#pragma unroll
+    for (int j = 0; j < 3; j++) p.r[j] = w.r[j] & 0x0fff0fffu;
+    p.r[3] = ((w.r[0] >> 12) & 0x000f000fu) | ((w.r[1] >> 8) & 0x00f000f0u) | ((w.r[2] >> 4) & 0x0f000f00u);
+    return p;
 }
 
 __device__ __forceinline__ int lane_id() { return (int)__lane_id(); }

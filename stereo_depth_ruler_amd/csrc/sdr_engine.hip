@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -381,6 +382,9 @@ struct sdr_sgbm {
     Buf sweep, status;
     int* status_host = nullptr;
     int sweep_spin = sdr::kSweepSpin;  // debug knob SDR_DEBUG_SWEEP_SPIN
+    // SDR_PATH_REC=16 in the environment when the handle was created: int16 path-cost records
+    // always (A/B and tests; the default takes 12-bit records where enqueue_compute can)
+    bool rec16 = false;
     HostXfer hx;  // pinned staging of the host-pointer entry points
     Buf cls_bgr, cls_gray, cls_small, cls_dl, cls_wls, cls_f, cls_conf, cls_filt;
     int timing = 0;  // 0 off, 1 stage events, 2 stage + per-kernel events
@@ -842,6 +846,20 @@ static int enqueue_compute(sdr_sgbm* h, const uint8_t* L, const uint8_t* R, int 
         pl->prefix[0] = 0;
         for (int i = 0; i < pl->ndirs; i++) pl->prefix[i + 1] = pl->prefix[i] + pl->d[i].nchains;
     }
+    // The record format of this call, for both launches: e = C - L lies in [0, P2], so with P2 <=
+    // 4095 the chains' records take 12 bits a value (1.5 B instead of 2 B per cell and direction,
+    // written once and read once) and the fused pass rebuilds L = C - e exactly.  Not the sweep
+    // (k_sweep16 reads int16 records, and its up record is a sum of three), not 3WAY, and only
+    // where both launchers dispatch a kernel that implements it; the buffer keeps its int16 size.
+    const bool rec12 = !h->rec16 && !sweep && g.P2 >= 0 && g.P2 <= 4095 &&
+                       (e.mode == SDR_MODE_SGBM || e.mode == SDR_MODE_HH || e.mode == SDR_MODE_HH4) &&
+                       sdr::path_rec12_supported(g, pls, plS, nrec + 1, F);
+    if (rec12) {
+        const int recel = g.D * 3 / 4;  // int16 elements of one direction's record
+        pls.rec12 = plS.rec12 = 1;
+        pls.l_pix = plS.l_pix = nrec * recel;
+        for (int i = 0; i < pls.ndirs; i++) pls.d[i].out = Lr + (size_t)i * recel;
+    }
     { KTimer kt(h, SDR_KERNEL_PATHS); sdr::launch_paths(g, pls, F, st); }
     if (sweep) {
         char* sb = (char*)h->sweep.p;
@@ -968,6 +986,8 @@ int sdr_sgbm_create(const sdr_sgbm_params* p, int device, sdr_sgbm** out) {
     sdr_sgbm* h = new sdr_sgbm();
     h->p = *p;
     h->device = device;
+    const char* rec = getenv("SDR_PATH_REC");
+    h->rec16 = rec && atoi(rec) == 16;
     if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) {
         delete h;
         return fail(SDR_ERR_DEVICE, "hipStreamCreate failed");

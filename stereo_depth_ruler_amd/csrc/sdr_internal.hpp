@@ -134,7 +134,11 @@ struct PathLaunch {
     const int16_t* C;
     size_t cs_fstride;   // elements per frame of C
     size_t l_fstride;    // elements per frame of L
-    int l_pix;           // elements per pixel record of L ((P-1) * D)
+    int l_pix;           // int16 elements per pixel record of L ((P-1) * D; rec12: (P-1) * D * 3/4)
+    // Record format, one decision per call for the producer (k_paths) and the consumer
+    // (k_south_wta), made by the engine: 0 = int16 L; 1 = e = C - L in 12 bits a value (sdr_device.hpp
+    // rec12_pack), D * 3/2 bytes a direction, when path_rec12_supported() and P2 <= 4095
+    int rec12;
     size_t aux_fstride;
     int ndirs;
     int prefix[kMaxPathDirs + 1];  // chain prefix sums
@@ -208,6 +212,13 @@ struct SouthWtaArgs {
 };
 void launch_south_wta(const Geometry& g, const PathLaunch& pl, const SouthWtaArgs& a, int F,
                       hipStream_t st);
+// The launchers' own choices of a two-chain k_paths / two-column k_south_wta (both keep int16
+// records), and whether the kernels launch_paths(pls) and launch_south_wta(plS, npaths) would
+// dispatch both implement the 12-bit record format: D = 128 exactly, one chain or column a wave,
+// 4, 5 or 8 paths.
+bool paths_two_chain(const Geometry& g, const PathLaunch& pl, int F);
+bool south_two_col(const Geometry& g, const PathLaunch& pl, int npaths, int F);
+bool path_rec12_supported(const Geometry& g, const PathLaunch& pls, const PathLaunch& plS, int npaths, int F);
 
 // A.9, OpenCV's disp12MaxDiff check, at pixel (x, y) of a frame with geometry g: raw is the frame's
 // WTA map and d2 its right-view keys (both [H][W]).  Every consumer of the LR-checked map

@@ -63,9 +63,12 @@ __device__ __forceinline__ Chain make_chain(const Geometry& g, const PathDir& d,
 // alternately -- 4 x int16 vector ops, no packed op right after the one it reads, so none of
 // gfx950's wait states -- removed ~40 % of the path kernels' s_nops and measured no faster: at
 // 3-4 waves per SIMD the other waves fill those slots; profiles/r4_ab_variants.txt.)
-template <int K, bool PAD>
+// WE: also E = C - L = delta2 - t, the 12-bit record's value (0 <= E <= P2: minLp <= t <= delta2),
+// one packed op beside the recurrence's dependency chain.
+template <int K, bool PAD, bool WE = false>
 __device__ __forceinline__ void step_words(const Regs<K>& c, const Regs<K>& Lp, uint32_t delta2, uint32_t P1x2,
-                                           bool active, uint32_t up, uint32_t dn, Regs<K>& L, uint32_t& m) {
+                                           bool active, uint32_t up, uint32_t dn, Regs<K>& L, uint32_t& m,
+                                           Regs<K>* E = nullptr) {
     m = kMaxPair;
 #pragma unroll
     for (int i = 0; i < K; i++) {
@@ -75,6 +78,7 @@ __device__ __forceinline__ void step_words(const Regs<K>& c, const Regs<K>& Lp, 
         t = pk_min(pk_min(t, Lp.r[i]), delta2);
         uint32_t l = pk_sub(pk_add(c.r[i], t), delta2);
         if constexpr (PAD) l = active ? l : kMaxPair;
+        if constexpr (WE) E->r[i] = pk_sub(delta2, t);
         L.r[i] = l;
         m = pk_min(m, l);
     }
@@ -87,9 +91,10 @@ __device__ __forceinline__ void step_words(const Regs<K>& c, const Regs<K>& Lp, 
 // DPP's old value keeps the kMaxPair boundary there from the first step on, with no refill.
 // (An offset-carrying form that takes the wave minimum off the serial chain was bit-exact and
 // not faster on MI355X)  The wave minimum is a wave-uniform (SGPR) value.
-template <int K, bool PAD>
+template <int K, bool PAD, bool WE = false>
 __device__ __forceinline__ Regs<K> path_step(Regs<K> c, Regs<K>& Lp, uint32_t& delta2, uint32_t P1x2,
-                                             uint32_t P2x2, bool active, uint32_t& upr, uint32_t& dnr) {
+                                             uint32_t P2x2, bool active, uint32_t& upr, uint32_t& dnr,
+                                             Regs<K>* E = nullptr) {
     if constexpr (PAD) {
 #pragma unroll
         for (int i = 0; i < K; i++) c.r[i] = active ? c.r[i] : kMaxPair;
@@ -98,7 +103,7 @@ __device__ __forceinline__ Regs<K> path_step(Regs<K> c, Regs<K>& Lp, uint32_t& d
     const uint32_t dn = dnr = lane_from_next(Lp.r[0], dnr);
     Regs<K> L;
     uint32_t m;
-    step_words<K, PAD>(c, Lp, delta2, P1x2, active, up, dn, L, m);
+    step_words<K, PAD, WE>(c, Lp, delta2, P1x2, active, up, dn, L, m, E);
     // min of the pair into the low half (one SDWA op; L >= 0, so u16 order is int16 order), the
     // wave minimum as a wave-uniform value, splatted and offset by P2 in scalar registers
     const uint32_t m16 = (uint32_t)__builtin_elementwise_min((unsigned short)(m & 0xffffu),
@@ -122,8 +127,12 @@ constexpr int paths_la() { return DPL == 8 ? 8 : 16; }
 // 219 -> 183 us (MI355X, scripts/kbench.py A/B, bit-exact).
 constexpr int kLoadNT = 2;
 
-template <int DPL, bool PAD>
+// R12: the records are 12-bit e = C - L (rec12_pack): a quad of lanes' 8 disparities in 12 bytes,
+// lanes 0-2 of the quad storing a dword each, a pixel's record of one direction D * 3/2 contiguous
+// bytes (three whole 64-byte segments at D = 128).
+template <int DPL, bool PAD, bool R12 = false>
 __global__ __launch_bounds__(256) void k_paths(Geometry g, PathLaunch pl) {
+    static_assert(!R12 || (DPL == 2 && !PAD), "12-bit records: D = 128");
     constexpr int K = DPL / 2;
     // C is loaded LA steps ahead into a ring of 2*LA slots: the slot a load fills was consumed
     // LA steps earlier, so every slot keeps one register across the loop's back edge (a ring
@@ -198,14 +207,23 @@ __global__ __launch_bounds__(256) void k_paths(Geometry g, PathLaunch pl) {
     // assume the path where no store was issued: every step waited until only 15 memory ops
     // were outstanding, i.e. for the C load of ~8 steps back instead of 16 -- the E/W chains of
     // the padded D = 80 class path ran at the memory latency / 8 per step.
-    const uint32_t sofs_st = active ? lofs : 0x80000000u;
+    // (12-bit records: the quad's fourth lane has no dword of its own and is dropped the same way)
+    const uint32_t sofs_st = R12 ? ((lane & 3) == 3 ? 0x80000000u : (uint32_t)((lane >> 2) * 12 + (lane & 3) * 4))
+                                 : active ? lofs : 0x80000000u;
     auto step = [&](const int, auto jc) __attribute__((always_inline)) {
         constexpr int j = decltype(jc)::value;
         const Regs<K> c = cring[j];
         cring[(j + LA) % R] = load_buf<K>(rC, lofs, soff);
         soff += (uint32_t)rowb;
-        const Regs<K> L = path_step<K, PAD>(c, Lp, delta2, P1x2, P2x2, active, upr, dnr);
-        store_buf_nt<K>(rO, sofs_st, soffl, L);
+        if constexpr (R12) {
+            Regs<K> E;
+            (void)path_step<K, PAD, true>(c, Lp, delta2, P1x2, P2x2, active, upr, dnr, &E);
+            E.r[0] = rec12_pack(E.r[0], lane);
+            store_buf_nt<K>(rO, sofs_st, soffl, E);
+        } else {
+            const Regs<K> L = path_step<K, PAD>(c, Lp, delta2, P1x2, P2x2, active, upr, dnr);
+            store_buf_nt<K>(rO, sofs_st, soffl, L);
+        }
         soffl += (uint32_t)rowl;
         // one scheduling region per step (as the branch used to make it): scheduled across the
         // whole unrolled ring, the steps' loads and stores were reordered and the ring registers
@@ -352,7 +370,7 @@ __global__ __launch_bounds__(256) void k_paths_tc(Geometry g, PathLaunch pl) {
 // the two-chain kernel for this launch?  D <= 128, no redirected 3WAY rows, every direction with
 // chains of one length, and more chains than the chip's SIMDs (with fewer, one chain per wave
 // already has a SIMD each and the one-chain step is the cheaper one)
-static bool paths_two_chain(const Geometry& g, const PathLaunch& pl, int F) {
+bool paths_two_chain(const Geometry& g, const PathLaunch& pl, int F) {
     if (g.D > 128 || pl.nredir > 0) return false;
     for (int i = 0; i < pl.ndirs; i++)
         if (pl.d[i].dir != DIR_E && pl.d[i].dir != DIR_W && pl.d[i].dir != DIR_N) return false;
@@ -373,6 +391,7 @@ void launch_paths(const Geometry& g, const PathLaunch& pl, int F, hipStream_t st
     dim3 grid((total + 3) / 4, F);
     if (g.D <= 128) {
         if (g.D < 128) hipLaunchKernelGGL((k_paths<2, true>), grid, dim3(256), 0, st, g, pl);
+        else if (pl.rec12) hipLaunchKernelGGL((k_paths<2, false, true>), grid, dim3(256), 0, st, g, pl);
         else hipLaunchKernelGGL((k_paths<2, false>), grid, dim3(256), 0, st, g, pl);
     } else if (g.D <= 256) {
         if (g.D < 256) hipLaunchKernelGGL((k_paths<4, true>), grid, dim3(256), 0, st, g, pl);
@@ -394,7 +413,7 @@ void launch_paths(const Geometry& g, const PathLaunch& pl, int F, hipStream_t st
 //     directions' L are read from HBM (prefetched whole blocks ahead), the staged L is added
 //     from LDS, and the winner-take-all runs on the saturated sums.
 // A block is handed over by one barrier.  L of this direction is never written to HBM, so the
-// pass moves 2 + 2(P-1) B/cell.  The uniqueness test needs only the smallest S[d] with
+// pass moves 2 + 2(P-1) B/cell (2 + 1.5(P-1) with 12-bit records, PathLaunch::rec12).  The uniqueness test needs only the smallest S[d] with
 // |d - best| > 1 (both of OpenCV's rules are monotone in S[d]): a masked packed minimum.
 // Each pixel's results -- the WTA disparity and (minS << 16 | bestDisp) for the right-view WTA --
 // are staged in LDS and written out once per kStageBlocks blocks, so no global store or atomic
@@ -426,10 +445,17 @@ constexpr uint32_t kRejected = 0xffffffffu;    // no disp2 candidate
 // k_paths_tc step), and the consumers take both columns' pixels of a block (two passes).  The
 // class path's 3WAY stripes at 640x360 are 4480 short chains of ~100 rows, each a workgroup whose
 // producer's serial steps bound the pass; two per workgroup halves the workgroups to run.
-template <int DPL, bool PAD, int NP, bool TC = false>
+// R12 (12-bit records, D = 128, one column): the producer stages each row's C beside its L in a
+// second sL plane, and the consumers rebuild L_r = C - e_r from three dwords a direction
+// (rec12_unpack) before the same saturating sum in the same order.
+template <int DPL, bool PAD, int NP, bool TC = false, bool R12 = false>
 __global__ __launch_bounds__(64 * (1 + kSouthConsumers)) void k_south_wta(Geometry g0, PathLaunch pl,
                                                                            SouthWtaArgs a) {
     static_assert(!TC || DPL == 2, "two columns per workgroup: the D <= 128 layout");
+    static_assert(!R12 || (DPL == 2 && !PAD && !TC), "12-bit records: D = 128, one column");
+    constexpr int NPL = R12 ? 2 : 1;             // sL planes: L of the fused direction, C
+    constexpr int WR = R12 ? 3 : DPL * 2;        // consumer: dwords of one direction's record per lane
+    constexpr int RECB = 64 * DPL * (R12 ? 3 : 4) / 2;  // R12: bytes of one direction's record (unpadded D)
     const Geometry g = frame_geom(g0, blockIdx.y);
     constexpr int K = DPL / 2;
     constexpr int NCOL = TC ? 2 : 1;   // columns per workgroup
@@ -451,9 +477,11 @@ __global__ __launch_bounds__(64 * (1 + kSouthConsumers)) void k_south_wta(Geomet
 #ifndef SDR_SOUTH_TC_PD
 #define SDR_SOUTH_TC_PD 2
 #endif
+    // (12-bit records: a ring of 3 or 4 blocks fits the same registers and measured the same as 2,
+    // as did a producer lookahead of 3 blocks; profiles/rec12/README.md)
     constexpr int PD = TC ? SDR_SOUTH_TC_PD : NP * WK * kSouthRPW <= 128 ? 2 : 1;
     static_assert((PD + 1) * RB <= kSouthPad, "consumer load overrun must fit the row slack");
-    __shared__ uint32_t sL[2][RB][NCOL][LSTR];
+    __shared__ uint32_t sL[2][RB][NCOL][NPL][LSTR];
     // each consumer row's S staged for the subpixel neighbours and the uniqueness minimum (one
     // 16-B write per lane, three masking u16 writes, one read back); rows padded by 4 dwords so
     // the four lane groups' 16-B writes start on different banks
@@ -523,7 +551,7 @@ __global__ __launch_bounds__(64 * (1 + kSouthConsumers)) void k_south_wta(Geomet
         uint32_t upr = kMaxPair, dnr = kMaxPair;  // see path_step
         // block bb (= slot ic of the ring): RB recurrence steps into LDS slot bb & 1, then hand over
         auto block = [&](const int bb, auto ic) __attribute__((always_inline)) {
-            uint32_t* dst = &sL[bb & 1][0][half][hl * PK];
+            uint32_t* dst = &sL[bb & 1][0][half][0][hl * PK];
             auto st = [&](const int, auto jc) __attribute__((always_inline)) {
                 constexpr int j = decltype(jc)::value + decltype(ic)::value * RB;  // ring slot = k % R
                 const Regs<PK> c = cring[j];
@@ -532,7 +560,10 @@ __global__ __launch_bounds__(64 * (1 + kSouthConsumers)) void k_south_wta(Geomet
                 if constexpr (TC) L = path_step_tc<PAD>(c, Lp, delta2, P1x2, P2x2, active, upr, dnr, lane);
                 else L = path_step<K, PAD>(c, Lp, delta2, P1x2, P2x2, active, upr, dnr);
 #pragma unroll
-                for (int i = 0; i < PK; i++) dst[(j % RB) * NCOL * LSTR + i] = L.r[i];
+                for (int i = 0; i < PK; i++) {
+                    dst[(j % RB) * NCOL * NPL * LSTR + i] = L.r[i];
+                    if constexpr (R12) dst[(j % RB) * NCOL * NPL * LSTR + LSTR + i] = c.r[i];
+                }
             };
             unroll_rows(st, bb * RB, std::make_integer_sequence<int, RB>{});
             __syncthreads();
@@ -562,7 +593,7 @@ __global__ __launch_bounds__(64 * (1 + kSouthConsumers)) void k_south_wta(Geomet
     for (int ps = 0; ps < NPASS; ps++) {
         const int col = ps / RPASS;  // TC: passes of the second column are one pixel further on
         rr[ps] = (wv - 1) * kSouthRPW + (ps % RPASS) * 4 + grp;
-        lofs[ps] = (uint32_t)((((size_t)rr[ps] * W1 + col) * pl.l_pix + wd0) * 2);
+        lofs[ps] = (uint32_t)(((size_t)rr[ps] * W1 + col) * pl.l_pix * 2 + (R12 ? gl * 12 : wd0 * 2));
     }
     const char* lbase = (const char*)(a.L + (size_t)f * pl.l_fstride + ((size_t)ch.y0 * W1 + ch.x0) * pl.l_pix);
     // blocks past the chain's last one re-read that block (L2 hits), not the buffers' slack
@@ -574,7 +605,7 @@ __global__ __launch_bounds__(64 * (1 + kSouthConsumers)) void k_south_wta(Geomet
         const Rsrc r = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<char*>(lbase + (ptrdiff_t)min(blk, nblk - 1) * bstepb), (short)0, need ? 0x7fffffff : 0,
             0x00020000);
-        return load_buf<WK, kLoadNT>(r, lofs[ps] + (uint32_t)(q * D * 2));
+        return load_buf<WR, kLoadNT>(r, lofs[ps] + (uint32_t)(R12 ? q * RECB : q * D * 2));
     };
     // rows before kw belong to the previous 3WAY stripe: recurred through, never output
     const int kw = ch.kwrite;
@@ -612,15 +643,27 @@ __global__ __launch_bounds__(64 * (1 + kSouthConsumers)) void k_south_wta(Geomet
 
     // one 4-row pass of block b: S of row k = b*RB + r, the WTA, its outputs staged in LDS
     // S = sat(sum of the P path costs) of row r of block b, the fused direction's L from LDS
-    auto ssum = [&](const int b, const int r, const int col, const Regs<WK> (&o)[NP]) __attribute__((always_inline)) {
-        const uint32_t* ls = &sL[b & 1][r][col][wd0 / 2];
+    auto ssum = [&](const int b, const int r, const int col, const Regs<WR> (&o)[NP]) __attribute__((always_inline)) {
+        const uint32_t* ls = &sL[b & 1][r][col][0][wd0 / 2];
+        Regs<WK> Lq[NP];  // the other directions' L
+#pragma unroll
+        for (int q = 0; q < NP; q++) {
+            if constexpr (R12) {
+                const Regs<4> e = rec12_unpack(o[q]);
+#pragma unroll
+                for (int i = 0; i < WK; i++) Lq[q].r[i] = pk_sub(ls[LSTR + i], e.r[i]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < WK; i++) Lq[q].r[i] = o[q].r[i];
+            }
+        }
         Regs<WK> St;
 #pragma unroll
         for (int i = 0; i < WK; i++) {
             uint32_t acc = 0;
 #pragma unroll
             for (int p = 0; p <= NP; p++) {
-                const uint32_t v = p == kSouthIdx ? ls[i] : o[p < kSouthIdx ? p : p - 1].r[i];
+                const uint32_t v = p == kSouthIdx ? ls[i] : Lq[p < kSouthIdx ? p : p - 1].r[i];
                 acc = p == 0 ? v : pk_add_sat(acc, v);
             }
             if constexpr (PAD && DPL == 8) acc = wd0 + 2 * i < D ? acc : kMaxPair;  // past D: never a minimum
@@ -692,7 +735,7 @@ __global__ __launch_bounds__(64 * (1 + kSouthConsumers)) void k_south_wta(Geomet
     // load of block b + PD goes into the same registers, so each block's loads have PD block
     // periods to land (the loop is unrolled by PD: static slots, no copies at the back edge);
     // unconditional: blocks past the chain's end re-read its last block (oload clamps)
-    Regs<WK> oring[PD][NPASS][NP];
+    Regs<WR> oring[PD][NPASS][NP];
 #pragma unroll
     for (int s = 0; s < PD; s++)
 #pragma unroll
@@ -732,16 +775,33 @@ __global__ __launch_bounds__(256) void k_lr_apply(Geometry g0, const int16_t* __
         out[fo + (size_t)y * g.W + x] = (int16_t)lr_at(g, raw + fo, d2 + fo, x, y, d12);
 }
 
+// two columns per workgroup when the chains far outnumber what the chip holds at once (short,
+// latency-bound chains: the class path's 3WAY stripes), D <= 128, up to 5 paths
+bool south_two_col(const Geometry& g, const PathLaunch& pl, int npaths, int F) {
+    return g.D <= 128 && npaths <= 5 && (long)pl.prefix[pl.ndirs] * F > 8L * device_cus();
+}
+
+bool path_rec12_supported(const Geometry& g, const PathLaunch& pls, const PathLaunch& plS, int npaths, int F) {
+    return g.D == 128 && (npaths == 4 || npaths == 5 || npaths == 8) && pls.nredir == 0 &&
+           !paths_two_chain(g, pls, F) && !south_two_col(g, plS, npaths, F);
+}
+
 template <int DPL, bool PAD>
 static void launch_south_np(const Geometry& g, const PathLaunch& pl, const SouthWtaArgs& a, int F,
                             hipStream_t st) {
     dim3 grid(pl.prefix[pl.ndirs], F);
     dim3 block(64 * (1 + kSouthConsumers));
+    if constexpr (DPL == 2 && !PAD) {
+        if (pl.rec12) {  // the engine's decision (path_rec12_supported): one column, 4, 5 or 8 paths
+            switch (a.npaths) {
+            case 4: hipLaunchKernelGGL((k_south_wta<2, false, 3, false, true>), grid, block, 0, st, g, pl, a); return;
+            case 5: hipLaunchKernelGGL((k_south_wta<2, false, 4, false, true>), grid, block, 0, st, g, pl, a); return;
+            default: hipLaunchKernelGGL((k_south_wta<2, false, 7, false, true>), grid, block, 0, st, g, pl, a); return;
+            }
+        }
+    }
     if constexpr (DPL == 2) {
-        // two columns per workgroup when the chains far outnumber what the chip holds at once
-        // (short, latency-bound chains: the class path's 3WAY stripes), up to 5 paths
-        const int cus = device_cus();
-        if (a.npaths <= 5 && (long)pl.prefix[pl.ndirs] * F > 8L * cus) {
+        if (south_two_col(g, pl, a.npaths, F)) {
             int wgs = 0;
             for (int i = 0; i < pl.ndirs; i++) wgs += (pl.d[i].nchains + 1) / 2;
             const dim3 grid2(wgs, F);
