@@ -550,6 +550,126 @@ int sdr_measurements_csv(const int* image_index, const sdr_segment* segs,
                          const sdr_measurement* records, int n, int with_header, char* buf,
                          size_t cap);
 
+/* ---- the ruler against a surface: robust plane fit and point-to-plane distance ----
+ * sdr_fit_planes* fits a plane d = a*u + b*v + c to the disparities of a rectangle (a plane in
+ * (x, y, d) is a plane in XYZ under any Q) and reports it in pixels and as a 3-D plane;
+ * sdr_plane_distance* measures sampled points against fitted planes.  Every output is defined to
+ * the bit: the fit rests on exact integer moments, so it has no floating-point reduction.
+ *   - Region: an sdr_segment read as a rectangle of frame `frame` with corners (x0, y0), (x1, y1) in
+ *     any order; xs = min, xe = max of the x, ys / ye of the y, inclusive; u = x - xs, v = y - ys;
+ *     area = (xe-xs+1) * (ye-ys+1).  The record's x0 / y0 are xs / ys.  A frame outside [0, F) or a
+ *     corner outside the image: SDR_PLANE_OUT_OF_RANGE, nothing read, every float field the
+ *     canonical NaN, every count (area, n_valid, n_inliers, fits) 0.  xe == xs or ye == ys makes
+ *     the fit degenerate (SDR_PLANE_DEGENERATE; n_valid is still counted).
+ *   - Valid pixel: the ruler's rule (finite, d > min_disp, and with a confidence map
+ *     conf >= conf_min; int16 read as (float)v * 0.0625f), and for float maps fabsf(d) < 2048.  The
+ *     fit works on the 1/16 px grid: q = v for int16, q = (int)rint((double)d * 16.0)
+ *     (round-half-even) for float.
+ *   - Moments of a pixel set: nine exact int64 sums n, Su, Sv, Sq, Suu, Suv, Svv, Suq, Svq.  The
+ *     host refuses width or height > 8192 and width * height > 2^24, so no sum can overflow.
+ *   - Solve, in double, no contraction, every operation rounded, in this order: N = (double)n,
+ *     su, sv, sq the sums converted; cuu = N*Suu - su*su; cuv = N*Suv - su*sv; cvv = N*Svv - sv*sv;
+ *     cuq = N*Suq - su*sq; cvq = N*Svq - sv*sq; det = cuu*cvv - cuv*cuv;
+ *     a = (cuq*cvv - cvq*cuv) / det; b = (cvq*cuu - cuq*cuv) / det; c = ((sq - a*su) - b*sv) / N.
+ *     The fit is degenerate iff n < min_inliers, or !(det > 0), or a, b or c is not finite.
+ *   - Residual of a pixel, in 1/16 px: r = (double)q - ((a*u + b*v) + c); T = (double)inlier_px * 16.
+ *   - Schedule: fit 0 uses every valid pixel; refit k = 1..iterations uses the valid pixels with
+ *     |r| <= T * 2^(iterations-k) against the previous plane (the last refit uses T itself).  A
+ *     degenerate fit stops the chain: SDR_PLANE_DEGENERATE, `fits` the number of fits completed,
+ *     coef, normal, offset, centroid, rms_px and max_abs_px NaN, n_inliers 0.
+ *   - Statistics against the last plane: n_inliers = the valid pixels with |r| <= T;
+ *     See = sum of e*e over them as int64, e = llrint(r * 16); rms_px = sqrt((double)See /
+ *     (double)n_inliers) / 256 and max_abs_px = (float)(max |r| / 16) over them (both NaN with no
+ *     inlier).
+ *   - coef = {a/16, b/16, c/16}: px per px and px, relative to (xs, ys) (an exact scaling).
+ *   - 3-D plane: the anchors (xs, ys), (xe, ys), (xs, ye) with the plane's disparity
+ *     ((a*u + b*v) + c) * 0.0625 are reprojected in double: the four row sums of
+ *     reprojectImageTo3D in its order (from 0: + Q[i][0]*x, + Q[i][1]*y, + Q[i][2]*d, + Q[i][3]*1),
+ *     X = h0/h3, Y = h1/h3, Z = h2/h3 (no float rounding).  e1 = P1 - P0, e2 = P2 - P0;
+ *     m = e1 x e2 with mx = e1y*e2z - e1z*e2y, my = e1z*e2x - e1x*e2z, mz = e1x*e2y - e1y*e2x;
+ *     len = sqrt((mx*mx + my*my) + mz*mz); normal = m / len; offset = -((nx*P0x + ny*P0y) + nz*P0z);
+ *     offset < 0 negates normal and offset (the camera origin is on the non-negative side).
+ *     centroid: the same reprojection at the real-valued pixel (xs + su/N, ys + sv/N) of the last
+ *     fit's set with the plane's disparity ((a*(su/N) + b*(sv/N)) + c) * 0.0625.  A non-finite
+ *     value among them: SDR_PLANE_NONFINITE, normal, offset and centroid NaN, the rest stays.
+ *     SDR_PLANE_OK is set iff none of DEGENERATE, NONFINITE and OUT_OF_RANGE is.
+ *   - Point query {frame, x, y, plane}: (x, y) is sampled exactly as an endpoint of
+ *     sdr_measure_disp (radius, min_count, lower median, reprojection); p, d and n are the
+ *     sample's.  distance = ((nx*X + ny*Y) + nz*Z) + offset in double from the float XYZ, positive
+ *     towards the camera, with SDR_PDIST_VALID iff the sample is valid and the plane is OK; NaN
+ *     otherwise.  SDR_PDIST_OUT_OF_RANGE: frame or pixel outside, nothing read of the maps, p and
+ *     d NaN, n 0.  SDR_PDIST_NO_PLANE: `plane` outside [0, P) or a plane without SDR_PLANE_OK.
+ *   - Every NaN computed is written as the canonical quiet NaN, as in the ruler. */
+typedef struct sdr_plane_params { /* 32 bytes */
+    int32_t iterations;  /* refits after the first fit, 0..8 */
+    int32_t min_inliers; /* >= 3 */
+    float inlier_px;     /* the final band in px: finite, 0 < inlier_px <= 64 */
+    float min_disp;      /* valid iff d > min_disp */
+    float conf_min;      /* valid iff conf >= conf_min (with a confidence map) */
+    int32_t reserved[3]; /* 0 */
+} sdr_plane_params;
+
+enum {
+    SDR_PLANE_OK = 1, SDR_PLANE_DEGENERATE = 2, SDR_PLANE_NONFINITE = 4, SDR_PLANE_OUT_OF_RANGE = 8
+};
+
+typedef struct sdr_plane { /* 128 bytes */
+    double coef[3];      /* a, b (px / px) and c (px): d = a*(x-x0) + b*(y-y0) + c */
+    double normal[3];    /* unit normal of the 3-D plane */
+    double offset;       /* normal . X + offset = 0 on the plane; offset >= 0 */
+    double centroid[3];  /* the plane's point under the centroid of the last fit's pixels */
+    double rms_px;       /* of the inliers' residuals */
+    float max_abs_px;    /* largest inlier residual */
+    int32_t x0, y0;      /* xs, ys: the origin of coef */
+    int32_t frame, area, n_valid, n_inliers, fits;
+    uint32_t flags;      /* SDR_PLANE_* */
+    int32_t reserved;    /* 0 */
+} sdr_plane;
+
+typedef struct sdr_plane_query { /* 16 bytes */
+    int32_t frame, x, y, plane;
+} sdr_plane_query;
+
+enum { SDR_PDIST_VALID = 1, SDR_PDIST_OUT_OF_RANGE = 2, SDR_PDIST_NO_PLANE = 4 };
+
+/* The record shares its name with the host entry point below, as struct stat does with stat():
+ * it has no typedef and is written `struct sdr_plane_distance`. */
+struct sdr_plane_distance { /* 32 bytes */
+    float p[3];          /* XYZ of the sampled point */
+    float d;             /* its median disparity (px) */
+    double distance;     /* signed distance to the plane, positive towards the camera */
+    int32_t n;           /* valid values in the window */
+    uint32_t flags;      /* SDR_PDIST_* */
+};
+
+/* {3, 16, 1.0f, -1.0f, 0.0f, {0, 0, 0}} */
+void sdr_plane_params_default(sdr_plane_params* p);
+/* K regions on device maps (arguments as sdr_measure_disp_device), asynchronous on `stream`:
+ * iterations + 2 sweeps over the regions' pixels and one launch that writes d_planes (K sdr_plane);
+ * the moment accumulators are stream-ordered scratch.  K == 0 is SDR_OK with no launch.  Every
+ * argument is checked on the host before any device call; here a bad disp_type is SDR_ERR_ARG
+ * too. */
+int sdr_fit_planes_device(const void* d_disp, int disp_type, size_t stride, size_t frame_stride,
+                          int width, int height, int nframes, const float* d_conf,
+                          const double Q[16], const sdr_plane_params* params,
+                          const sdr_segment* d_regions, int K, sdr_plane* d_planes, void* stream);
+/* K queries against the P planes of d_planes (e.g. the records sdr_fit_planes_device wrote
+ * earlier on the same stream); params: radius, min_count, min_disp and conf_min of the sample. */
+int sdr_plane_distance_device(const void* d_disp, int disp_type, size_t stride, size_t frame_stride,
+                              int width, int height, int nframes, const float* d_conf,
+                              const double Q[16], const sdr_ruler_params* params,
+                              const sdr_plane* d_planes, int P, const sdr_plane_query* d_queries,
+                              int K, struct sdr_plane_distance* d_out, void* stream);
+/* Host-pointer versions (synchronous; per-thread persistent device buffers as sdr_measure_disp). */
+int sdr_fit_planes(const void* disp, int disp_type, size_t stride, size_t frame_stride, int width,
+                   int height, int nframes, const float* conf, const double Q[16],
+                   const sdr_plane_params* params, const sdr_segment* regions, int K,
+                   sdr_plane* planes);
+int sdr_plane_distance(const void* disp, int disp_type, size_t stride, size_t frame_stride, int width,
+                       int height, int nframes, const float* conf, const double Q[16],
+                       const sdr_ruler_params* params, const sdr_plane* planes, int P,
+                       const sdr_plane_query* queries, int K, struct sdr_plane_distance* out);
+
 /* Bytes of device scratch the handle holds for the given frame shape (for capacity planning);
  * 0 when compute would refuse the shape or parameters.  sdr_sgbm_scratch_bytes is the CV_8UC1
  * figure, sdr_sgbm_scratch_bytes_cn takes the channel count (1 or 3: colour input holds three

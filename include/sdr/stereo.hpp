@@ -444,6 +444,8 @@ private:
 
 // The ruler: StereoDisplayer::onMouseMeasure (stereo_displayer.cpp:24-63) and save_csvFile (:74-102).
 using Measurement = sdr_measurement;
+using Plane = sdr_plane;
+using PlaneDistance = struct sdr_plane_distance;  // the C record shares its name with a function
 struct Point {
     int x = 0, y = 0;
 };
@@ -505,7 +507,66 @@ public:
         return measure_xyz(depth, {sdr_segment{0, a.x, a.y, b.x, b.y}})[0];
     }
 
+    // Against a surface (sdr.h, "the ruler against a surface"): robust plane fits of rectangles
+    // {frame, x0, y0, x1, y1} (corners in any order) of one disparity map, with the ruler's
+    // min_disp and conf_min
+    std::vector<Plane> fit_plane(const Mat& disparity, const std::vector<sdr_segment>& regions,
+                                 const Mat* conf = nullptr, int iterations = 3, float inlier_px = 1.0f,
+                                 int min_inliers = 16) const {
+        check_maps(disparity, conf, "fit_plane");
+        const size_t es = elem_size(disparity.type);
+        sdr_plane_params pp;
+        sdr_plane_params_default(&pp);
+        pp.iterations = iterations;
+        pp.inlier_px = inlier_px;
+        pp.min_inliers = min_inliers;
+        pp.min_disp = p_.min_disp;
+        pp.conf_min = p_.conf_min;
+        std::vector<Plane> out(regions.size());
+        check(sdr_fit_planes(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16,
+                             disparity.step / es, disparity.step / es * disparity.rows, disparity.cols,
+                             disparity.rows, 1, conf ? conf->ptr<float>(0) : nullptr, q_, &pp,
+                             regions.empty() ? nullptr : regions.data(), (int)regions.size(),
+                             out.empty() ? nullptr : out.data()));
+        return out;
+    }
+    Plane fit_plane(const Mat& disparity, Point a, Point b, const Mat* conf = nullptr, int iterations = 3,
+                    float inlier_px = 1.0f, int min_inliers = 16) const {
+        return fit_plane(disparity, {sdr_segment{0, a.x, a.y, b.x, b.y}}, conf, iterations, inlier_px,
+                         min_inliers)[0];
+    }
+    // signed distances of points {frame, x, y, plane}, sampled with the ruler's radius and
+    // min_count, to `planes`; positive towards the camera
+    std::vector<PlaneDistance> plane_distance(const Mat& disparity, const std::vector<Plane>& planes,
+                                              const std::vector<sdr_plane_query>& points,
+                                              const Mat* conf = nullptr) const {
+        check_maps(disparity, conf, "plane_distance");
+        const size_t es = elem_size(disparity.type);
+        sdr_ruler_params p = p_;
+        p.profile = 0;
+        p.profile_cap = 0;
+        std::vector<PlaneDistance> out(points.size());
+        check(sdr_plane_distance(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16,
+                                 disparity.step / es, disparity.step / es * disparity.rows, disparity.cols,
+                                 disparity.rows, 1, conf ? conf->ptr<float>(0) : nullptr, q_, &p,
+                                 planes.empty() ? nullptr : planes.data(), (int)planes.size(),
+                                 points.empty() ? nullptr : points.data(), (int)points.size(),
+                                 out.empty() ? nullptr : out.data()));
+        return out;
+    }
+    PlaneDistance plane_distance(const Mat& disparity, const Plane& plane, Point at,
+                                 const Mat* conf = nullptr) const {
+        return plane_distance(disparity, std::vector<Plane>{plane}, {sdr_plane_query{0, at.x, at.y, 0}}, conf)[0];
+    }
+
 private:
+    static void check_maps(const Mat& disparity, const Mat* conf, const char* what) {
+        if (disparity.type != CV_32FC1 && disparity.type != CV_16SC1)
+            throw Exception(SDR_ERR_TYPE, std::string(what) + " expects a CV_32F or CV_16S disparity");
+        if (conf && (conf->type != CV_32FC1 || conf->rows != disparity.rows || conf->cols != disparity.cols ||
+                     conf->step != (size_t)conf->cols * 4))
+            throw Exception(SDR_ERR_TYPE, "conf must be a continuous CV_32F map of the disparity's size");
+    }
     double q_[16];
     sdr_ruler_params p_;
 };

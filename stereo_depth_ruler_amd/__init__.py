@@ -13,7 +13,11 @@ from .display import COLORMAP_JET, COLORMAP_TURBO, Display, colormap_lut  # noqa
 from .ximgproc import (  # noqa: F401
     DisparityWLSFilter, createDisparityWLSFilter, fastGlobalSmootherFilter,
 )
-from .ruler import MEASUREMENT_DTYPE, MeasurementLog, Ruler  # noqa: F401
+from .ruler import (  # noqa: F401
+    MEASUREMENT_DTYPE, PDIST_NO_PLANE, PDIST_OUT_OF_RANGE, PDIST_VALID, PLANE_DEGENERATE,
+    PLANE_DISTANCE_DTYPE, PLANE_DTYPE, PLANE_NONFINITE, PLANE_OK, PLANE_OUT_OF_RANGE,
+    MeasurementLog, Ruler, plane_angle_deg,
+)
 from .stereo_disparity import StereoDisparity  # noqa: F401
 
 __all__ = [
@@ -22,5 +26,7 @@ __all__ = [
     "MODE_SGBM", "MODE_HH", "MODE_SGBM_3WAY", "MODE_HH4", "WlsParams", "DisparityWLSFilter",
     "createDisparityWLSFilter", "fastGlobalSmootherFilter", "StereoDisparity", "Display",
     "colormap_lut", "COLORMAP_JET", "COLORMAP_TURBO", "host_empty", "COST_BT", "COST_CENSUS",
-    "Ruler", "MeasurementLog", "MEASUREMENT_DTYPE",
+    "Ruler", "MeasurementLog", "MEASUREMENT_DTYPE", "PLANE_DTYPE", "PLANE_DISTANCE_DTYPE",
+    "PLANE_OK", "PLANE_DEGENERATE", "PLANE_NONFINITE", "PLANE_OUT_OF_RANGE", "PDIST_VALID",
+    "PDIST_OUT_OF_RANGE", "PDIST_NO_PLANE", "plane_angle_deg",
 ]

@@ -102,6 +102,35 @@ class Measurement(ctypes.Structure):
 DISP_F32, DISP_S16 = 0, 1  # SDR_DISP_*
 
 
+class PlaneParams(ctypes.Structure):
+    """sdr_plane_params (32 bytes)."""
+    _fields_ = [("iterations", ctypes.c_int32), ("min_inliers", ctypes.c_int32),
+                ("inlier_px", ctypes.c_float), ("min_disp", ctypes.c_float),
+                ("conf_min", ctypes.c_float), ("reserved", ctypes.c_int32 * 3)]
+
+
+class Plane(ctypes.Structure):
+    """sdr_plane (128 bytes)."""
+    _fields_ = [("coef", ctypes.c_double * 3), ("normal", ctypes.c_double * 3),
+                ("offset", ctypes.c_double), ("centroid", ctypes.c_double * 3),
+                ("rms_px", ctypes.c_double), ("max_abs_px", ctypes.c_float),
+                ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("frame", ctypes.c_int32),
+                ("area", ctypes.c_int32), ("n_valid", ctypes.c_int32),
+                ("n_inliers", ctypes.c_int32), ("fits", ctypes.c_int32),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_int32)]
+
+
+class PlaneQuery(ctypes.Structure):
+    """sdr_plane_query (16 bytes)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("frame", "x", "y", "plane")]
+
+
+class PlaneDistance(ctypes.Structure):
+    """sdr_plane_distance (32 bytes)."""
+    _fields_ = [("p", ctypes.c_float * 3), ("d", ctypes.c_float), ("distance", ctypes.c_double),
+                ("n", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
 _lib = None
 _path = LIB_PATH
 
@@ -224,6 +253,15 @@ SIGNATURES = [
                               _c.POINTER(RulerParams), _vp, _i, _vp, _vp]),
     ("sdr_measure_xyz", _i, [_vp, _sz, _sz, _i, _i, _i, _vp, _i, _vp]),
     ("sdr_measurements_csv", _i, [_vp, _vp, _vp, _i, _i, _vp, _sz]),
+    ("sdr_plane_params_default", None, [_c.POINTER(PlaneParams)]),
+    ("sdr_fit_planes_device", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _c.POINTER(_c.c_double),
+                                   _c.POINTER(PlaneParams), _vp, _i, _vp, _vp]),
+    ("sdr_plane_distance_device", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _c.POINTER(_c.c_double),
+                                       _c.POINTER(RulerParams), _vp, _i, _vp, _i, _vp, _vp]),
+    ("sdr_fit_planes", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _c.POINTER(_c.c_double),
+                            _c.POINTER(PlaneParams), _vp, _i, _vp]),
+    ("sdr_plane_distance", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _c.POINTER(_c.c_double),
+                                _c.POINTER(RulerParams), _vp, _i, _vp, _i, _vp]),
     ("sdr_build_id", _c.c_char_p, []),
     ("sdr_last_error", _c.c_char_p, []),
     ("sdr_abi_version", _i, []),

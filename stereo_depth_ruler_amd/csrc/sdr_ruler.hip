@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 
 #include "sdr_device.hpp"
@@ -366,6 +367,341 @@ __global__ __launch_bounds__(256) void k_ruler_xyz(const float* __restrict__ xyz
     write_measurement(out + k, p0, p1, q, q, canon(ruler_distance(p0, p1)), 1, 1, 0, 0, 0, q, q, q, flags);
 }
 
+// ---- the plane fit (the definition: sdr.h, "the ruler against a surface") ----
+static_assert(sizeof(sdr_plane_params) == 32, "sdr_plane_params is 32 bytes");
+static_assert(sizeof(sdr_plane) == 128, "sdr_plane is 128 bytes");
+static_assert(sizeof(sdr_plane_query) == 16, "sdr_plane_query is 16 bytes");
+static_assert(sizeof(struct sdr_plane_distance) == 32, "sdr_plane_distance is 32 bytes");
+
+// A region is cut into slices of kPlaneSlice pixels of its row-major order, a workgroup a slice.
+// The sums are integers, so neither the slice size nor the order the workgroups finish in shows
+// in the result.
+constexpr int kPlaneThreads = 256;
+constexpr int kPlaneWaves = kPlaneThreads / 64;
+constexpr int kPlanePix = 8;  // pixels a thread
+constexpr int kPlaneSlice = kPlaneThreads * kPlanePix;
+// accumulators of a region: [iterations + 2 sweeps][kPlaneSlots] int64.  Sweeps 0..iterations hold
+// the nine moments of their fit's pixel set {n, Su, Sv, Sq, Suu, Suv, Svv, Suq, Svq}, the last
+// sweep {n_inliers, See, the bits of max |r|}
+constexpr int kPlaneSlots = 16;
+constexpr int kPlaneMoments = 9;
+
+struct PlaneFit {
+    double a, b, c;  // in 1/16 px
+    bool ok;
+};
+
+// The solve of sdr.h from a set's moments.  Every workgroup of a sweep and the record writer
+// repeat it from the same integers: the same bits everywhere.
+__device__ __forceinline__ PlaneFit plane_solve(const long long* __restrict__ m, int min_inliers) {
+#pragma clang fp contract(off)
+    const long long n = m[0];
+    const double N = (double)n, su = (double)m[1], sv = (double)m[2], sq = (double)m[3];
+    const double cuu = N * (double)m[4] - su * su;
+    const double cuv = N * (double)m[5] - su * sv;
+    const double cvv = N * (double)m[6] - sv * sv;
+    const double cuq = N * (double)m[7] - su * sq;
+    const double cvq = N * (double)m[8] - sv * sq;
+    const double det = cuu * cvv - cuv * cuv;
+    PlaneFit f;
+    f.a = (cuq * cvv - cvq * cuv) / det;
+    f.b = (cvq * cuu - cuq * cuv) / det;
+    f.c = ((sq - f.a * su) - f.b * sv) / N;
+    f.ok = n >= (long long)min_inliers && det > 0.0 && isfinite(f.a) && isfinite(f.b) && isfinite(f.c);
+    return f;
+}
+
+__device__ __forceinline__ double plane_at(const PlaneFit& f, double u, double v) {
+#pragma clang fp contract(off)
+    return (f.a * u + f.b * v) + f.c;
+}
+
+struct PlaneRect {
+    int xs, ys, rw, rh;
+};
+__device__ __forceinline__ PlaneRect plane_rect(const sdr_segment& s) {
+    PlaneRect r;
+    r.xs = min(s.x0, s.x1);
+    r.ys = min(s.y0, s.y1);
+    r.rw = max(s.x0, s.x1) - r.xs + 1;
+    r.rh = max(s.y0, s.y1) - r.ys + 1;
+    return r;
+}
+
+__device__ __forceinline__ long long wave_sum(long long v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// the valid pixel's value on the 1/16 px grid
+__device__ __forceinline__ bool plane_q(const float* p, float min_disp, int* q) {
+    const float d = *p;
+    *q = (int)rint((double)d * 16.0);
+    return isfinite(d) && d > min_disp && fabsf(d) < 2048.f;
+}
+__device__ __forceinline__ bool plane_q(const int16_t* p, float min_disp, int* q) {
+    const int v = *p;
+    *q = v;
+    return (float)v * 0.0625f > min_disp;
+}
+
+// One sweep over the regions' pixels: grid (slices of a W x H frame, regions).  Sweep 0 sums the
+// moments of the valid pixels, sweep s = 1..iterations those of the pixels within the scheduled
+// band of fit s - 1, sweep iterations + 1 the statistics against the last fit.  A region that is
+// out of range, a slice past its area and a chain that a degenerate fit has stopped leave at once
+// (block-uniform); no workgroup waits on another.
+template <typename T>
+__global__ __launch_bounds__(kPlaneThreads) void k_plane_sweep(const T* __restrict__ disp, size_t stride,
+                                                               size_t fstride, int W, int H, int F,
+                                                               const float* __restrict__ conf,
+                                                               sdr_plane_params P,
+                                                               const sdr_segment* __restrict__ regs,
+                                                               long long* __restrict__ acc, int sweep) {
+#pragma clang fp contract(off)
+    __shared__ long long red[kPlaneWaves][kPlaneMoments];
+    const int k = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const sdr_segment sg = regs[k];
+    if (!segment_in_range(sg, W, H, F)) return;
+    const PlaneRect R = plane_rect(sg);
+    const unsigned area = (unsigned)R.rw * (unsigned)R.rh;  // <= W * H <= 2^24
+    const unsigned base = blockIdx.x * (unsigned)kPlaneSlice;
+    if (base >= area) return;
+    long long* A = acc + (size_t)k * (size_t)(P.iterations + 2) * kPlaneSlots;
+    const bool last = sweep == P.iterations + 1;
+    PlaneFit fit = {0.0, 0.0, 0.0, true};
+    double band = 0.0;
+    if (sweep > 0) {
+        fit = plane_solve(A + (size_t)(sweep - 1) * kPlaneSlots, P.min_inliers);
+        if (!fit.ok) return;  // the chain has stopped: the later sweeps' accumulators stay 0
+        band = (double)P.inlier_px * 16.0 * (double)(1 << (last ? 0 : P.iterations - sweep));
+    }
+    const T* fd = disp + (size_t)sg.frame * fstride + (size_t)R.ys * stride + (size_t)R.xs;
+    const float* fc = conf ? conf + ((size_t)sg.frame * H + (size_t)R.ys) * W + (size_t)R.xs : nullptr;
+
+    long long m[kPlaneMoments];
+#pragma unroll
+    for (int i = 0; i < kPlaneMoments; i++) m[i] = 0;
+    double rmax = 0.0;
+#pragma unroll
+    for (int j = 0; j < kPlanePix; j++) {
+        const unsigned p = base + (unsigned)(j * kPlaneThreads + tid);
+        if (p >= area) continue;
+        const unsigned v = p / (unsigned)R.rw, u = p - v * (unsigned)R.rw;
+        int q;
+        bool ok = plane_q(fd + (size_t)v * stride + u, P.min_disp, &q);
+        if (fc) ok = ok && fc[(size_t)v * W + u] >= P.conf_min;
+        double r = 0.0;
+        if (sweep > 0) {
+            r = (double)q - plane_at(fit, (double)u, (double)v);
+            ok = ok && fabs(r) <= band;
+        }
+        if (!ok) continue;
+        if (last) {
+            const long long e = llrint(r * 16.0);
+            m[0] += 1;
+            m[1] += e * e;
+            rmax = fmax(rmax, fabs(r));
+        } else {
+            const long long lu = u, lv = v, lq = q;
+            m[0] += 1;
+            m[1] += lu;
+            m[2] += lv;
+            m[3] += lq;
+            m[4] += lu * lu;
+            m[5] += lu * lv;
+            m[6] += lv * lv;
+            m[7] += lu * lq;
+            m[8] += lv * lq;
+        }
+    }
+    // wave butterflies, then the waves' sums through LDS; a maximum of non-negative doubles is
+    // the maximum of their bits
+    const int nsum = last ? 2 : kPlaneMoments;
+#pragma unroll
+    for (int i = 0; i < kPlaneMoments; i++) {
+        if (i < nsum) {  // block-uniform
+            const long long s = wave_sum(m[i]);
+            if (lane == 0) red[wave][i] = s;
+        }
+    }
+    if (last) {
+        long long b = __double_as_longlong(rmax);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) b = max(b, __shfl_xor(b, o, 64));
+        if (lane == 0) red[wave][2] = b;
+    }
+    __syncthreads();
+    long long* dst = A + (size_t)sweep * kPlaneSlots;
+    if (tid < nsum) {
+        long long s = 0;
+#pragma unroll
+        for (int w = 0; w < kPlaneWaves; w++) s += red[w][tid];
+        if (s) atomicAdd((unsigned long long*)dst + tid, (unsigned long long)s);
+    } else if (last && tid == 2) {
+        long long b = 0;
+#pragma unroll
+        for (int w = 0; w < kPlaneWaves; w++) b = max(b, red[w][2]);
+        if (b) atomicMax((unsigned long long*)dst + 2, (unsigned long long)b);
+    }
+}
+
+// reprojectImageTo3D's row sums at a real-valued pixel, the point kept in double
+__device__ __forceinline__ void plane_reproject(const Q16& Q, double x, double y, double d, double* o) {
+#pragma clang fp contract(off)
+    double h[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        double s = 0.0;
+        s += Q.q[i * 4 + 0] * x;
+        s += Q.q[i * 4 + 1] * y;
+        s += Q.q[i * 4 + 2] * d;
+        s += Q.q[i * 4 + 3] * 1.0;
+        h[i] = s;
+    }
+    o[0] = h[0] / h[3];
+    o[1] = h[1] / h[3];
+    o[2] = h[2] / h[3];
+}
+
+// The records, one lane a region, from the accumulators the sweeps have left.
+__global__ __launch_bounds__(64) void k_plane_finish(const sdr_segment* __restrict__ regs, int K, int W,
+                                                     int H, int F, Q16 Q, sdr_plane_params P,
+                                                     const long long* __restrict__ acc,
+                                                     sdr_plane* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= K) return;
+    const sdr_segment sg = regs[k];
+    const double qn = __builtin_nan("");
+    sdr_plane o;
+    for (int i = 0; i < 3; i++) o.coef[i] = o.normal[i] = o.centroid[i] = qn;
+    o.offset = o.rms_px = qn;
+    o.max_abs_px = ruler_nan();
+    o.x0 = min(sg.x0, sg.x1);
+    o.y0 = min(sg.y0, sg.y1);
+    o.frame = sg.frame;
+    o.area = o.n_valid = o.n_inliers = o.fits = 0;
+    o.flags = SDR_PLANE_OUT_OF_RANGE;
+    o.reserved = 0;
+    if (!segment_in_range(sg, W, H, F)) {
+        out[k] = o;
+        return;
+    }
+    const PlaneRect R = plane_rect(sg);
+    const long long* A = acc + (size_t)k * (size_t)(P.iterations + 2) * kPlaneSlots;
+    o.area = R.rw * R.rh;
+    o.n_valid = (int)A[0];
+    PlaneFit fit = {0.0, 0.0, 0.0, false};
+    const long long* M = A;
+    for (int s = 0; s <= P.iterations; s++) {
+        M = A + (size_t)s * kPlaneSlots;
+        fit = plane_solve(M, P.min_inliers);
+        if (!fit.ok) break;
+        o.fits++;
+    }
+    if (!fit.ok) {
+        o.flags = SDR_PLANE_DEGENERATE;
+        out[k] = o;
+        return;
+    }
+    const long long* L = A + (size_t)(P.iterations + 1) * kPlaneSlots;
+    o.n_inliers = (int)L[0];
+    if (L[0] > 0) {
+        o.rms_px = canon(sqrt((double)L[1] / (double)L[0]) / 256.0);
+        o.max_abs_px = (float)(__longlong_as_double(L[2]) / 16.0);
+    }
+    o.coef[0] = fit.a * 0.0625;
+    o.coef[1] = fit.b * 0.0625;
+    o.coef[2] = fit.c * 0.0625;
+    const double ue = (double)(R.rw - 1), ve = (double)(R.rh - 1);
+    const double xs = (double)R.xs, ys = (double)R.ys;
+    double p0[3], p1[3], p2[3], ce[3];
+    plane_reproject(Q, xs, ys, plane_at(fit, 0.0, 0.0) * 0.0625, p0);
+    plane_reproject(Q, (double)(R.xs + R.rw - 1), ys, plane_at(fit, ue, 0.0) * 0.0625, p1);
+    plane_reproject(Q, xs, (double)(R.ys + R.rh - 1), plane_at(fit, 0.0, ve) * 0.0625, p2);
+    const double e1x = p1[0] - p0[0], e1y = p1[1] - p0[1], e1z = p1[2] - p0[2];
+    const double e2x = p2[0] - p0[0], e2y = p2[1] - p0[1], e2z = p2[2] - p0[2];
+    const double mx = e1y * e2z - e1z * e2y;
+    const double my = e1z * e2x - e1x * e2z;
+    const double mz = e1x * e2y - e1y * e2x;
+    const double len = sqrt((mx * mx + my * my) + mz * mz);
+    double nx = mx / len, ny = my / len, nz = mz / len;
+    double off = -((nx * p0[0] + ny * p0[1]) + nz * p0[2]);
+    if (off < 0.0) {
+        nx = -nx;
+        ny = -ny;
+        nz = -nz;
+        off = -off;
+    }
+    const double N = (double)M[0];
+    const double cu = (double)M[1] / N, cv = (double)M[2] / N;
+    plane_reproject(Q, xs + cu, ys + cv, plane_at(fit, cu, cv) * 0.0625, ce);
+    if (isfinite(nx) && isfinite(ny) && isfinite(nz) && isfinite(off) && isfinite(ce[0]) && isfinite(ce[1]) &&
+        isfinite(ce[2])) {
+        o.normal[0] = nx;
+        o.normal[1] = ny;
+        o.normal[2] = nz;
+        o.offset = off;
+        for (int i = 0; i < 3; i++) o.centroid[i] = ce[i];
+        o.flags = SDR_PLANE_OK;
+    } else {
+        o.flags = SDR_PLANE_NONFINITE;
+    }
+    out[k] = o;
+}
+
+// Point queries, one wave a query: the ruler's sample and its distance to a fitted plane.
+template <typename T>
+__global__ __launch_bounds__(kPlaneThreads) void k_plane_distance(const T* __restrict__ disp, size_t stride,
+                                                                  size_t fstride, int W, int H, int F,
+                                                                  const float* __restrict__ conf, Q16 Q,
+                                                                  sdr_ruler_params P,
+                                                                  const sdr_plane* __restrict__ planes, int NP,
+                                                                  const sdr_plane_query* __restrict__ qs, int K,
+                                                                  struct sdr_plane_distance* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int k = (int)blockIdx.x * kPlaneWaves + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    if (k >= K) return;  // wave-uniform
+    const sdr_plane_query q = qs[k];
+    const bool inside = q.frame >= 0 && q.frame < F && q.x >= 0 && q.x < W && q.y >= 0 && q.y < H;
+    uint32_t flags = inside ? 0 : SDR_PDIST_OUT_OF_RANGE;
+    double n[3] = {0.0, 0.0, 0.0}, off = 0.0;
+    bool plane_ok = q.plane >= 0 && q.plane < NP;
+    if (plane_ok) {
+        const sdr_plane* pl = planes + q.plane;
+        plane_ok = (pl->flags & SDR_PLANE_OK) != 0;
+        n[0] = pl->normal[0];
+        n[1] = pl->normal[1];
+        n[2] = pl->normal[2];
+        off = pl->offset;
+    }
+    if (!plane_ok) flags |= SDR_PDIST_NO_PLANE;
+    RulerSample s;
+    s.d = s.xyz[0] = s.xyz[1] = s.xyz[2] = ruler_nan();
+    s.n = 0;
+    s.valid = false;
+    if (inside)
+        s = ruler_sample(disp + (size_t)q.frame * fstride, stride,
+                         conf ? conf + (size_t)q.frame * W * H : nullptr, W, H, Q, P, q.x, q.y, lane);
+    if (lane != 0) return;
+    double dist = __builtin_nan("");
+    if (s.valid && plane_ok) {
+        dist = canon(((n[0] * (double)s.xyz[0] + n[1] * (double)s.xyz[1]) + n[2] * (double)s.xyz[2]) + off);
+        flags |= SDR_PDIST_VALID;
+    }
+    struct sdr_plane_distance* o = out + k;
+    o->p[0] = canon(s.xyz[0]);
+    o->p[1] = canon(s.xyz[1]);
+    o->p[2] = canon(s.xyz[2]);
+    o->d = s.d;
+    o->distance = dist;
+    o->n = s.n;
+    o->flags = flags;
+}
+
 }  // namespace sdr
 
 namespace {
@@ -398,6 +734,37 @@ int check_disp_args(const void* disp, int disp_type, size_t stride, size_t fstri
     return SDR_OK;
 }
 
+// argument guards shared by the plane fit and the point query (host only): check_disp_args' rules
+// for the maps, with a bad disp_type an argument error too, and the sizes the moments allow
+int check_plane_maps(const void* disp, int disp_type, size_t stride, size_t fstride, int W, int H, int F,
+                     const double* Q, const void* params, const void* items, int K, const void* out) {
+    if (!disp || !Q || !params) return rfail(SDR_ERR_ARG, "null argument");
+    if (K < 0) return rfail(SDR_ERR_ARG, "negative count");
+    if (K > 0 && (!items || !out)) return rfail(SDR_ERR_ARG, "null argument");
+    if (W <= 0 || H <= 0 || F <= 0) return rfail(SDR_ERR_ARG, "bad size");
+    if (W > 8192 || H > 8192 || (size_t)W * (size_t)H > ((size_t)1 << 24))
+        return rfail(SDR_ERR_ARG, "the plane fit takes maps of at most 8192 x 8192 and 2^24 pixels");
+    if (stride < (size_t)W || fstride < stride * (size_t)(H - 1) + (size_t)W)
+        return rfail(SDR_ERR_ARG, "bad stride");
+    if (disp_type != SDR_DISP_F32 && disp_type != SDR_DISP_S16)
+        return rfail(SDR_ERR_ARG, "disp_type must be SDR_DISP_F32 or SDR_DISP_S16");
+    return SDR_OK;
+}
+
+int check_plane_params(const sdr_plane_params* p) {
+    if (p->iterations < 0 || p->iterations > 8) return rfail(SDR_ERR_ARG, "iterations must be in 0..8");
+    if (p->min_inliers < 3) return rfail(SDR_ERR_ARG, "min_inliers must be >= 3");
+    if (!(p->inlier_px > 0.0f && p->inlier_px <= 64.0f)) return rfail(SDR_ERR_ARG, "inlier_px must be in (0, 64]");
+    return SDR_OK;
+}
+
+int check_query_params(const sdr_ruler_params* p, const void* planes, int P) {
+    if (p->radius < 0 || p->radius > 4) return rfail(SDR_ERR_ARG, "radius must be in 0..4");
+    if (p->min_count < 1) return rfail(SDR_ERR_ARG, "min_count must be >= 1");
+    if (P < 0 || (P > 0 && !planes)) return rfail(SDR_ERR_ARG, "bad plane count or null planes");
+    return SDR_OK;
+}
+
 int check_xyz_args(const void* xyz, size_t stride, size_t fstride, int W, int H, int F, const void* segs,
                    int K, const void* out) {
     if (!xyz) return rfail(SDR_ERR_ARG, "null argument");
@@ -413,12 +780,12 @@ int check_xyz_args(const void* xyz, size_t stride, size_t fstride, int W, int H,
 struct HostState {
     int device = -1;
     hipStream_t st = nullptr;
-    sdr::Buf map, conf, segs, out, prof;
+    sdr::Buf map, conf, segs, out, prof, planes;
     void release() {
         if (device < 0) return;
         (void)hipSetDevice(device);
         if (st) (void)hipStreamSynchronize(st);
-        for (sdr::Buf* b : {&map, &conf, &segs, &out, &prof}) {
+        for (sdr::Buf* b : {&map, &conf, &segs, &out, &prof, &planes}) {
             if (b->p) (void)hipFree(b->p);
             *b = sdr::Buf();
         }
@@ -450,6 +817,18 @@ int upload_rows(void* dst, const void* src, size_t row_bytes, size_t src_row, si
         RULER_HIP(hipMemcpy2DAsync((char*)dst + (size_t)f * row_bytes * H, row_bytes,
                                    (const char*)src + (size_t)f * src_frame, src_row, row_bytes, H,
                                    hipMemcpyHostToDevice, st));
+    return SDR_OK;
+}
+
+// the host-pointer calls' maps into the thread's persistent buffers (dense rows)
+int upload_maps(HostState* S, const void* disp, int disp_type, size_t stride, size_t fstride, int W, int H,
+                int F, const float* conf) {
+    const size_t es = disp_type == SDR_DISP_F32 ? 4 : 2, px = (size_t)W * H;
+    int rc;
+    if ((rc = sdr::ensure(S->map, (size_t)F * px * es)) || (rc = sdr::ensure(S->conf, conf ? (size_t)F * px * 4 : 0)))
+        return rc;
+    if ((rc = upload_rows(S->map.p, disp, (size_t)W * es, stride * es, fstride * es, H, F, S->st))) return rc;
+    if (conf) RULER_HIP(hipMemcpyAsync(S->conf.p, conf, (size_t)F * px * 4, hipMemcpyHostToDevice, S->st));
     return SDR_OK;
 }
 
@@ -510,15 +889,13 @@ int sdr_measure_disp(const void* disp, int disp_type, size_t stride, size_t fram
     if (K == 0) return SDR_OK;
     HostState* S = nullptr;
     if ((rc = host_state(&S))) return rc;
-    const size_t es = disp_type == SDR_DISP_F32 ? 4 : 2, px = (size_t)W * H;
+    const size_t px = (size_t)W * H;
     const bool prof = profile && params->profile && params->profile_cap > 0;
     const size_t prof_bytes = prof ? (size_t)K * params->profile_cap * 16 : 0;
-    if ((rc = sdr::ensure(S->map, (size_t)F * px * es)) || (rc = sdr::ensure(S->conf, conf ? (size_t)F * px * 4 : 0)) ||
-        (rc = sdr::ensure(S->segs, (size_t)K * sizeof(sdr_segment))) ||
-        (rc = sdr::ensure(S->out, (size_t)K * sizeof(sdr_measurement))) || (rc = sdr::ensure(S->prof, prof_bytes)))
+    if ((rc = sdr::ensure(S->segs, (size_t)K * sizeof(sdr_segment))) ||
+        (rc = sdr::ensure(S->out, (size_t)K * sizeof(sdr_measurement))) || (rc = sdr::ensure(S->prof, prof_bytes)) ||
+        (rc = upload_maps(S, disp, disp_type, stride, frame_stride, W, H, F, conf)))
         return rc;
-    if ((rc = upload_rows(S->map.p, disp, (size_t)W * es, stride * es, frame_stride * es, H, F, S->st))) return rc;
-    if (conf) RULER_HIP(hipMemcpyAsync(S->conf.p, conf, (size_t)F * px * 4, hipMemcpyHostToDevice, S->st));
     RULER_HIP(hipMemcpyAsync(S->segs.p, segs, (size_t)K * sizeof(sdr_segment), hipMemcpyHostToDevice, S->st));
     // rows the kernel leaves untouched keep the caller's values
     if (prof) RULER_HIP(hipMemcpyAsync(S->prof.p, profile, prof_bytes, hipMemcpyHostToDevice, S->st));
@@ -549,6 +926,123 @@ int sdr_measure_xyz(const float* xyz, size_t xyz_stride, size_t xyz_frame_stride
                                 K, (sdr_measurement*)S->out.p, S->st);
     if (rc) return rc;
     RULER_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(sdr_measurement), hipMemcpyDeviceToHost, S->st));
+    RULER_HIP(hipStreamSynchronize(S->st));
+    return SDR_OK;
+}
+
+void sdr_plane_params_default(sdr_plane_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->iterations = 3;
+    p->min_inliers = 16;
+    p->inlier_px = 1.0f;
+    p->min_disp = -1.0f;
+    p->conf_min = 0.0f;
+}
+
+int sdr_fit_planes_device(const void* d_disp, int disp_type, size_t stride, size_t frame_stride, int W,
+                          int H, int F, const float* d_conf, const double Q[16],
+                          const sdr_plane_params* params, const sdr_segment* d_regions, int K,
+                          sdr_plane* d_planes, void* stream) {
+    int rc = check_plane_maps(d_disp, disp_type, stride, frame_stride, W, H, F, Q, params, d_regions, K, d_planes);
+    if (rc || (rc = check_plane_params(params))) return rc;
+    if (K == 0) return SDR_OK;
+    hipStream_t st = (hipStream_t)stream;
+    sdr::Q16 q;
+    for (int i = 0; i < 16; i++) q.q[i] = Q[i];
+    const int sweeps = params->iterations + 2;
+    const size_t per = (size_t)sweeps * sdr::kPlaneSlots, bytes = (size_t)K * per * sizeof(long long);
+    long long* acc = nullptr;
+    RULER_HIP(sdr::scratch_alloc((void**)&acc, bytes, st));
+    RULER_HIP(hipMemsetAsync(acc, 0, bytes, st));
+    const unsigned slices = (unsigned)(((size_t)W * H + sdr::kPlaneSlice - 1) / sdr::kPlaneSlice);
+    for (int s = 0; s < sweeps; s++)
+        for (int k0 = 0; k0 < K; k0 += 65535) {  // the grid's y extent
+            const dim3 grid(slices, (unsigned)std::min(K - k0, 65535)), block(sdr::kPlaneThreads);
+            if (disp_type == SDR_DISP_F32)
+                hipLaunchKernelGGL(sdr::k_plane_sweep<float>, grid, block, 0, st, (const float*)d_disp, stride,
+                                   frame_stride, W, H, F, d_conf, *params, d_regions + k0, acc + k0 * per, s);
+            else
+                hipLaunchKernelGGL(sdr::k_plane_sweep<int16_t>, grid, block, 0, st, (const int16_t*)d_disp,
+                                   stride, frame_stride, W, H, F, d_conf, *params, d_regions + k0,
+                                   acc + k0 * per, s);
+        }
+    hipLaunchKernelGGL(sdr::k_plane_finish, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, st, d_regions, K, W, H,
+                       F, q, *params, (const long long*)acc, d_planes);
+    const hipError_t le = hipGetLastError();
+    RULER_HIP(sdr::scratch_free(acc, st));
+    RULER_HIP(le);
+    return SDR_OK;
+}
+
+int sdr_plane_distance_device(const void* d_disp, int disp_type, size_t stride, size_t frame_stride, int W,
+                              int H, int F, const float* d_conf, const double Q[16],
+                              const sdr_ruler_params* params, const sdr_plane* d_planes, int P,
+                              const sdr_plane_query* d_queries, int K,
+                              struct sdr_plane_distance* d_out,
+                              void* stream) {
+    int rc = check_plane_maps(d_disp, disp_type, stride, frame_stride, W, H, F, Q, params, d_queries, K, d_out);
+    if (rc || (rc = check_query_params(params, d_planes, P))) return rc;
+    if (K == 0) return SDR_OK;
+    sdr::Q16 q;
+    for (int i = 0; i < 16; i++) q.q[i] = Q[i];
+    const dim3 grid((unsigned)((K + sdr::kPlaneWaves - 1) / sdr::kPlaneWaves)), block(sdr::kPlaneThreads);
+    if (disp_type == SDR_DISP_F32)
+        hipLaunchKernelGGL(sdr::k_plane_distance<float>, grid, block, 0, (hipStream_t)stream,
+                           (const float*)d_disp, stride, frame_stride, W, H, F, d_conf, q, *params, d_planes, P,
+                           d_queries, K, d_out);
+    else
+        hipLaunchKernelGGL(sdr::k_plane_distance<int16_t>, grid, block, 0, (hipStream_t)stream,
+                           (const int16_t*)d_disp, stride, frame_stride, W, H, F, d_conf, q, *params, d_planes,
+                           P, d_queries, K, d_out);
+    RULER_HIP(hipGetLastError());
+    return SDR_OK;
+}
+
+int sdr_fit_planes(const void* disp, int disp_type, size_t stride, size_t frame_stride, int W, int H, int F,
+                   const float* conf, const double Q[16], const sdr_plane_params* params,
+                   const sdr_segment* regions, int K, sdr_plane* planes) {
+    int rc = check_plane_maps(disp, disp_type, stride, frame_stride, W, H, F, Q, params, regions, K, planes);
+    if (rc || (rc = check_plane_params(params))) return rc;
+    if (K == 0) return SDR_OK;
+    HostState* S = nullptr;
+    if ((rc = host_state(&S))) return rc;
+    if ((rc = upload_maps(S, disp, disp_type, stride, frame_stride, W, H, F, conf)) ||
+        (rc = sdr::ensure(S->segs, (size_t)K * sizeof(sdr_segment))) ||
+        (rc = sdr::ensure(S->planes, (size_t)K * sizeof(sdr_plane))))
+        return rc;
+    RULER_HIP(hipMemcpyAsync(S->segs.p, regions, (size_t)K * sizeof(sdr_segment), hipMemcpyHostToDevice, S->st));
+    rc = sdr_fit_planes_device(S->map.p, disp_type, (size_t)W, (size_t)W * H, W, H, F,
+                               conf ? (const float*)S->conf.p : nullptr, Q, params, (const sdr_segment*)S->segs.p,
+                               K, (sdr_plane*)S->planes.p, S->st);
+    if (rc) return rc;
+    RULER_HIP(hipMemcpyAsync(planes, S->planes.p, (size_t)K * sizeof(sdr_plane), hipMemcpyDeviceToHost, S->st));
+    RULER_HIP(hipStreamSynchronize(S->st));
+    return SDR_OK;
+}
+
+int sdr_plane_distance(const void* disp, int disp_type, size_t stride, size_t frame_stride, int W, int H,
+                       int F, const float* conf, const double Q[16], const sdr_ruler_params* params,
+                       const sdr_plane* planes, int P, const sdr_plane_query* queries, int K,
+                       struct sdr_plane_distance* out) {
+    int rc = check_plane_maps(disp, disp_type, stride, frame_stride, W, H, F, Q, params, queries, K, out);
+    if (rc || (rc = check_query_params(params, planes, P))) return rc;
+    if (K == 0) return SDR_OK;
+    HostState* S = nullptr;
+    if ((rc = host_state(&S))) return rc;
+    if ((rc = upload_maps(S, disp, disp_type, stride, frame_stride, W, H, F, conf)) ||
+        (rc = sdr::ensure(S->segs, (size_t)K * sizeof(sdr_plane_query))) ||
+        (rc = sdr::ensure(S->planes, (size_t)P * sizeof(sdr_plane))) ||
+        (rc = sdr::ensure(S->out, (size_t)K * sizeof(struct sdr_plane_distance))))
+        return rc;
+    RULER_HIP(hipMemcpyAsync(S->segs.p, queries, (size_t)K * sizeof(sdr_plane_query), hipMemcpyHostToDevice, S->st));
+    if (P) RULER_HIP(hipMemcpyAsync(S->planes.p, planes, (size_t)P * sizeof(sdr_plane), hipMemcpyHostToDevice, S->st));
+    rc = sdr_plane_distance_device(S->map.p, disp_type, (size_t)W, (size_t)W * H, W, H, F,
+                                   conf ? (const float*)S->conf.p : nullptr, Q, params,
+                                   P ? (const sdr_plane*)S->planes.p : nullptr, P,
+                                   (const sdr_plane_query*)S->segs.p, K, (struct sdr_plane_distance*)S->out.p, S->st);
+    if (rc) return rc;
+    RULER_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(struct sdr_plane_distance), hipMemcpyDeviceToHost, S->st));
     RULER_HIP(hipStreamSynchronize(S->st));
     return SDR_OK;
 }

@@ -123,6 +123,21 @@ class LiveLoop:
         return self.ruler.measure_device(self.disp, segments, conf=self.conf, stream=stream,
                                          profile_cap=profile_cap, profile_out=profile_out)
 
+    def fit_plane(self, regions, stream, iterations: int = 3, inlier_px: float = 1.0, min_inliers: int = 16):
+        """Ruler.fit_plane_device on the frames the last enqueue left in `disp`, with their
+        confidence map, enqueued on `stream` like measure(): the (K, 128) records tensor."""
+        if self.ruler is None:
+            raise RuntimeError("LiveLoop was built without ruler=")
+        return self.ruler.fit_plane_device(self.disp, regions, conf=self.conf, iterations=iterations,
+                                           inlier_px=inlier_px, min_inliers=min_inliers, stream=stream)
+
+    def plane_distance(self, planes, points, stream):
+        """Ruler.plane_distance_device on the same frames: `planes` the tensor fit_plane returned
+        (or host records), the (K, 32) distances tensor, no synchronise in between."""
+        if self.ruler is None:
+            raise RuntimeError("LiveLoop was built without ruler=")
+        return self.ruler.plane_distance_device(self.disp, planes, points, conf=self.conf, stream=stream)
+
     def close(self):
         for o in (self.left, self.right, self.wls, self.display):
             if o is not None:

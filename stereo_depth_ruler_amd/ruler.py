@@ -9,6 +9,10 @@ engine (csrc/sdr_ruler.hip; the definition is in include/sdr/sdr.h).
   ``profile=True`` every pixel of the segment is sampled and the record reports the depth profile
   (valid samples, longest hole, Z range, largest Z step), which shows whether both endpoints lie on
   one surface.  ``radius=0, min_count=1`` equals the reference's lookup on finite pixels.
+* ``Ruler.fit_plane(disparity, regions)`` fits a plane to the disparities of each rectangle (exact
+  integer moments, a coarse-to-fine inlier refit) and ``Ruler.plane_distance(disparity, planes,
+  points)`` gives the signed distance of sampled points to those planes, positive towards the
+  camera: heights above a table, steps, distances from a wall.
 
 A segment is ``(frame, x0, y0, x1, y1)`` (or ``(x0, y0, x1, y1)`` on frame 0), in pixels of the
 map.  The walk rounds ties towards +x / +y: from P1 to P0 it visits the same pixels in reverse, so
@@ -24,7 +28,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import DISP_F32, DISP_S16, RulerParams, SDRError, check, lib
+from ._lib import DISP_F32, DISP_S16, PlaneParams, RulerParams, SDRError, check, lib
 from .sgbm import _Q, _is_cuda, torch
 
 MEASUREMENT_DTYPE = np.dtype([
@@ -36,6 +40,40 @@ assert MEASUREMENT_DTYPE.itemsize == 80
 
 # sdr_measurement.flags (SDR_MEAS_*)
 P0_VALID, P1_VALID, OUT_OF_RANGE, PROFILE_TRUNCATED = 1, 2, 4, 8
+
+PLANE_DTYPE = np.dtype([
+    ("coef", "<f8", (3,)), ("normal", "<f8", (3,)), ("offset", "<f8"), ("centroid", "<f8", (3,)),
+    ("rms_px", "<f8"), ("max_abs_px", "<f4"), ("x0", "<i4"), ("y0", "<i4"), ("frame", "<i4"),
+    ("area", "<i4"), ("n_valid", "<i4"), ("n_inliers", "<i4"), ("fits", "<i4"), ("flags", "<u4"),
+    ("reserved", "<i4")])
+assert PLANE_DTYPE.itemsize == 128
+PLANE_DISTANCE_DTYPE = np.dtype([
+    ("p", "<f4", (3,)), ("d", "<f4"), ("distance", "<f8"), ("n", "<i4"), ("flags", "<u4")])
+assert PLANE_DISTANCE_DTYPE.itemsize == 32
+
+# sdr_plane.flags (SDR_PLANE_*) and sdr_plane_distance.flags (SDR_PDIST_*)
+PLANE_OK, PLANE_DEGENERATE, PLANE_NONFINITE, PLANE_OUT_OF_RANGE = 1, 2, 4, 8
+PDIST_VALID, PDIST_OUT_OF_RANGE, PDIST_NO_PLANE = 1, 2, 4
+
+
+def as_queries(points) -> np.ndarray:
+    """(K, 4) int32 {frame, x, y, plane} from (K, 4) / (K, 3) {x, y, plane} on frame 0 / one tuple."""
+    q = np.asarray(points)
+    if q.size == 0:
+        return np.zeros((0, 4), np.int32)
+    if q.ndim == 1:
+        q = q[None, :]
+    if q.ndim != 2 or q.shape[1] not in (3, 4):
+        raise SDRError(-1, "points must be (K, 4) {frame, x, y, plane} or (K, 3) {x, y, plane}")
+    if q.shape[1] == 3:
+        q = np.concatenate([np.zeros((q.shape[0], 1), q.dtype), q], axis=1)
+    return np.ascontiguousarray(q, dtype=np.int32)
+
+
+def plane_angle_deg(a, b) -> float:
+    """Angle between the normals of two PLANE_DTYPE records, in degrees (a host dot product)."""
+    c = float(np.dot(np.asarray(a["normal"], np.float64), np.asarray(b["normal"], np.float64)))
+    return float(np.degrees(np.arccos(min(1.0, abs(c)))))
 
 
 def as_segments(segments) -> np.ndarray:
@@ -74,21 +112,22 @@ class _SegmentStaging:
     event recorded behind that transfer.  A slot is reused only after its event has completed,
     which the host waits for only when `slots` uploads are still in flight."""
 
-    def __init__(self, slots: int = 8):
+    def __init__(self, slots: int = 8, cols: int = 5):
         self._ring = [None] * slots
         self._next = 0
+        self._cols = cols
 
     def upload(self, host: np.ndarray, dev, stream):
         K = host.shape[0]
         if K == 0:
-            return torch.empty((0, 5), dtype=torch.int32, device=dev)
+            return torch.empty((0, self._cols), dtype=torch.int32, device=dev)
         i = self._next
         self._next = (i + 1) % len(self._ring)
         slot = self._ring[i]
         if slot is not None:
             slot[1].synchronize()  # the slot's last transfer has left the buffer
         if slot is None or slot[0].shape[0] < K:
-            slot = (torch.empty((max(K, 64), 5), dtype=torch.int32, pin_memory=True), torch.cuda.Event())
+            slot = (torch.empty((max(K, 64), self._cols), dtype=torch.int32, pin_memory=True), torch.cuda.Event())
             self._ring[i] = slot
         buf, ev = slot
         buf[:K].copy_(torch.from_numpy(host))
@@ -110,12 +149,13 @@ class Ruler:
         self.min_disp, self.conf_min = float(min_disp), float(conf_min)
         self.profile = bool(profile)
         self.device = int(device)
-        self._staging = {}  # device index -> _SegmentStaging
+        self._staging = {}  # (device index, columns) -> _SegmentStaging
 
     def _upload_segments(self, host: np.ndarray, dev, stream):
-        st = self._staging.get(dev.index)
+        key = (dev.index, host.shape[1])
+        st = self._staging.get(key)
         if st is None:
-            st = self._staging[dev.index] = _SegmentStaging()
+            st = self._staging[key] = _SegmentStaging(cols=host.shape[1])
         return st.upload(host, dev, stream)
 
     def _params(self, cap: int) -> RulerParams:
@@ -131,30 +171,17 @@ class Ruler:
             rec, prof = self.measure_device(disparity, segments, conf)
             out = _records(rec.cpu().numpy())
             return (out, prof.cpu().numpy()) if self.profile else out
-        d = np.asarray(disparity)
-        if d.dtype not in (np.float32, np.int16):
-            raise SDRError(-5, "disparity must be float32 (px) or int16 (1/16 px)")
-        d = _frames3(d, "disparity")
-        if d.strides[2] != d.itemsize or d.strides[1] % d.itemsize or d.strides[0] % d.itemsize \
-                or min(d.strides) <= 0:
-            d = np.ascontiguousarray(d)
+        d, c, rs, fs = self._host_maps(disparity, conf)
         F, H, W = d.shape
-        c = None
-        if conf is not None:
-            c = np.ascontiguousarray(_frames3(np.asarray(conf, dtype=np.float32), "conf"))
-            if c.shape != d.shape:
-                raise SDRError(-1, "conf must have the disparity's shape")
         segs = as_segments(segments)
         K = segs.shape[0]
         cap = self._cap(segs, W, H, F)
         rec = np.zeros(K, MEASUREMENT_DTYPE)
         prof = np.full((K, cap, 4), np.nan, np.float32) if self.profile else None
         p = self._params(cap)
-        rs = d.strides[1] // d.itemsize
         with _on_device(self.device):
             rc = lib().sdr_measure_disp(
-                d.ctypes.data, DISP_F32 if d.dtype == np.float32 else DISP_S16, rs,
-                rs * H if F == 1 else d.strides[0] // d.itemsize, W, H, F,
+                d.ctypes.data, DISP_F32 if d.dtype == np.float32 else DISP_S16, rs, fs, W, H, F,
                 c.ctypes.data if c is not None else None, _Q(self.Q), ctypes.byref(p),
                 segs.ctypes.data if K else None, K, rec.ctypes.data if K else None,
                 prof.ctypes.data if prof is not None and prof.size else None)
@@ -182,23 +209,13 @@ class Ruler:
         copy on `stream` (the host does not wait for the stream's earlier work), or a CUDA int32
         tensor (K, 5) (then profile_cap defaults to max(W, H)).  profile_cap: rows a segment of the profile (0: the record's profile fields
         only).  profile_out: a (K, cap, 4) tensor to write the profile into."""
-        d = disparity
-        if not _is_cuda(d) or d.dtype not in (torch.float32, torch.int16):
+        if not _is_cuda(disparity):
             raise SDRError(-5, "measure_device expects a CUDA float32 or int16 tensor")
-        if d.dim() == 2:
-            d = d.unsqueeze(0)
-        if d.dim() != 3:
-            raise SDRError(-1, "disparity must be (H, W) or (F, H, W)")
-        F, H, W = d.shape
-        dev = d.device
+        dev = disparity.device
         s = stream if stream is not None else torch.cuda.current_stream(dev.index)
         with torch.cuda.stream(s):
-            if d.stride(2) != 1 or d.stride(1) < W or d.stride(0) < d.stride(1):
-                d = d.contiguous()  # on `s`, ahead of the kernel
-            if conf is not None:
-                if not _is_cuda(conf) or conf.dtype != torch.float32 or conf.numel() != d.numel():
-                    raise SDRError(-5, "conf must be a CUDA float32 tensor of the disparity's shape")
-                conf = conf.contiguous()
+            d, conf = self._device_maps(disparity, conf)  # copies, if any, on `s`, ahead of the kernel
+            F, H, W = d.shape
             if _is_cuda(segments):
                 if segments.dtype != torch.int32 or segments.dim() != 2 or segments.shape[1] != 5:
                     raise SDRError(-5, "device segments must be an int32 tensor (K, 5)")
@@ -231,6 +248,164 @@ class Ruler:
                 prof.data_ptr() if prof is not None and prof.numel() else None,
                 ctypes.c_void_p(s.cuda_stream)))
         return rec, prof
+
+    # ---- the maps of the disparity-mode calls ----
+    @staticmethod
+    def _host_maps(disparity, conf):
+        """(d (F, H, W), conf or None, row stride, frame stride) of host maps for the host ABI."""
+        d = np.asarray(disparity)
+        if d.dtype not in (np.float32, np.int16):
+            raise SDRError(-5, "disparity must be float32 (px) or int16 (1/16 px)")
+        d = _frames3(d, "disparity")
+        if d.strides[2] != d.itemsize or d.strides[1] % d.itemsize or d.strides[0] % d.itemsize \
+                or min(d.strides) <= 0:
+            d = np.ascontiguousarray(d)
+        F, H, W = d.shape
+        c = None
+        if conf is not None:
+            c = np.ascontiguousarray(_frames3(np.asarray(conf, dtype=np.float32), "conf"))
+            if c.shape != d.shape:
+                raise SDRError(-1, "conf must have the disparity's shape")
+        rs = d.strides[1] // d.itemsize
+        return d, c, rs, (rs * H if F == 1 else d.strides[0] // d.itemsize)
+
+    @staticmethod
+    def _device_maps(disparity, conf):
+        """(d (F, H, W), conf or None) of CUDA maps, made contiguous on the current stream."""
+        d = disparity
+        if not _is_cuda(d) or d.dtype not in (torch.float32, torch.int16):
+            raise SDRError(-5, "expected a CUDA float32 or int16 disparity tensor")
+        if d.dim() == 2:
+            d = d.unsqueeze(0)
+        if d.dim() != 3:
+            raise SDRError(-1, "disparity must be (H, W) or (F, H, W)")
+        if d.stride(2) != 1 or d.stride(1) < d.shape[2] or d.stride(0) < d.stride(1):
+            d = d.contiguous()
+        if conf is not None:
+            if not _is_cuda(conf) or conf.dtype != torch.float32 or conf.numel() != d.numel():
+                raise SDRError(-5, "conf must be a CUDA float32 tensor of the disparity's shape")
+            conf = conf.contiguous()
+        return d, conf
+
+    # ---- against a surface: plane fit and point-to-plane distance ----
+    def _plane_params(self, iterations, inlier_px, min_inliers) -> PlaneParams:
+        return PlaneParams(int(iterations), int(min_inliers), float(inlier_px), self.min_disp, self.conf_min)
+
+    def fit_plane(self, disparity, regions, conf=None, iterations: int = 3, inlier_px: float = 1.0,
+                  min_inliers: int = 16):
+        """Robust plane fits (sdr.h, "the ruler against a surface") of K rectangles
+        (frame, x0, y0, x1, y1) / (x0, y0, x1, y1), corners in any order: a PLANE_DTYPE array."""
+        if _is_cuda(disparity):
+            rec = self.fit_plane_device(disparity, regions, conf, iterations, inlier_px, min_inliers)
+            return rec.cpu().numpy().reshape(-1).view(PLANE_DTYPE)
+        d, c, rs, fs = self._host_maps(disparity, conf)
+        F, H, W = d.shape
+        regs = as_segments(regions)
+        K = regs.shape[0]
+        rec = np.zeros(K, PLANE_DTYPE)
+        p = self._plane_params(iterations, inlier_px, min_inliers)
+        with _on_device(self.device):
+            rc = lib().sdr_fit_planes(
+                d.ctypes.data, DISP_F32 if d.dtype == np.float32 else DISP_S16, rs, fs, W, H, F,
+                c.ctypes.data if c is not None else None, _Q(self.Q), ctypes.byref(p),
+                regs.ctypes.data if K else None, K, rec.ctypes.data if K else None)
+        check(rc)
+        return rec
+
+    def fit_plane_device(self, disparity, regions, conf=None, iterations: int = 3, inlier_px: float = 1.0,
+                         min_inliers: int = 16, stream=None):
+        """Enqueues the fits on `stream` (default: the current stream) and returns the records as
+        a uint8 tensor (K, 128) without synchronising (view its host copy as PLANE_DTYPE, or hand
+        it to plane_distance_device).  regions: host (K, 5) / (K, 4) or a CUDA int32 (K, 5)."""
+        if not _is_cuda(disparity):
+            raise SDRError(-5, "fit_plane_device expects a CUDA float32 or int16 tensor")
+        dev = disparity.device
+        s = stream if stream is not None else torch.cuda.current_stream(dev.index)
+        with torch.cuda.stream(s):
+            d, conf = self._device_maps(disparity, conf)
+            F, H, W = d.shape
+            if _is_cuda(regions):
+                if regions.dtype != torch.int32 or regions.dim() != 2 or regions.shape[1] != 5:
+                    raise SDRError(-5, "device regions must be an int32 tensor (K, 5)")
+                regs = regions.contiguous()
+            else:
+                regs = self._upload_segments(as_segments(regions), dev, s)
+            K = regs.shape[0]
+            rec = torch.empty((K, 128), dtype=torch.uint8, device=dev)
+            p = self._plane_params(iterations, inlier_px, min_inliers)
+            check(lib().sdr_fit_planes_device(
+                d.data_ptr(), DISP_F32 if d.dtype == torch.float32 else DISP_S16, d.stride(1),
+                d.stride(1) * H if F == 1 else d.stride(0), W, H, F,
+                conf.data_ptr() if conf is not None else None, _Q(self.Q), ctypes.byref(p),
+                regs.data_ptr() if K else None, K, rec.data_ptr() if K else None,
+                ctypes.c_void_p(s.cuda_stream)))
+        return rec
+
+    def plane_distance(self, disparity, planes, points, conf=None):
+        """Signed distances of sampled points to fitted planes: a PLANE_DISTANCE_DTYPE array of K.
+        planes: PLANE_DTYPE records or fit_plane_device's tensor; points: (K, 4)
+        {frame, x, y, plane} or (K, 3) {x, y, plane} on frame 0; each point is sampled with the
+        ruler's radius and min_count."""
+        if _is_cuda(disparity):
+            out = self.plane_distance_device(disparity, planes, points, conf)
+            return out.cpu().numpy().reshape(-1).view(PLANE_DISTANCE_DTYPE)
+        if _is_cuda(planes):
+            planes = planes.cpu().numpy()
+        pl = np.ascontiguousarray(planes).reshape(-1).view(np.uint8).view(PLANE_DTYPE)
+        d, c, rs, fs = self._host_maps(disparity, conf)
+        F, H, W = d.shape
+        qs = as_queries(points)
+        K, P = qs.shape[0], pl.shape[0]
+        out = np.zeros(K, PLANE_DISTANCE_DTYPE)
+        p = self._params(0)
+        p.profile = 0
+        with _on_device(self.device):
+            rc = lib().sdr_plane_distance(
+                d.ctypes.data, DISP_F32 if d.dtype == np.float32 else DISP_S16, rs, fs, W, H, F,
+                c.ctypes.data if c is not None else None, _Q(self.Q), ctypes.byref(p),
+                pl.ctypes.data if P else None, P, qs.ctypes.data if K else None, K,
+                out.ctypes.data if K else None)
+        check(rc)
+        return out
+
+    def plane_distance_device(self, disparity, planes, points, conf=None, stream=None):
+        """Enqueues the queries on `stream` and returns a uint8 tensor (K, 32) without
+        synchronising.  planes: the uint8 tensor (P, 128) of fit_plane_device (a fit and its queries
+        then chain on one stream with no host round trip) or host records; points: host (K, 4) /
+        (K, 3) or a CUDA int32 (K, 4)."""
+        if not _is_cuda(disparity):
+            raise SDRError(-5, "plane_distance_device expects a CUDA float32 or int16 tensor")
+        dev = disparity.device
+        s = stream if stream is not None else torch.cuda.current_stream(dev.index)
+        with torch.cuda.stream(s):
+            d, conf = self._device_maps(disparity, conf)
+            F, H, W = d.shape
+            if _is_cuda(planes):
+                if planes.dtype != torch.uint8 or planes.numel() % 128:
+                    raise SDRError(-5, "device planes must be a uint8 tensor (P, 128)")
+                pl = planes.contiguous()
+                P = pl.numel() // 128
+            else:
+                host = np.ascontiguousarray(planes).reshape(-1).view(np.uint8).reshape(-1, 128)
+                P = host.shape[0]
+                pl = torch.from_numpy(host.copy()).to(dev) if P else None
+            if _is_cuda(points):
+                if points.dtype != torch.int32 or points.dim() != 2 or points.shape[1] != 4:
+                    raise SDRError(-5, "device points must be an int32 tensor (K, 4)")
+                qs = points.contiguous()
+            else:
+                qs = self._upload_segments(as_queries(points), dev, s)
+            K = qs.shape[0]
+            out = torch.empty((K, 32), dtype=torch.uint8, device=dev)
+            p = self._params(0)
+            p.profile = 0
+            check(lib().sdr_plane_distance_device(
+                d.data_ptr(), DISP_F32 if d.dtype == torch.float32 else DISP_S16, d.stride(1),
+                d.stride(1) * H if F == 1 else d.stride(0), W, H, F,
+                conf.data_ptr() if conf is not None else None, _Q(self.Q), ctypes.byref(p),
+                pl.data_ptr() if P else None, P, qs.data_ptr() if K else None, K,
+                out.data_ptr() if K else None, ctypes.c_void_p(s.cuda_stream)))
+        return out
 
     # ---- XYZ-map mode (the reference's measurement) ----
     def measure_xyz(self, depth_map, segments):
