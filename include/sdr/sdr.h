@@ -670,6 +670,103 @@ int sdr_plane_distance(const void* disp, int disp_type, size_t stride, size_t fr
                        const sdr_ruler_params* params, const sdr_plane* planes, int P,
                        const sdr_plane_query* queries, int K, struct sdr_plane_distance* out);
 
+/* ---- the dominant planes of a region: a seeded search without a prior ----
+ * sdr_find_planes* finds up to max_planes planes in one rectangle, the largest first, and says
+ * which pixel lies on which.  Fit 0 of sdr_fit_planes is a least-squares fit of every valid pixel,
+ * which lies on no surface when the rectangle holds several; here each round draws M three-point
+ * hypotheses, scores them on the pixels no earlier round has claimed, refits the winner with the
+ * plane fit's schedule and claims its inliers.  Hypothesis generation, scoring and selection are
+ * exact integer arithmetic; the refit is the plane fit's (exact moments, the same solve): every
+ * output is defined to the bit, for any grid shape and any order the workgroups finish in.
+ *   - Region, valid pixel, q, u, v, xs, xe, ys, ye, rw = xe-xs+1, rh = ye-ys+1, area = rw*rh, the
+ *     moments, the solve, the residual r and T = (double)fit.inlier_px * 16: the plane fit's,
+ *     above.  Tq = (int64)floor(T) (at most 1024).  A pixel is FREE in round r iff it is valid and
+ *     no round before r has claimed it.
+ *   - Round r = 0 .. max_planes-1, while the search has not stopped:
+ *     1. Draws.  mix(x) on uint32: x ^= x>>16; x *= 0x7feb352d; x ^= x>>15; x *= 0x846ca68b;
+ *        x ^= x>>16.  R(r,h,j,t) = mix(mix(mix(seed ^ (0x9E3779B9u*(r+1))) ^ h) ^ (16*j + t)).
+ *        Hypothesis h in [0, M) draws the points j = 0, 1, 2; point j tries t = 0..15 the pixel of
+ *        index p = ((uint64)R * area) >> 32 of the region's row-major order (v = p / rw,
+ *        u = p % rw) and takes the first try that is free.  No free pixel in 16 tries makes the
+ *        hypothesis VOID.  (Two points may be the same pixel: C == 0 below.)
+ *     2. The plane through P_j = (u_j, v_j, q_j), with (du1, dv1, dq1) = P1 - P0 and
+ *        (du2, dv2, dq2) = P2 - P0:  A = dv1*dq2 - dq1*dv2;  B = dq1*du2 - du1*dq2;
+ *        C = du1*dv2 - dv1*du2;  D = A*u0 + B*v0 + C*q0 (int64).  C == 0 makes the hypothesis
+ *        void.  The guards keep |du|, |dv| <= 8191 and |dq| <= 65536 (|q| <= 32768), so
+ *        |A|, |B| <= 2 * 8191 * 65536 < 2^31 and, as du*dv < area <= 2^24, |C| < 2^25 < 2^28: they
+ *        are int32.  A*u, B*v < 2^44, C*q < 2^43, |D| < 2^45, Tq*|C| < 2^38: every product and sum
+ *        below stays below 2^46 in int64.
+ *     3. Score of a hypothesis that is not void: the number of free pixels with
+ *        |A*u + B*v + C*q - D| <= Tq * |C|, in int64, no floating point.  (Its own three points
+ *        count: a score is at least 3.)
+ *     4. Pick.  The winner is the highest score among the hypotheses that are not void, ties to the
+ *        lowest h.  All void: the search stops with SDR_SEARCH_NO_HYPOTHESIS.  The winner's score
+ *        < fit.min_inliers: it stops with SDR_SEARCH_LOW_SCORE.
+ *     5. Seed plane in 1/16 px, each one rounded double division of exactly converted integers:
+ *        a = -(double)A / (double)C;  b = -(double)B / (double)C;  c = (double)D / (double)C.
+ *     6. Refits k = 1..fit.iterations, the plane fit's schedule with the seed plane in the place of
+ *        fit 0: the set of refit k is the free pixels with |r| <= T * 2^(iterations-k) against the
+ *        previous plane; its nine moments, the same solve (degenerate also with fewer than
+ *        min_inliers pixels).  A degenerate solve stops the search: SDR_SEARCH_REFIT_DEGENERATE.
+ *     7. The inliers are the free pixels with |r| <= T against the last refit's plane.  Fewer than
+ *        fit.min_inliers: the search stops with SDR_SEARCH_FEW_INLIERS and claims nothing.
+ *        Otherwise they are claimed (label r) and record r is what sdr_fit_planes writes for the
+ *        region, with: the plane the last refit's; n_valid the free pixels at the start of the
+ *        round; n_inliers, rms_px, max_abs_px over the claimed pixels; fits = iterations + 1; the
+ *        centroid from the last refit's moments; area, x0, y0, frame the region's; flags
+ *        SDR_PLANE_OK or SDR_PLANE_NONFINITE (a non-finite 3-D plane still claims its pixels and
+ *        the search goes on).  rounds[r] = {winner h, its score, the number of void hypotheses, 0}.
+ *   - After a stop in round r: *count = r (max_planes when no round stopped); the records r.. are
+ *     the plane fit's DEGENERATE record (floats the canonical NaN, n_valid, n_inliers, fits 0; area,
+ *     x0, y0, frame the region's); rounds[r] = {h, score, voids, stop code} with what the round had
+ *     found: {-1, 0, M, NO_HYPOTHESIS}, else the winner and its score; rounds after r are
+ *     {-1, 0, 0, SDR_SEARCH_NOT_RUN}.
+ *   - A region out of range (the plane fit's rule): *count = 0, every record the plane fit's
+ *     OUT_OF_RANGE record, every round {-1, 0, 0, SDR_SEARCH_NOT_RUN}, every label 255.
+ *   - Labels: uint8 [height][width] of the region's frame, 255 everywhere but on claimed pixels,
+ *     which hold their round: the count of label r is planes[r].n_inliers.
+ *   - A region one pixel wide or high has C == 0 in every hypothesis: count 0, NO_HYPOTHESIS. */
+typedef struct sdr_plane_search_params { /* 64 bytes */
+    sdr_plane_params fit; /* as in sdr_fit_planes, but iterations in 1..8 */
+    int32_t max_planes;   /* rounds, 1..8 */
+    int32_t hypotheses;   /* M, 1..4096 */
+    uint32_t seed;
+    int32_t reserved[5];  /* 0 */
+} sdr_plane_search_params;
+
+enum { /* sdr_plane_search_round.stop */
+    SDR_SEARCH_RAN = 0, SDR_SEARCH_NO_HYPOTHESIS = 1, SDR_SEARCH_LOW_SCORE = 2,
+    SDR_SEARCH_REFIT_DEGENERATE = 3, SDR_SEARCH_FEW_INLIERS = 4, SDR_SEARCH_NOT_RUN = 5
+};
+
+typedef struct sdr_plane_search_round { /* 16 bytes */
+    int32_t hypothesis;  /* the winner, -1 without one */
+    int32_t score;       /* its score */
+    int32_t voids;       /* void hypotheses of the round */
+    uint32_t stop;       /* SDR_SEARCH_* */
+} sdr_plane_search_round;
+
+/* {{3, 64, 1.0f, -1.0f, 0.0f, {0, 0, 0}}, 4, 256, 0, {0, 0, 0, 0, 0}} */
+void sdr_plane_search_params_default(sdr_plane_search_params* p);
+/* One region (d_region: one sdr_segment on the device) of device maps (arguments as
+ * sdr_fit_planes_device), asynchronous on `stream` with no host synchronisation between rounds: a
+ * fixed sequence of launches for max_planes rounds, which a stopped search leaves at once.  Writes
+ * every one of the max_planes records of d_planes, *d_count, and when they are not NULL the
+ * max_planes records of d_rounds and the width * height labels of d_labels; hypotheses, scores,
+ * moments, the search's state and, without d_labels, the claim map are stream-ordered scratch.
+ * Every argument is checked on the host before any device call. */
+int sdr_find_planes_device(const void* d_disp, int disp_type, size_t stride, size_t frame_stride,
+                           int width, int height, int nframes, const float* d_conf,
+                           const double Q[16], const sdr_plane_search_params* params,
+                           const sdr_segment* d_region, sdr_plane* d_planes, int32_t* d_count,
+                           sdr_plane_search_round* d_rounds, uint8_t* d_labels, void* stream);
+/* Host-pointer version (synchronous; per-thread persistent device buffers as sdr_fit_planes). */
+int sdr_find_planes(const void* disp, int disp_type, size_t stride, size_t frame_stride, int width,
+                    int height, int nframes, const float* conf, const double Q[16],
+                    const sdr_plane_search_params* params, const sdr_segment* region,
+                    sdr_plane* planes, int32_t* count, sdr_plane_search_round* rounds,
+                    uint8_t* labels);
+
 /* Bytes of device scratch the handle holds for the given frame shape (for capacity planning);
  * 0 when compute would refuse the shape or parameters.  sdr_sgbm_scratch_bytes is the CV_8UC1
  * figure, sdr_sgbm_scratch_bytes_cn takes the channel count (1 or 3: colour input holds three

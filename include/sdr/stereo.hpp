@@ -535,6 +535,45 @@ public:
         return fit_plane(disparity, {sdr_segment{0, a.x, a.y, b.x, b.y}}, conf, iterations, inlier_px,
                          min_inliers)[0];
     }
+    // The dominant planes of a rectangle without a prior (sdr.h, "the dominant planes of a region"):
+    // a seeded search, the largest plane first.  planes: the planes found (rounds that stopped are
+    // left out); rounds: one record a round of max_planes; labels (with_labels): CV_8UC1 of the
+    // map's size, the index of the plane a pixel lies on, 255 on none
+    struct PlaneSearch {
+        std::vector<Plane> planes;
+        std::vector<sdr_plane_search_round> rounds;
+        Mat labels;
+    };
+    PlaneSearch find_planes(const Mat& disparity, Point a, Point b, const Mat* conf = nullptr, int max_planes = 4,
+                            int hypotheses = 256, uint32_t seed = 0, int iterations = 3, float inlier_px = 1.0f,
+                            int min_inliers = 64, bool with_labels = false) const {
+        check_maps(disparity, conf, "find_planes");
+        const size_t es = elem_size(disparity.type);
+        sdr_plane_search_params sp;
+        sdr_plane_search_params_default(&sp);
+        sp.fit.iterations = iterations;
+        sp.fit.inlier_px = inlier_px;
+        sp.fit.min_inliers = min_inliers;
+        sp.fit.min_disp = p_.min_disp;
+        sp.fit.conf_min = p_.conf_min;
+        sp.max_planes = max_planes;
+        sp.hypotheses = hypotheses;
+        sp.seed = seed;
+        const size_t n = max_planes > 0 ? (size_t)max_planes : 0;
+        PlaneSearch out;
+        out.planes.resize(n);
+        out.rounds.resize(n);
+        if (with_labels) out.labels = Mat::pageable(disparity.rows, disparity.cols, CV_8UC1);
+        const sdr_segment reg{0, a.x, a.y, b.x, b.y};
+        int32_t count = 0;
+        check(sdr_find_planes(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16,
+                              disparity.step / es, disparity.step / es * disparity.rows, disparity.cols,
+                              disparity.rows, 1, conf ? conf->ptr<float>(0) : nullptr, q_, &sp, &reg,
+                              n ? out.planes.data() : nullptr, &count, n ? out.rounds.data() : nullptr,
+                              with_labels ? out.labels.data : nullptr));
+        out.planes.resize((size_t)count);
+        return out;
+    }
     // signed distances of points {frame, x, y, plane}, sampled with the ruler's radius and
     // min_count, to `planes`; positive towards the camera
     std::vector<PlaneDistance> plane_distance(const Mat& disparity, const std::vector<Plane>& planes,

@@ -16,7 +16,8 @@ from .ximgproc import (  # noqa: F401
 from .ruler import (  # noqa: F401
     MEASUREMENT_DTYPE, PDIST_NO_PLANE, PDIST_OUT_OF_RANGE, PDIST_VALID, PLANE_DEGENERATE,
     PLANE_DISTANCE_DTYPE, PLANE_DTYPE, PLANE_NONFINITE, PLANE_OK, PLANE_OUT_OF_RANGE,
-    MeasurementLog, Ruler, plane_angle_deg,
+    PLANE_SEARCH_ROUND_DTYPE, SEARCH_FEW_INLIERS, SEARCH_LOW_SCORE, SEARCH_NO_HYPOTHESIS, SEARCH_NOT_RUN,
+    SEARCH_RAN, SEARCH_REFIT_DEGENERATE, MeasurementLog, Ruler, plane_angle_deg,
 )
 from .stereo_disparity import StereoDisparity  # noqa: F401
 
@@ -28,5 +29,6 @@ __all__ = [
     "colormap_lut", "COLORMAP_JET", "COLORMAP_TURBO", "host_empty", "COST_BT", "COST_CENSUS",
     "Ruler", "MeasurementLog", "MEASUREMENT_DTYPE", "PLANE_DTYPE", "PLANE_DISTANCE_DTYPE",
     "PLANE_OK", "PLANE_DEGENERATE", "PLANE_NONFINITE", "PLANE_OUT_OF_RANGE", "PDIST_VALID",
-    "PDIST_OUT_OF_RANGE", "PDIST_NO_PLANE", "plane_angle_deg",
+    "PDIST_OUT_OF_RANGE", "PDIST_NO_PLANE", "plane_angle_deg", "PLANE_SEARCH_ROUND_DTYPE", "SEARCH_RAN",
+    "SEARCH_NO_HYPOTHESIS", "SEARCH_LOW_SCORE", "SEARCH_REFIT_DEGENERATE", "SEARCH_FEW_INLIERS", "SEARCH_NOT_RUN",
 ]

@@ -131,6 +131,18 @@ class PlaneDistance(ctypes.Structure):
                 ("n", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
+class PlaneSearchParams(ctypes.Structure):
+    """sdr_plane_search_params (64 bytes)."""
+    _fields_ = [("fit", PlaneParams), ("max_planes", ctypes.c_int32), ("hypotheses", ctypes.c_int32),
+                ("seed", ctypes.c_uint32), ("reserved", ctypes.c_int32 * 5)]
+
+
+class PlaneSearchRound(ctypes.Structure):
+    """sdr_plane_search_round (16 bytes)."""
+    _fields_ = [("hypothesis", ctypes.c_int32), ("score", ctypes.c_int32), ("voids", ctypes.c_int32),
+                ("stop", ctypes.c_uint32)]
+
+
 _lib = None
 _path = LIB_PATH
 
@@ -262,6 +274,11 @@ SIGNATURES = [
                             _c.POINTER(PlaneParams), _vp, _i, _vp]),
     ("sdr_plane_distance", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _c.POINTER(_c.c_double),
                                 _c.POINTER(RulerParams), _vp, _i, _vp, _i, _vp]),
+    ("sdr_plane_search_params_default", None, [_c.POINTER(PlaneSearchParams)]),
+    ("sdr_find_planes_device", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _c.POINTER(_c.c_double),
+                                    _c.POINTER(PlaneSearchParams), _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("sdr_find_planes", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _c.POINTER(_c.c_double),
+                             _c.POINTER(PlaneSearchParams), _vp, _vp, _vp, _vp, _vp]),
     ("sdr_build_id", _c.c_char_p, []),
     ("sdr_last_error", _c.c_char_p, []),
     ("sdr_abi_version", _i, []),

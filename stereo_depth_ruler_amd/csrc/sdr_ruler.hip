@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <string>
+#include <type_traits>
 
 #include "sdr_device.hpp"
 #include "sdr_internal.hpp"
@@ -446,22 +447,40 @@ __device__ __forceinline__ bool plane_q(const int16_t* p, float min_disp, int* q
     return (float)v * 0.0625f > min_disp;
 }
 
+// The plane search's state (sdr_find_planes*), written by its one-workgroup kernels and read by the
+// kernels behind them on the stream.
+struct SearchState {
+    int stopped;      // a round has stopped the search (or the region is out of range)
+    int winner;       // the round's winning hypothesis
+    int score, voids;
+    double a, b, c;   // its seed plane, in 1/16 px
+};
+constexpr uint8_t kFreeLabel = 255;
+
 // One sweep over the regions' pixels: grid (slices of a W x H frame, regions).  Sweep 0 sums the
 // moments of the valid pixels, sweep s = 1..iterations those of the pixels within the scheduled
 // band of fit s - 1, sweep iterations + 1 the statistics against the last fit.  A region that is
 // out of range, a slice past its area and a chain that a degenerate fit has stopped leave at once
 // (block-uniform); no workgroup waits on another.
-template <typename T>
+//
+// kSearch (sdr_find_planes*): one region, `acc` its round's accumulators, the sweeps 1..iterations + 1
+// only; a pixel counts only while it is free (its label 255), sweep 1's previous plane is the
+// round's seed plane, and a stopped search leaves at once.  The sums and the residual are the
+// same code either way.
+template <typename T, bool kSearch>
 __global__ __launch_bounds__(kPlaneThreads) void k_plane_sweep(const T* __restrict__ disp, size_t stride,
                                                                size_t fstride, int W, int H, int F,
                                                                const float* __restrict__ conf,
                                                                sdr_plane_params P,
                                                                const sdr_segment* __restrict__ regs,
-                                                               long long* __restrict__ acc, int sweep) {
+                                                               long long* __restrict__ acc, int sweep,
+                                                               const uint8_t* __restrict__ labels,
+                                                               const SearchState* __restrict__ state) {
 #pragma clang fp contract(off)
     __shared__ long long red[kPlaneWaves][kPlaneMoments];
     const int k = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (kSearch && state->stopped) return;  // block-uniform
     const sdr_segment sg = regs[k];
     if (!segment_in_range(sg, W, H, F)) return;
     const PlaneRect R = plane_rect(sg);
@@ -473,12 +492,16 @@ __global__ __launch_bounds__(kPlaneThreads) void k_plane_sweep(const T* __restri
     PlaneFit fit = {0.0, 0.0, 0.0, true};
     double band = 0.0;
     if (sweep > 0) {
-        fit = plane_solve(A + (size_t)(sweep - 1) * kPlaneSlots, P.min_inliers);
+        if (kSearch && sweep == 1)
+            fit = PlaneFit{state->a, state->b, state->c, true};
+        else
+            fit = plane_solve(A + (size_t)(sweep - 1) * kPlaneSlots, P.min_inliers);
         if (!fit.ok) return;  // the chain has stopped: the later sweeps' accumulators stay 0
         band = (double)P.inlier_px * 16.0 * (double)(1 << (last ? 0 : P.iterations - sweep));
     }
     const T* fd = disp + (size_t)sg.frame * fstride + (size_t)R.ys * stride + (size_t)R.xs;
     const float* fc = conf ? conf + ((size_t)sg.frame * H + (size_t)R.ys) * W + (size_t)R.xs : nullptr;
+    const uint8_t* fl = kSearch ? labels + (size_t)R.ys * W + (size_t)R.xs : nullptr;
 
     long long m[kPlaneMoments];
 #pragma unroll
@@ -492,6 +515,7 @@ __global__ __launch_bounds__(kPlaneThreads) void k_plane_sweep(const T* __restri
         int q;
         bool ok = plane_q(fd + (size_t)v * stride + u, P.min_disp, &q);
         if (fc) ok = ok && fc[(size_t)v * W + u] >= P.conf_min;
+        if (kSearch) ok = ok && fl[(size_t)v * W + u] == kFreeLabel;
         double r = 0.0;
         if (sweep > 0) {
             r = (double)q - plane_at(fit, (double)u, (double)v);
@@ -565,48 +589,13 @@ __device__ __forceinline__ void plane_reproject(const Q16& Q, double x, double y
     o[2] = h[2] / h[3];
 }
 
-// The records, one lane a region, from the accumulators the sweeps have left.
-__global__ __launch_bounds__(64) void k_plane_finish(const sdr_segment* __restrict__ regs, int K, int W,
-                                                     int H, int F, Q16 Q, sdr_plane_params P,
-                                                     const long long* __restrict__ acc,
-                                                     sdr_plane* __restrict__ out) {
+// The statistics, coefficients and 3-D plane of a record from the last fit, its moment set M and
+// the statistics sweep's sums L = {n_inliers, See, the bits of max |r|}; o.flags becomes
+// SDR_PLANE_OK or SDR_PLANE_NONFINITE.
+__device__ __forceinline__ void plane_record(sdr_plane& o, const PlaneRect& R, const PlaneFit& fit,
+                                             const long long* __restrict__ M,
+                                             const long long* __restrict__ L, const Q16& Q) {
 #pragma clang fp contract(off)
-    const int k = blockIdx.x * 64 + threadIdx.x;
-    if (k >= K) return;
-    const sdr_segment sg = regs[k];
-    const double qn = __builtin_nan("");
-    sdr_plane o;
-    for (int i = 0; i < 3; i++) o.coef[i] = o.normal[i] = o.centroid[i] = qn;
-    o.offset = o.rms_px = qn;
-    o.max_abs_px = ruler_nan();
-    o.x0 = min(sg.x0, sg.x1);
-    o.y0 = min(sg.y0, sg.y1);
-    o.frame = sg.frame;
-    o.area = o.n_valid = o.n_inliers = o.fits = 0;
-    o.flags = SDR_PLANE_OUT_OF_RANGE;
-    o.reserved = 0;
-    if (!segment_in_range(sg, W, H, F)) {
-        out[k] = o;
-        return;
-    }
-    const PlaneRect R = plane_rect(sg);
-    const long long* A = acc + (size_t)k * (size_t)(P.iterations + 2) * kPlaneSlots;
-    o.area = R.rw * R.rh;
-    o.n_valid = (int)A[0];
-    PlaneFit fit = {0.0, 0.0, 0.0, false};
-    const long long* M = A;
-    for (int s = 0; s <= P.iterations; s++) {
-        M = A + (size_t)s * kPlaneSlots;
-        fit = plane_solve(M, P.min_inliers);
-        if (!fit.ok) break;
-        o.fits++;
-    }
-    if (!fit.ok) {
-        o.flags = SDR_PLANE_DEGENERATE;
-        out[k] = o;
-        return;
-    }
-    const long long* L = A + (size_t)(P.iterations + 1) * kPlaneSlots;
     o.n_inliers = (int)L[0];
     if (L[0] > 0) {
         o.rms_px = canon(sqrt((double)L[1] / (double)L[0]) / 256.0);
@@ -649,7 +638,405 @@ __global__ __launch_bounds__(64) void k_plane_finish(const sdr_segment* __restri
     } else {
         o.flags = SDR_PLANE_NONFINITE;
     }
+}
+
+// The records, one lane a region, from the accumulators the sweeps have left.
+__global__ __launch_bounds__(64) void k_plane_finish(const sdr_segment* __restrict__ regs, int K, int W,
+                                                     int H, int F, Q16 Q, sdr_plane_params P,
+                                                     const long long* __restrict__ acc,
+                                                     sdr_plane* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= K) return;
+    const sdr_segment sg = regs[k];
+    const double qn = __builtin_nan("");
+    sdr_plane o;
+    for (int i = 0; i < 3; i++) o.coef[i] = o.normal[i] = o.centroid[i] = qn;
+    o.offset = o.rms_px = qn;
+    o.max_abs_px = ruler_nan();
+    o.x0 = min(sg.x0, sg.x1);
+    o.y0 = min(sg.y0, sg.y1);
+    o.frame = sg.frame;
+    o.area = o.n_valid = o.n_inliers = o.fits = 0;
+    o.flags = SDR_PLANE_OUT_OF_RANGE;
+    o.reserved = 0;
+    if (!segment_in_range(sg, W, H, F)) {
+        out[k] = o;
+        return;
+    }
+    const PlaneRect R = plane_rect(sg);
+    const long long* A = acc + (size_t)k * (size_t)(P.iterations + 2) * kPlaneSlots;
+    o.area = R.rw * R.rh;
+    o.n_valid = (int)A[0];
+    PlaneFit fit = {0.0, 0.0, 0.0, false};
+    const long long* M = A;
+    for (int s = 0; s <= P.iterations; s++) {
+        M = A + (size_t)s * kPlaneSlots;
+        fit = plane_solve(M, P.min_inliers);
+        if (!fit.ok) break;
+        o.fits++;
+    }
+    if (!fit.ok) {
+        o.flags = SDR_PLANE_DEGENERATE;
+        out[k] = o;
+        return;
+    }
+    plane_record(o, R, fit, M, A + (size_t)(P.iterations + 1) * kPlaneSlots, Q);
     out[k] = o;
+}
+
+// ---- the plane search (the definition: sdr.h, "the dominant planes of a region") ----
+static_assert(sizeof(sdr_plane_search_params) == 64, "sdr_plane_search_params is 64 bytes");
+static_assert(sizeof(sdr_plane_search_round) == 16, "sdr_plane_search_round is 16 bytes");
+static_assert(sizeof(SearchState) == 40, "SearchState is 40 bytes");
+
+// A hypothesis: the plane A*u + B*v + C*q = D through its three points; C == 0: void.
+struct SearchHyp {
+    int A, B, C, pad;
+    long long D;
+    long long pad2;
+};
+static_assert(sizeof(SearchHyp) == 32, "SearchHyp is 32 bytes");
+
+constexpr int kSearchTries = 16;
+constexpr int kSearchChunk = 64;  // hypotheses a workgroup of the score kernel (grid y)
+
+__device__ __forceinline__ uint32_t search_mix(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+// the record of a round that did not run, or of a region out of range (flags)
+__device__ __forceinline__ void search_empty_record(sdr_plane* o, const sdr_segment& sg, int area, uint32_t flags) {
+    const double qn = __builtin_nan("");
+    for (int i = 0; i < 3; i++) o->coef[i] = o->normal[i] = o->centroid[i] = qn;
+    o->offset = o->rms_px = qn;
+    o->max_abs_px = ruler_nan();
+    o->x0 = min(sg.x0, sg.x1);
+    o->y0 = min(sg.y0, sg.y1);
+    o->frame = sg.frame;
+    o->area = area;
+    o->n_valid = o->n_inliers = o->fits = 0;
+    o->flags = flags;
+    o->reserved = 0;
+}
+
+__device__ __forceinline__ void search_round(sdr_plane_search_round* rounds, int r, int h, int score, int voids,
+                                             uint32_t stop) {
+    if (!rounds) return;
+    rounds[r].hypothesis = h;
+    rounds[r].score = score;
+    rounds[r].voids = voids;
+    rounds[r].stop = stop;
+}
+
+// One thread stops the search in round r: the count, the records r.., the rounds r..
+__device__ __forceinline__ void search_stop(SearchState* st, const sdr_segment& sg, int area, int r, int max_planes,
+                                            int h, int score, int voids, uint32_t code, uint32_t rec_flags,
+                                            sdr_plane* planes, int32_t* count, sdr_plane_search_round* rounds) {
+    st->stopped = 1;
+    *count = r;
+    for (int i = r; i < max_planes; i++) {
+        search_empty_record(planes + i, sg, area, rec_flags);
+        if (i == r && code != SDR_SEARCH_NOT_RUN)
+            search_round(rounds, i, h, score, voids, code);
+        else
+            search_round(rounds, i, -1, 0, 0, SDR_SEARCH_NOT_RUN);
+    }
+}
+
+// Before round 0: a region out of range stops the search with its records.
+__global__ __launch_bounds__(64) void k_search_init(const sdr_segment* __restrict__ reg, int W, int H, int F,
+                                                    int max_planes, SearchState* __restrict__ st,
+                                                    sdr_plane* __restrict__ planes, int32_t* __restrict__ count,
+                                                    sdr_plane_search_round* __restrict__ rounds) {
+    if (threadIdx.x != 0) return;
+    const sdr_segment sg = reg[0];
+    *count = 0;
+    if (!segment_in_range(sg, W, H, F))
+        search_stop(st, sg, 0, 0, max_planes, -1, 0, 0, SDR_SEARCH_NOT_RUN, SDR_PLANE_OUT_OF_RANGE, planes, count,
+                    rounds);
+}
+
+// The draws of round r, a thread a hypothesis.
+template <typename T>
+__global__ __launch_bounds__(64) void k_search_draw(const T* __restrict__ disp, size_t stride, size_t fstride, int W,
+                                                    int H, int F, const float* __restrict__ conf,
+                                                    sdr_plane_params P, const sdr_segment* __restrict__ reg,
+                                                    const uint8_t* __restrict__ labels, int r, int M, uint32_t seed,
+                                                    const SearchState* __restrict__ st,
+                                                    SearchHyp* __restrict__ hyp) {
+    if (st->stopped) return;
+    const int h = blockIdx.x * 64 + threadIdx.x;
+    if (h >= M) return;
+    const sdr_segment sg = reg[0];
+    const PlaneRect R = plane_rect(sg);  // in range: k_search_init
+    const unsigned area = (unsigned)R.rw * (unsigned)R.rh;
+    const T* fd = disp + (size_t)sg.frame * fstride + (size_t)R.ys * stride + (size_t)R.xs;
+    const float* fc = conf ? conf + ((size_t)sg.frame * H + (size_t)R.ys) * W + (size_t)R.xs : nullptr;
+    const uint8_t* fl = labels + (size_t)R.ys * W + (size_t)R.xs;
+    const uint32_t key = search_mix(search_mix(seed ^ (0x9E3779B9u * (uint32_t)(r + 1))) ^ (uint32_t)h);
+    int pu[3], pv[3], pq[3];
+    bool found = true;
+    for (int j = 0; j < 3; j++) {
+        bool got = false;
+        for (int t = 0; t < kSearchTries && !got; t++) {
+            const uint32_t x = search_mix(key ^ (uint32_t)(16 * j + t));
+            const unsigned p = (unsigned)(((unsigned long long)x * area) >> 32);  // < area
+            const unsigned v = p / (unsigned)R.rw, u = p - v * (unsigned)R.rw;
+            int q;
+            bool ok = plane_q(fd + (size_t)v * stride + u, P.min_disp, &q);
+            if (fc) ok = ok && fc[(size_t)v * W + u] >= P.conf_min;
+            ok = ok && fl[(size_t)v * W + u] == kFreeLabel;
+            if (ok) {
+                pu[j] = (int)u;
+                pv[j] = (int)v;
+                pq[j] = q;
+                got = true;
+            }
+        }
+        found = found && got;
+        if (!got) pu[j] = pv[j] = pq[j] = 0;
+    }
+    SearchHyp o = {0, 0, 0, 0, 0, 0};
+    if (found) {
+        const long long du1 = pu[1] - pu[0], dv1 = pv[1] - pv[0], dq1 = pq[1] - pq[0];
+        const long long du2 = pu[2] - pu[0], dv2 = pv[2] - pv[0], dq2 = pq[2] - pq[0];
+        const long long A = dv1 * dq2 - dq1 * dv2, B = dq1 * du2 - du1 * dq2, C = du1 * dv2 - dv1 * du2;
+        if (C != 0) {  // |A|, |B| < 2^31, |C| < 2^25 (sdr.h)
+            o.A = (int)A;
+            o.B = (int)B;
+            o.C = (int)C;
+            o.D = A * pu[0] + B * pv[0] + C * pq[0];
+        }
+    }
+    hyp[h] = o;
+}
+
+// The scores of round r: grid (slices of a W x H frame, chunks of kSearchChunk hypotheses).  A
+// workgroup keeps its slice's pixels in registers and walks its chunk's hypotheses (their index is
+// wave-uniform: scalar loads).  A wave counts a hypothesis' pixels by
+// ballots, the waves' counts meet in LDS, and one integer atomic a (workgroup, hypothesis with a
+// count) goes to the score array: neither the slices' order nor the grid shows in the result.  It
+// also counts the round's free pixels (the record's n_valid) into acc[0].
+template <typename T>
+__global__ __launch_bounds__(kPlaneThreads) void k_search_score(const T* __restrict__ disp, size_t stride,
+                                                                size_t fstride, int W, int H, int F,
+                                                                const float* __restrict__ conf,
+                                                                sdr_plane_params P,
+                                                                const sdr_segment* __restrict__ reg,
+                                                                const uint8_t* __restrict__ labels, int M,
+                                                                const SearchState* __restrict__ st,
+                                                                const SearchHyp* __restrict__ hyp,
+                                                                unsigned* __restrict__ scores,
+                                                                long long* __restrict__ acc) {
+    __shared__ unsigned cnt[kPlaneWaves][kSearchChunk];
+    if (st->stopped) return;  // block-uniform
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const sdr_segment sg = reg[0];
+    const PlaneRect R = plane_rect(sg);
+    const unsigned area = (unsigned)R.rw * (unsigned)R.rh;
+    const unsigned base = blockIdx.x * (unsigned)kPlaneSlice;
+    if (base >= area) return;
+    const T* fd = disp + (size_t)sg.frame * fstride + (size_t)R.ys * stride + (size_t)R.xs;
+    const float* fc = conf ? conf + ((size_t)sg.frame * H + (size_t)R.ys) * W + (size_t)R.xs : nullptr;
+    const uint8_t* fl = labels + (size_t)R.ys * W + (size_t)R.xs;
+    const long long Tq = (long long)floor((double)P.inlier_px * 16.0);
+
+    int pu[kPlanePix], pv[kPlanePix], pq[kPlanePix];
+    bool pf[kPlanePix];
+    int nfree = 0;
+#pragma unroll
+    for (int j = 0; j < kPlanePix; j++) {
+        const unsigned p = base + (unsigned)(j * kPlaneThreads + tid);
+        pu[j] = pv[j] = pq[j] = 0;
+        pf[j] = false;
+        if (p < area) {
+            const unsigned v = p / (unsigned)R.rw, u = p - v * (unsigned)R.rw;
+            int q;
+            bool ok = plane_q(fd + (size_t)v * stride + u, P.min_disp, &q);
+            if (fc) ok = ok && fc[(size_t)v * W + u] >= P.conf_min;
+            ok = ok && fl[(size_t)v * W + u] == kFreeLabel;
+            pu[j] = (int)u;
+            pv[j] = (int)v;
+            pq[j] = ok ? q : 0;
+            pf[j] = ok;
+        }
+        nfree += __popcll(__ballot(pf[j]));  // the wave's count, in every lane
+    }
+    const int c0 = (int)blockIdx.y * kSearchChunk;  // < M: the grid
+    if (c0 == 0 && lane == 0 && nfree) atomicAdd((unsigned long long*)acc, (unsigned long long)nfree);
+    {
+        const int nh = min(M - c0, kSearchChunk);
+        for (int i = 0; i < nh; i++) {  // at most kSearchChunk
+            const SearchHyp hp = hyp[c0 + i];  // wave-uniform
+            unsigned c = 0;
+            if (hp.C != 0) {
+                const long long thr = Tq * (long long)abs(hp.C);
+#pragma unroll
+                for (int j = 0; j < kPlanePix; j++) {
+                    const long long e = ((long long)hp.A * pu[j] + (long long)hp.B * pv[j] +
+                                         (long long)hp.C * pq[j]) - hp.D;
+                    const bool in = pf[j] && (e < 0 ? -e : e) <= thr;
+                    c += (unsigned)__popcll(__ballot(in));
+                }
+            }
+            if (lane == 0) cnt[wave][i] = c;
+        }
+        __syncthreads();
+        if (tid < nh) {
+            unsigned s = 0;
+#pragma unroll
+            for (int w = 0; w < kPlaneWaves; w++) s += cnt[w][tid];
+            if (s) atomicAdd(scores + c0 + tid, s);
+        }
+    }
+}
+
+// The pick of round r by one workgroup: the highest score among the hypotheses that are not void,
+// ties to the lowest index (the maximum of (score << 32) | ~h), the stop decision, the seed plane.
+__global__ __launch_bounds__(kPlaneThreads) void k_search_pick(const sdr_segment* __restrict__ reg, int r,
+                                                               int max_planes, int M, int min_inliers,
+                                                               const SearchHyp* __restrict__ hyp,
+                                                               const unsigned* __restrict__ scores,
+                                                               SearchState* __restrict__ st,
+                                                               sdr_plane* __restrict__ planes,
+                                                               int32_t* __restrict__ count,
+                                                               sdr_plane_search_round* __restrict__ rounds) {
+#pragma clang fp contract(off)
+    __shared__ unsigned long long best[kPlaneWaves];
+    __shared__ int nvoid[kPlaneWaves];
+    if (st->stopped) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned long long key = 0;
+    int voids = 0;
+    for (int h = tid; h < M; h += kPlaneThreads) {  // at most 16 passes
+        if (hyp[h].C == 0) {
+            voids++;
+        } else {
+            const unsigned long long k = ((unsigned long long)scores[h] << 32) | (unsigned long long)(0xffffffffu - (unsigned)h);
+            key = max(key, k);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        key = max(key, (unsigned long long)__shfl_xor((long long)key, o, 64));
+        voids += __shfl_xor(voids, o, 64);
+    }
+    if (lane == 0) {
+        best[wave] = key;
+        nvoid[wave] = voids;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    key = 0;
+    voids = 0;
+    for (int w = 0; w < kPlaneWaves; w++) {
+        key = max(key, best[w]);
+        voids += nvoid[w];
+    }
+    const sdr_segment sg = reg[0];
+    const PlaneRect R = plane_rect(sg);
+    const int area = R.rw * R.rh;
+    if (voids == M) {
+        search_stop(st, sg, area, r, max_planes, -1, 0, voids, SDR_SEARCH_NO_HYPOTHESIS, SDR_PLANE_DEGENERATE, planes,
+                    count, rounds);
+        return;
+    }
+    const int h = (int)(0xffffffffu - (unsigned)(key & 0xffffffffull));
+    const int score = (int)(key >> 32);
+    if (score < min_inliers) {
+        search_stop(st, sg, area, r, max_planes, h, score, voids, SDR_SEARCH_LOW_SCORE, SDR_PLANE_DEGENERATE, planes,
+                    count, rounds);
+        return;
+    }
+    const SearchHyp hp = hyp[h];
+    st->winner = h;
+    st->score = score;
+    st->voids = voids;
+    st->a = -(double)hp.A / (double)hp.C;
+    st->b = -(double)hp.B / (double)hp.C;
+    st->c = (double)hp.D / (double)hp.C;
+}
+
+// The record of round r from its accumulators, or the stop the refits or the statistics call for.
+__global__ __launch_bounds__(64) void k_search_finish(const sdr_segment* __restrict__ reg, int r, int max_planes,
+                                                      Q16 Q, sdr_plane_params P, const long long* __restrict__ A,
+                                                      SearchState* __restrict__ st, sdr_plane* __restrict__ planes,
+                                                      int32_t* __restrict__ count,
+                                                      sdr_plane_search_round* __restrict__ rounds) {
+#pragma clang fp contract(off)
+    if (threadIdx.x != 0 || st->stopped) return;
+    const sdr_segment sg = reg[0];
+    const PlaneRect R = plane_rect(sg);
+    const int area = R.rw * R.rh;
+    const int h = st->winner, score = st->score, voids = st->voids;
+    PlaneFit fit = {0.0, 0.0, 0.0, false};
+    const long long* M = A;
+    for (int s = 1; s <= P.iterations; s++) {
+        M = A + (size_t)s * kPlaneSlots;
+        fit = plane_solve(M, P.min_inliers);
+        if (!fit.ok) break;
+    }
+    const long long* L = A + (size_t)(P.iterations + 1) * kPlaneSlots;
+    if (!fit.ok || L[0] < (long long)P.min_inliers) {
+        search_stop(st, sg, area, r, max_planes, h, score, voids,
+                    fit.ok ? SDR_SEARCH_FEW_INLIERS : SDR_SEARCH_REFIT_DEGENERATE, SDR_PLANE_DEGENERATE, planes,
+                    count, rounds);
+        return;
+    }
+    sdr_plane o;
+    search_empty_record(&o, sg, area, 0);
+    o.n_valid = (int)A[0];
+    o.fits = P.iterations + 1;
+    plane_record(o, R, fit, M, L, Q);
+    planes[r] = o;
+    *count = r + 1;
+    search_round(rounds, r, h, score, voids, SDR_SEARCH_RAN);
+}
+
+// The claim of round r: the statistics sweep's inliers (the same residual against the same plane)
+// get the round's label.  A pass of its own behind k_search_finish: a round that stops claims
+// nothing, and no sweep can see a partly claimed map.
+template <typename T>
+__global__ __launch_bounds__(kPlaneThreads) void k_search_claim(const T* __restrict__ disp, size_t stride,
+                                                                size_t fstride, int W, int H, int F,
+                                                                const float* __restrict__ conf,
+                                                                sdr_plane_params P,
+                                                                const sdr_segment* __restrict__ reg,
+                                                                uint8_t* __restrict__ labels, int r,
+                                                                const SearchState* __restrict__ st,
+                                                                const long long* __restrict__ A) {
+#pragma clang fp contract(off)
+    if (st->stopped) return;  // block-uniform
+    const int tid = threadIdx.x;
+    const sdr_segment sg = reg[0];
+    const PlaneRect R = plane_rect(sg);
+    const unsigned area = (unsigned)R.rw * (unsigned)R.rh;
+    const unsigned base = blockIdx.x * (unsigned)kPlaneSlice;
+    if (base >= area) return;
+    const PlaneFit fit = plane_solve(A + (size_t)P.iterations * kPlaneSlots, P.min_inliers);  // ok: not stopped
+    const double band = (double)P.inlier_px * 16.0;
+    const T* fd = disp + (size_t)sg.frame * fstride + (size_t)R.ys * stride + (size_t)R.xs;
+    const float* fc = conf ? conf + ((size_t)sg.frame * H + (size_t)R.ys) * W + (size_t)R.xs : nullptr;
+    uint8_t* fl = labels + (size_t)R.ys * W + (size_t)R.xs;
+#pragma unroll
+    for (int j = 0; j < kPlanePix; j++) {
+        const unsigned p = base + (unsigned)(j * kPlaneThreads + tid);
+        if (p >= area) continue;
+        const unsigned v = p / (unsigned)R.rw, u = p - v * (unsigned)R.rw;
+        int q;
+        bool ok = plane_q(fd + (size_t)v * stride + u, P.min_disp, &q);
+        if (fc) ok = ok && fc[(size_t)v * W + u] >= P.conf_min;
+        ok = ok && fl[(size_t)v * W + u] == kFreeLabel;
+        const double res = (double)q - plane_at(fit, (double)u, (double)v);
+        if (ok && fabs(res) <= band) fl[(size_t)v * W + u] = (uint8_t)r;
+    }
 }
 
 // Point queries, one wave a query: the ruler's sample and its distance to a fitted plane.
@@ -755,6 +1142,15 @@ int check_plane_params(const sdr_plane_params* p) {
     if (p->iterations < 0 || p->iterations > 8) return rfail(SDR_ERR_ARG, "iterations must be in 0..8");
     if (p->min_inliers < 3) return rfail(SDR_ERR_ARG, "min_inliers must be >= 3");
     if (!(p->inlier_px > 0.0f && p->inlier_px <= 64.0f)) return rfail(SDR_ERR_ARG, "inlier_px must be in (0, 64]");
+    return SDR_OK;
+}
+
+int check_search_params(const sdr_plane_search_params* p) {
+    const int rc = check_plane_params(&p->fit);
+    if (rc) return rc;
+    if (p->fit.iterations < 1) return rfail(SDR_ERR_ARG, "the plane search takes iterations in 1..8");
+    if (p->max_planes < 1 || p->max_planes > 8) return rfail(SDR_ERR_ARG, "max_planes must be in 1..8");
+    if (p->hypotheses < 1 || p->hypotheses > 4096) return rfail(SDR_ERR_ARG, "hypotheses must be in 1..4096");
     return SDR_OK;
 }
 
@@ -960,18 +1356,129 @@ int sdr_fit_planes_device(const void* d_disp, int disp_type, size_t stride, size
         for (int k0 = 0; k0 < K; k0 += 65535) {  // the grid's y extent
             const dim3 grid(slices, (unsigned)std::min(K - k0, 65535)), block(sdr::kPlaneThreads);
             if (disp_type == SDR_DISP_F32)
-                hipLaunchKernelGGL(sdr::k_plane_sweep<float>, grid, block, 0, st, (const float*)d_disp, stride,
-                                   frame_stride, W, H, F, d_conf, *params, d_regions + k0, acc + k0 * per, s);
+                hipLaunchKernelGGL((sdr::k_plane_sweep<float, false>), grid, block, 0, st, (const float*)d_disp, stride,
+                                   frame_stride, W, H, F, d_conf, *params, d_regions + k0, acc + k0 * per, s,
+                                   (const uint8_t*)nullptr, (const sdr::SearchState*)nullptr);
             else
-                hipLaunchKernelGGL(sdr::k_plane_sweep<int16_t>, grid, block, 0, st, (const int16_t*)d_disp,
+                hipLaunchKernelGGL((sdr::k_plane_sweep<int16_t, false>), grid, block, 0, st, (const int16_t*)d_disp,
                                    stride, frame_stride, W, H, F, d_conf, *params, d_regions + k0,
-                                   acc + k0 * per, s);
+                                   acc + k0 * per, s, (const uint8_t*)nullptr, (const sdr::SearchState*)nullptr);
         }
     hipLaunchKernelGGL(sdr::k_plane_finish, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, st, d_regions, K, W, H,
                        F, q, *params, (const long long*)acc, d_planes);
     const hipError_t le = hipGetLastError();
     RULER_HIP(sdr::scratch_free(acc, st));
     RULER_HIP(le);
+    return SDR_OK;
+}
+
+void sdr_plane_search_params_default(sdr_plane_search_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    sdr_plane_params_default(&p->fit);
+    p->fit.min_inliers = 64;
+    p->max_planes = 4;
+    p->hypotheses = 256;
+    p->seed = 0;
+}
+
+int sdr_find_planes_device(const void* d_disp, int disp_type, size_t stride, size_t frame_stride, int W, int H,
+                           int F, const float* d_conf, const double Q[16], const sdr_plane_search_params* params,
+                           const sdr_segment* d_region, sdr_plane* d_planes, int32_t* d_count,
+                           sdr_plane_search_round* d_rounds, uint8_t* d_labels, void* stream) {
+    int rc = check_plane_maps(d_disp, disp_type, stride, frame_stride, W, H, F, Q, params, d_region, 1, d_planes);
+    if (rc) return rc;
+    if (!d_count) return rfail(SDR_ERR_ARG, "null argument");
+    if ((rc = check_search_params(params))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    sdr::Q16 q;
+    for (int i = 0; i < 16; i++) q.q[i] = Q[i];
+    const sdr_plane_params P = params->fit;
+    const int NP = params->max_planes, M = params->hypotheses;
+    const size_t px = (size_t)W * H;
+    // scratch: {state, the rounds' accumulators, the rounds' scores} zeroed, the hypotheses of one
+    // round (every round writes all M before it reads them), the claim map when the caller has none
+    const size_t per = (size_t)(P.iterations + 2) * sdr::kPlaneSlots;
+    const size_t o_acc = 64, o_sc = o_acc + (size_t)NP * per * sizeof(long long);
+    const size_t o_hyp = (o_sc + (size_t)NP * M * sizeof(unsigned) + 63) & ~(size_t)63;
+    const size_t o_lab = o_hyp + (size_t)M * sizeof(sdr::SearchHyp);
+    char* sc = nullptr;
+    RULER_HIP(sdr::scratch_alloc((void**)&sc, o_lab + (d_labels ? 0 : px), st));
+    sdr::SearchState* state = (sdr::SearchState*)sc;
+    long long* acc = (long long*)(sc + o_acc);
+    unsigned* scores = (unsigned*)(sc + o_sc);
+    sdr::SearchHyp* hyp = (sdr::SearchHyp*)(sc + o_hyp);
+    uint8_t* labels = d_labels ? d_labels : (uint8_t*)(sc + o_lab);
+    hipError_t e = hipMemsetAsync(sc, 0, o_hyp, st);
+    if (e == hipSuccess) e = hipMemsetAsync(labels, 0xff, px, st);
+    if (e != hipSuccess) {
+        (void)sdr::scratch_free(sc, st);
+        RULER_HIP(e);
+    }
+    const unsigned slices = (unsigned)((px + sdr::kPlaneSlice - 1) / sdr::kPlaneSlice);
+    const dim3 sgrid(slices), sblock(sdr::kPlaneThreads), dgrid((unsigned)((M + 63) / 64)), one(1), wave(64);
+    const dim3 cgrid(slices, (unsigned)((M + sdr::kSearchChunk - 1) / sdr::kSearchChunk));
+    hipLaunchKernelGGL(sdr::k_search_init, one, wave, 0, st, d_region, W, H, F, NP, state, d_planes, d_count,
+                       d_rounds);
+    auto round = [&](auto* disp, int r) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(disp)>>;
+        long long* A = acc + (size_t)r * per;
+        unsigned* S = scores + (size_t)r * M;
+        hipLaunchKernelGGL(sdr::k_search_draw<T>, dgrid, wave, 0, st, disp, stride, frame_stride, W, H, F, d_conf, P,
+                           d_region, (const uint8_t*)labels, r, M, params->seed, (const sdr::SearchState*)state, hyp);
+        hipLaunchKernelGGL(sdr::k_search_score<T>, cgrid, sblock, 0, st, disp, stride, frame_stride, W, H, F, d_conf,
+                           P, d_region, (const uint8_t*)labels, M, (const sdr::SearchState*)state,
+                           (const sdr::SearchHyp*)hyp, S, A);
+        hipLaunchKernelGGL(sdr::k_search_pick, one, sblock, 0, st, d_region, r, NP, M, P.min_inliers,
+                           (const sdr::SearchHyp*)hyp, (const unsigned*)S, state, d_planes, d_count, d_rounds);
+        for (int s = 1; s <= P.iterations + 1; s++)
+            hipLaunchKernelGGL((sdr::k_plane_sweep<T, true>), sgrid, sblock, 0, st, disp, stride, frame_stride, W, H,
+                               F, d_conf, P, d_region, A, s, (const uint8_t*)labels, (const sdr::SearchState*)state);
+        hipLaunchKernelGGL(sdr::k_search_finish, one, wave, 0, st, d_region, r, NP, q, P, (const long long*)A, state,
+                           d_planes, d_count, d_rounds);
+        hipLaunchKernelGGL(sdr::k_search_claim<T>, sgrid, sblock, 0, st, disp, stride, frame_stride, W, H, F, d_conf,
+                           P, d_region, labels, r, (const sdr::SearchState*)state, (const long long*)A);
+    };
+    for (int r = 0; r < NP; r++) {
+        if (disp_type == SDR_DISP_F32)
+            round((const float*)d_disp, r);
+        else
+            round((const int16_t*)d_disp, r);
+    }
+    const hipError_t le = hipGetLastError();
+    RULER_HIP(sdr::scratch_free(sc, st));
+    RULER_HIP(le);
+    return SDR_OK;
+}
+
+int sdr_find_planes(const void* disp, int disp_type, size_t stride, size_t frame_stride, int W, int H, int F,
+                    const float* conf, const double Q[16], const sdr_plane_search_params* params,
+                    const sdr_segment* region, sdr_plane* planes, int32_t* count, sdr_plane_search_round* rounds,
+                    uint8_t* labels) {
+    int rc = check_plane_maps(disp, disp_type, stride, frame_stride, W, H, F, Q, params, region, 1, planes);
+    if (rc) return rc;
+    if (!count) return rfail(SDR_ERR_ARG, "null argument");
+    if ((rc = check_search_params(params))) return rc;
+    HostState* S = nullptr;
+    if ((rc = host_state(&S))) return rc;
+    const int NP = params->max_planes;
+    const size_t px = (size_t)W * H, rbytes = (size_t)NP * sizeof(sdr_plane_search_round);
+    // out: {count, padding to 16 bytes, the rounds}; prof: the labels
+    if ((rc = upload_maps(S, disp, disp_type, stride, frame_stride, W, H, F, conf)) ||
+        (rc = sdr::ensure(S->segs, sizeof(sdr_segment))) || (rc = sdr::ensure(S->planes, (size_t)NP * sizeof(sdr_plane))) ||
+        (rc = sdr::ensure(S->out, 16 + rbytes)) || (rc = sdr::ensure(S->prof, labels ? px : 0)))
+        return rc;
+    RULER_HIP(hipMemcpyAsync(S->segs.p, region, sizeof(sdr_segment), hipMemcpyHostToDevice, S->st));
+    rc = sdr_find_planes_device(S->map.p, disp_type, (size_t)W, px, W, H, F, conf ? (const float*)S->conf.p : nullptr, Q,
+                                params, (const sdr_segment*)S->segs.p, (sdr_plane*)S->planes.p, (int32_t*)S->out.p,
+                                (sdr_plane_search_round*)((char*)S->out.p + 16), labels ? (uint8_t*)S->prof.p : nullptr,
+                                S->st);
+    if (rc) return rc;
+    RULER_HIP(hipMemcpyAsync(planes, S->planes.p, (size_t)NP * sizeof(sdr_plane), hipMemcpyDeviceToHost, S->st));
+    RULER_HIP(hipMemcpyAsync(count, S->out.p, sizeof(int32_t), hipMemcpyDeviceToHost, S->st));
+    if (rounds) RULER_HIP(hipMemcpyAsync(rounds, (char*)S->out.p + 16, rbytes, hipMemcpyDeviceToHost, S->st));
+    if (labels) RULER_HIP(hipMemcpyAsync(labels, S->prof.p, px, hipMemcpyDeviceToHost, S->st));
+    RULER_HIP(hipStreamSynchronize(S->st));
     return SDR_OK;
 }
 

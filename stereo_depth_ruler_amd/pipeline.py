@@ -131,6 +131,19 @@ class LiveLoop:
         return self.ruler.fit_plane_device(self.disp, regions, conf=self.conf, iterations=iterations,
                                            inlier_px=inlier_px, min_inliers=min_inliers, stream=stream)
 
+    def find_planes(self, region, stream, max_planes: int = 4, hypotheses: int = 256, seed: int = 0,
+                    iterations: int = 3, inlier_px: float = 1.0, min_inliers: int = 64, labels: bool = False,
+                    labels_out=None):
+        """Ruler.find_planes_device on the frames the last enqueue left in `disp`, with their
+        confidence map, enqueued on `stream` like fit_plane(): the (planes, count, rounds, labels)
+        tensors.  region: (frame, x0, y0, x1, y1) / (x0, y0, x1, y1), None: all of frame 0."""
+        if self.ruler is None:
+            raise RuntimeError("LiveLoop was built without ruler=")
+        return self.ruler.find_planes_device(self.disp, region, conf=self.conf, max_planes=max_planes,
+                                             hypotheses=hypotheses, seed=seed, iterations=iterations,
+                                             inlier_px=inlier_px, min_inliers=min_inliers, labels=labels,
+                                             stream=stream, labels_out=labels_out)
+
     def plane_distance(self, planes, points, stream):
         """Ruler.plane_distance_device on the same frames: `planes` the tensor fit_plane returned
         (or host records), the (K, 32) distances tensor, no synchronise in between."""

@@ -13,6 +13,11 @@ engine (csrc/sdr_ruler.hip; the definition is in include/sdr/sdr.h).
   integer moments, a coarse-to-fine inlier refit) and ``Ruler.plane_distance(disparity, planes,
   points)`` gives the signed distance of sampled points to those planes, positive towards the
   camera: heights above a table, steps, distances from a wall.
+* ``Ruler.find_planes(disparity, region=None)`` finds a region's dominant planes without a prior (a
+  box on a table in front of a wall): rounds of seeded three-point hypotheses scored in exact
+  integer arithmetic on the pixels no earlier plane has claimed, the winner refitted as
+  ``fit_plane`` does; the records feed ``plane_distance``, a label map says which pixel lies on
+  which plane.
 
 A segment is ``(frame, x0, y0, x1, y1)`` (or ``(x0, y0, x1, y1)`` on frame 0), in pixels of the
 map.  The walk rounds ties towards +x / +y: from P1 to P0 it visits the same pixels in reverse, so
@@ -28,7 +33,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import DISP_F32, DISP_S16, PlaneParams, RulerParams, SDRError, check, lib
+from ._lib import DISP_F32, DISP_S16, PlaneParams, PlaneSearchParams, RulerParams, SDRError, check, lib
 from .sgbm import _Q, _is_cuda, torch
 
 MEASUREMENT_DTYPE = np.dtype([
@@ -54,6 +59,12 @@ assert PLANE_DISTANCE_DTYPE.itemsize == 32
 # sdr_plane.flags (SDR_PLANE_*) and sdr_plane_distance.flags (SDR_PDIST_*)
 PLANE_OK, PLANE_DEGENERATE, PLANE_NONFINITE, PLANE_OUT_OF_RANGE = 1, 2, 4, 8
 PDIST_VALID, PDIST_OUT_OF_RANGE, PDIST_NO_PLANE = 1, 2, 4
+
+# sdr_plane_search_round and its stop codes (SDR_SEARCH_*)
+PLANE_SEARCH_ROUND_DTYPE = np.dtype([("hypothesis", "<i4"), ("score", "<i4"), ("voids", "<i4"), ("stop", "<u4")])
+assert PLANE_SEARCH_ROUND_DTYPE.itemsize == 16
+(SEARCH_RAN, SEARCH_NO_HYPOTHESIS, SEARCH_LOW_SCORE, SEARCH_REFIT_DEGENERATE, SEARCH_FEW_INLIERS,
+ SEARCH_NOT_RUN) = range(6)
 
 
 def as_queries(points) -> np.ndarray:
@@ -340,6 +351,107 @@ class Ruler:
                 regs.data_ptr() if K else None, K, rec.data_ptr() if K else None,
                 ctypes.c_void_p(s.cuda_stream)))
         return rec
+
+    # ---- the dominant planes of a region (sdr.h, "the dominant planes of a region") ----
+    def _search_params(self, max_planes, hypotheses, seed, iterations, inlier_px, min_inliers) -> PlaneSearchParams:
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 32:
+            raise SDRError(-1, "seed must be in 0..2^32-1")
+        return PlaneSearchParams(self._plane_params(iterations, inlier_px, min_inliers), int(max_planes),
+                                 int(hypotheses), seed)
+
+    @staticmethod
+    def _search_region(region, W, H) -> np.ndarray:
+        if region is None:
+            return np.array([[0, 0, 0, W - 1, H - 1]], np.int32)
+        reg = as_segments(region)
+        if reg.shape[0] != 1:
+            raise SDRError(-1, "find_planes takes one region")
+        return reg
+
+    def find_planes(self, disparity, region=None, conf=None, max_planes: int = 4, hypotheses: int = 256,
+                    seed: int = 0, iterations: int = 3, inlier_px: float = 1.0, min_inliers: int = 64,
+                    labels: bool = False):
+        """The dominant planes of one rectangle, the largest first, without a prior: a seeded search
+        (three-point hypotheses scored on the pixels no earlier plane has claimed, the winner
+        refitted as fit_plane does).  region: (frame, x0, y0, x1, y1) / (x0, y0, x1, y1), None: the
+        whole map of frame 0.  Returns the planes found as a PLANE_DTYPE array (at most
+        max_planes), and with labels=True also the (H, W) uint8 map of the region's frame: the
+        index of the plane a pixel lies on, 255 on none."""
+        if _is_cuda(disparity):
+            rec, count, _, lab = self.find_planes_device(disparity, region, conf, max_planes, hypotheses, seed,
+                                                         iterations, inlier_px, min_inliers, labels=labels)
+            n = int(count.cpu()[0])
+            out = rec.cpu().numpy().reshape(-1).view(PLANE_DTYPE)[:n].copy()
+            return (out, lab.cpu().numpy()) if labels else out
+        out, count, _, lab = self.find_planes_full(disparity, region, conf, max_planes, hypotheses, seed, iterations,
+                                                   inlier_px, min_inliers, labels=labels)
+        return (out[:count].copy(), lab) if labels else out[:count].copy()
+
+    def find_planes_full(self, disparity, region=None, conf=None, max_planes: int = 4, hypotheses: int = 256,
+                         seed: int = 0, iterations: int = 3, inlier_px: float = 1.0, min_inliers: int = 64,
+                         labels: bool = False):
+        """find_planes on host maps with everything the search writes: (all max_planes records, count,
+        the rounds as a PLANE_SEARCH_ROUND_DTYPE array, the labels or None)."""
+        d, c, rs, fs = self._host_maps(disparity, conf)
+        F, H, W = d.shape
+        reg = self._search_region(region, W, H)
+        p = self._search_params(max_planes, hypotheses, seed, iterations, inlier_px, min_inliers)
+        n = max(int(max_planes), 0)
+        rec = np.zeros(n, PLANE_DTYPE)
+        rounds = np.zeros(n, PLANE_SEARCH_ROUND_DTYPE)
+        count = np.zeros(1, np.int32)
+        lab = np.full((H, W), 255, np.uint8) if labels else None
+        with _on_device(self.device):
+            rc = lib().sdr_find_planes(
+                d.ctypes.data, DISP_F32 if d.dtype == np.float32 else DISP_S16, rs, fs, W, H, F,
+                c.ctypes.data if c is not None else None, _Q(self.Q), ctypes.byref(p), reg.ctypes.data,
+                rec.ctypes.data if n else None, count.ctypes.data, rounds.ctypes.data if n else None,
+                lab.ctypes.data if lab is not None else None)
+        check(rc)
+        return rec, int(count[0]), rounds, lab
+
+    def find_planes_device(self, disparity, region=None, conf=None, max_planes: int = 4, hypotheses: int = 256,
+                           seed: int = 0, iterations: int = 3, inlier_px: float = 1.0, min_inliers: int = 64,
+                           labels: bool = False, stream=None, labels_out=None):
+        """Enqueues the search on `stream` (default: the current stream) without synchronising and
+        returns (planes uint8 (max_planes, 128), count int32 (1,), rounds int32 (max_planes, 4),
+        labels uint8 (H, W) or None).  The planes tensor feeds plane_distance_device unchanged
+        (records past count are not PLANE_OK).  region: host, or a CUDA int32 (1, 5); labels_out: a
+        contiguous CUDA uint8 (H, W) tensor to write the labels into."""
+        if not _is_cuda(disparity):
+            raise SDRError(-5, "find_planes_device expects a CUDA float32 or int16 tensor")
+        dev = disparity.device
+        s = stream if stream is not None else torch.cuda.current_stream(dev.index)
+        with torch.cuda.stream(s):
+            d, conf = self._device_maps(disparity, conf)
+            F, H, W = d.shape
+            p = self._search_params(max_planes, hypotheses, seed, iterations, inlier_px, min_inliers)
+            if _is_cuda(region):
+                if region.dtype != torch.int32 or region.dim() != 2 or tuple(region.shape) != (1, 5):
+                    raise SDRError(-5, "a device region must be an int32 tensor (1, 5)")
+                reg = region.contiguous()
+            else:
+                reg = self._upload_segments(self._search_region(region, W, H), dev, s)
+            n = max(int(max_planes), 0)
+            rec = torch.empty((n, 128), dtype=torch.uint8, device=dev)
+            count = torch.empty((1,), dtype=torch.int32, device=dev)
+            rounds = torch.empty((n, 4), dtype=torch.int32, device=dev)
+            lab = None
+            if labels_out is not None:
+                if (not _is_cuda(labels_out) or labels_out.dtype != torch.uint8 or not labels_out.is_contiguous()
+                        or tuple(labels_out.shape) != (H, W)):
+                    raise SDRError(-5, "labels_out must be a contiguous CUDA uint8 tensor (H, W)")
+                lab = labels_out
+            elif labels:
+                lab = torch.empty((H, W), dtype=torch.uint8, device=dev)
+            check(lib().sdr_find_planes_device(
+                d.data_ptr(), DISP_F32 if d.dtype == torch.float32 else DISP_S16, d.stride(1),
+                d.stride(1) * H if F == 1 else d.stride(0), W, H, F,
+                conf.data_ptr() if conf is not None else None, _Q(self.Q), ctypes.byref(p), reg.data_ptr(),
+                rec.data_ptr() if n else None, count.data_ptr(), rounds.data_ptr() if n else None,
+                lab.data_ptr() if lab is not None else None, ctypes.c_void_p(s.cuda_stream)))
+        return rec, count, rounds, lab
 
     def plane_distance(self, disparity, planes, points, conf=None):
         """Signed distances of sampled points to fitted planes: a PLANE_DISTANCE_DTYPE array of K.
