@@ -273,7 +273,7 @@ int sdr_fgs_filter_device(const uint8_t* d_guide, size_t guide_stride, int width
                           double lambda, double sigma_color, double lambda_attenuation,
                           int num_iter, float* d_img, int nimg, int solver, void* stream);
 /* Self-test of the reciprocal the SDR_FGS_THOMAS coefficient jobs use (v_rcp_f32 + one Newton
- * step, sdr_wls.hip fgs_rcp) against the IEEE quotient 1.0f / d, on the current device, for all
+ * step, sdr_fgs_seq.hip fgs_rcp) against the IEEE quotient 1.0f / d, on the current device, for all
  * 2^23 mantissas of d in [2^e, 2^(e+1)), 0 <= e <= 126: *mismatches = how many differ (0 expected
  * for e <= 125, where 1/d is normal: the jobs' bit-exactness rests on it; SDR_FGS_THOMAS refuses
  * lambda > 2^100 so that its pivots stay below 2^126). Synchronous. */

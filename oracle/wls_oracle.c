@@ -2,7 +2,8 @@
  * wls_oracle.c -- CPU restatement of ximgproc's DisparityWLSFilter + FastGlobalSmootherFilter.
  * TEST INFRASTRUCTURE ONLY; see wls_oracle.h for what is restated and why parity is unpinned.
  * Built with -ffp-contract=off (oracle/Makefile): every float operation below is rounded on its
- * own, the order the GPU kernels (sdr_wls.hip) reproduce.
+ * own, the order the GPU kernels (sdr_wls.hip, sdr_fgs_seq.hip, sdr_fgs_pcr.hip)
+ * reproduce.
  */
 #include "wls_oracle.h"
 

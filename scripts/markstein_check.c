@@ -1,4 +1,4 @@
-/* Checks the sequential FGS solver's division (stereo_depth_ruler_amd/csrc/sdr_wls.hip div_by):
+/* Checks the sequential FGS solver's division (stereo_depth_ruler_amd/csrc/sdr_fgs_seq.hip):
  *   q0 = x * r,  rem = -fma(q0, den, -x),  q = fma(rem, r, q0)      (r = 1/den, correctly rounded)
  * against the IEEE quotient x / den, for den >= 1 (every FGS pivot is) and |q0| >= 2^-96 (the
  * kernel redoes a chunk with real divisions when some 0 < |q0| < 2^-96).  Random den over

@@ -269,7 +269,7 @@ __device__ __forceinline__ int div_trunc_small(int n, int d) {
 
 // ------------------------------------------------------------------------------------------
 // A.12 reprojectImageTo3D of one pixel (sdr_post.hip's kernels, the class path's fused WLS
-// epilogue in sdr_wls.hip): double math, sequential sums from 0, no contraction, Vec3f then
+// epilogue, sdr_fgs.hpp wls_emit): double math, sequential sums from 0, no contraction, Vec3f then
 // *(1.0/h3) rounded to float; handleMissing: Z = 10000 where |d - min(disp)| <= FLT_EPSILON.
 // ------------------------------------------------------------------------------------------
 struct Q16 {

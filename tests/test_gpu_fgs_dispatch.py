@@ -1,10 +1,10 @@
 """Every dispatch branch of the sequential FGS solver (SDR_FGS_THOMAS, the default), bit for bit
 against the oracle (oracle/wls_oracle.c fgs_line): no tolerance anywhere.
 
-launch_fgs_lr picks k_fgs_lr<L> from the line length (L = 16 only with SDR_FGS_LR_MAXL=16, 8 up
-to 768 samples, 4 up to 1536, 2 up to 3072, k_fgs_th beyond), launch_fgs_lrjob gives each
-coefficient job its own L (16 / 8 / 4) or sends all of them to k_fgs_th when one line is past 1536
-samples, and launch_fgs_th picks k_fgs_th<TWO, LPB> by how many line-frames the chip holds.  Each
+The dispatch plan (sdr_fgs_seq.hip fgs_plan) picks k_fgs_lr<L> from the line length (L = 16 only
+with SDR_FGS_LR_MAXL=16, 8 up to 768 samples, 4 up to 1536, 2 up to 3072, k_fgs_th beyond), gives
+each coefficient job its own L (16 / 8 / 4) or sends all of them to k_fgs_th when one line is past
+1536 samples, and picks k_fgs_th<TWO, LPB> by how many line-frames the chip holds.  Each
 instantiation has its own LDS layout, chunk length, DMA piece sizes and tiny-quotient redo, so
 each is run here as rows and as columns, through fastGlobalSmootherFilter (the pack-kernel entry,
 a stack of 2) and through DisparityWLSFilter.filter (the in_transposed entry), at (lambda, sigma) =

@@ -282,7 +282,7 @@ def test_default_solver_hypothesis(oracle):
 
 def test_fgs_reciprocal_exact_every_mantissa():
     """The sequential solver's coefficient jobs take 1/den as v_rcp_f32 + one Newton step
-    (sdr_wls.hip fgs_rcp) and its passes divide with that reciprocal (Markstein): bit-exactness rests
+    (sdr_fgs_seq.hip fgs_rcp) and its passes divide with that reciprocal (Markstein): bit-exactness rests
     on it being the IEEE quotient 1.0f / d for every d the jobs meet (1 <= d <= 1 + 2 lambda, lambda
     <= 2^100).  All 2^23 mantissas of d in [2^e, 2^(e+1)) on the device, for EVERY exponent the
     accepted parameters can reach, 0 <= e <= 125 (7 exponents were checked before)."""
