@@ -315,8 +315,9 @@ int sdr_fgs_plan_query(int width, int height, int nframes, int nimg, int num_ite
 /* ---- ingest in front of the path: StereoRectifier + SBS split ----
  * cv::initUndistortRectifyMap(K, dist, R, P, size, CV_16SC2, map1, map2)   stereo_rectifier.cpp:7-11
  * computed on the device (f64, OpenCV's scalar loop): map1 int16 [H][W][2], map2 uint16 [H][W]
- * (5-bit fractions, (v&31)*32 + (u&31)); host outputs.  dist has 0/4/5/8/12 coefficients; P is
- * row-major 3 x p_cols (p_cols 3 or 4, only the first 3 columns are used). */
+ * (5-bit fractions, (v&31)*32 + (u&31)); host outputs.  dist has 0/4/5/8/12/14 coefficients
+ * (14: tauX = tauY = 0 only, the tilted-sensor model is refused with SDR_ERR_ARG); P is row-major
+ * 3 x p_cols (p_cols 3 or 4, only the first 3 columns are used). */
 int sdr_init_undistort_rectify_map(const double K[9], const double* dist, int ndist,
                                    const double R[9], const double* P, int p_cols, int width,
                                    int height, int device, int16_t* map1, uint16_t* map2);
