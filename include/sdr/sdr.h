@@ -378,15 +378,19 @@ int sdr_stereo_class_depth_device(sdr_sgbm* left, sdr_sgbm* right, sdr_wls* wls,
  * Points are pcl::PointXYZRGB as savePCDFileBinary lays them out: 16-byte records
  * {float x, y, z; uint32 rgba}. */
 /* convertCVMatToPCL(xyz, left) (pcd_write.cpp:17-51): xyz float [F][H][W][3], bgr u8 3-channel
- * rows of bgr_stride bytes, frames bgr_frame_stride apart (0 = dense), or NULL -> organised cloud
- * [F][H*W]; non-finite points get NaN x/y/z.  Async on `stream`. */
+ * rows of bgr_stride bytes (0 = 3 * width), frames bgr_frame_stride bytes apart (0 = bgr_stride *
+ * height, with the row length in force), or NULL -> organised cloud [F][H*W]; non-finite points
+ * get NaN x/y/z and no colour.  Async on `stream`.  SDR_ERR_ARG (nothing is enqueued): d_xyz or
+ * d_points NULL, width, height or nframes <= 0, a non-zero bgr_stride < 3 * width with d_bgr given. */
 int sdr_xyz_to_cloud_device(const float* d_xyz, const uint8_t* d_bgr, size_t bgr_stride,
                             size_t bgr_frame_stride, int width, int height, int nframes,
                             void* d_points, void* stream);
 /* pcl::VoxelGrid<PointXYZRGB> with leaf (lx, ly, lz) (pcd_write.cpp:122-130) on n device points
  * -> d_out (capacity n) and *out_count.  PCL's int32-overflow case (leaf too small for the extent,
  * the reference's 5 mm leaf on millimetre clouds) copies the input through and sets *passthrough.
- * Synchronous on `stream` (the count is a host value).  Scratch: ~44 B a point plus the sort's
+ * Synchronous on `stream` (the count is a host value).  n == 0, or no finite point: *out_count = 0.
+ * `passthrough` may be NULL.  SDR_ERR_ARG (nothing written, the count included): d_points, d_out
+ * or out_count NULL, n < 0, a leaf that is not > 0 on any axis (0, negative, NaN).  Scratch: ~44 B a point plus the sort's
  * histograms, from a grow-only device arena a call leases and returns idle (one arena per call in
  * flight at once, kept for the process). */
 int sdr_voxel_grid_device(const void* d_points, int n, float lx, float ly, float lz, void* d_out,
@@ -412,7 +416,9 @@ int sdr_display_reset_stream(sdr_display* h);              /* back to its own st
 /* forget the EMA history and reset the handle's range state to {1000, 2000} */
 int sdr_display_reset(sdr_display* h);
 /* show_disparityMap (stereo_disparity.cpp:42-73) on nframes float disparities (px; `stride` and
- * `frame_stride` in ELEMENTS) -> d_vis u8 [F][H][W], frames in order through the EMA. */
+ * `frame_stride` in ELEMENTS, both used as given: there is no 0 = dense shorthand, and
+ * frame_stride is not read when nframes == 1) -> d_vis u8 [F][H][W] dense, frames in order through
+ * the EMA.  SDR_ERR_ARG: a NULL argument, width, height or nframes <= 0, stride < width. */
 int sdr_show_disparity_map_device(sdr_display* h, const float* d_disp, int width, int height,
                                   size_t stride, size_t frame_stride, int nframes,
                                   int num_disparities, uint8_t* d_vis);
@@ -420,24 +426,33 @@ int sdr_show_disparity_map_device(sdr_display* h, const float* d_disp, int width
  * channels 1: Z itself), dense [F][H][W][channels] -> d_bgr u8 [F][H][W][3].  d_zrange: device
  * {zmin_smooth, zmax_smooth} (the reference's function-static doubles, shared by every caller
  * that passes the same pointer), NULL = the handle's own.  coverage_pct (host [F], nullable):
- * depth_coverage of each frame (stereo_displayer.cpp:105-118, columns >= 80); synchronises. */
+ * depth_coverage of each frame (stereo_displayer.cpp:105-118, columns >= 80); synchronises.
+ * Valid Z for the range: 0 < Z < 10000 (10000 itself is not), a denormal included; a frame with
+ * fewer than two distinct valid Z takes 1000 / 2000.  SDR_ERR_ARG: h, d_xyz or d_bgr NULL, a size
+ * <= 0; SDR_ERR_TYPE: channels other than 1 or 3. */
 int sdr_show_depth_map_device(sdr_display* h, const float* d_xyz, int width, int height,
                               int channels, int nframes, double* d_zrange, const uint8_t* lut_bgr,
                               uint8_t* d_bgr, double* coverage_pct);
 /* StereoDisplayer::depth_coverage of xyz [F][H][W][3]: percent of Z in [0, 12000] among columns
- * >= col0 (80 in the reference), over all H*W pixels (host pct[F]; synchronous). */
+ * >= col0 (80 in the reference), over all H*W pixels (host pct[F]; synchronous); -0.0 and 12000
+ * count, NaN does not; col0 >= width gives 0.  SDR_ERR_ARG: a NULL argument, a size <= 0. */
 int sdr_depth_coverage_device(sdr_display* h, const float* d_xyz, int width, int height,
                               int nframes, int col0, double* pct);
 /* stereo_displayer.cpp:167-173: applyColorMap(vis, JET) -> d_heat (nullable) and
  * addWeighted(resize(left_rect, 0.5, INTER_AREA), 0.7, heat, 0.3, 0) -> d_overlay (nullable), from
- * the FULL-resolution rectified left BGR view (2*width x 2*height, left_stride bytes per row,
- * left_frame_stride bytes per frame, 0 = dense); vis/heat/overlay are [F][H][W](x3). */
+ * the FULL-resolution rectified left BGR view (2*width x 2*height, left_stride bytes per row, as
+ * given; left_frame_stride bytes per frame, 0 = left_stride * 2 * height); vis/heat/overlay are
+ * dense [F][H][W](x3).  d_left_bgr is read only for d_overlay and may be NULL for a heat map alone.
+ * SDR_ERR_ARG: h or d_vis NULL, neither output, d_overlay without d_left_bgr, a size <= 0,
+ * left_stride < 3 * (2 * width) with d_left_bgr given. */
 int sdr_disparity_overlay_device(sdr_display* h, const uint8_t* d_vis, const uint8_t* d_left_bgr,
                                  size_t left_stride, size_t left_frame_stride, int width,
                                  int height, int nframes, const uint8_t* lut_bgr, uint8_t* d_heat,
                                  uint8_t* d_overlay);
-/* Host-pointer versions (synchronous; `stride` in elements, out_stride in bytes).  zrange: host
- * {zmin_smooth, zmax_smooth} in/out, NULL = the handle's own state. */
+/* Host-pointer versions (synchronous; `stride` in elements, out_stride in bytes, both >= width,
+ * left_stride >= 3 * (2 * width); one frame, other arrays dense).  zrange: host {zmin_smooth,
+ * zmax_smooth} in/out, NULL = the handle's own state.  sdr_disparity_overlay needs left_bgr for
+ * either output.  The refusals are those of the device versions. */
 int sdr_show_disparity_map(sdr_display* h, const float* disp, int width, int height, size_t stride,
                            int num_disparities, uint8_t* out, size_t out_stride);
 int sdr_show_depth_map(sdr_display* h, const float* xyz, int width, int height, int channels,

@@ -197,9 +197,11 @@ __global__ __launch_bounds__(256) void k_overlay(const uint8_t* __restrict__ vis
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         const uint8_t hc = sl[3 * v + c];
-        const uint8_t lc = (uint8_t)((a[c] + a[3 + c] + b[c] + b[3 + c] + 2) >> 2);
         if (heat) heat[3 * i + c] = hc;
-        if (overlay) overlay[3 * i + c] = add_weighted(lc, 0.7f, hc, 0.3f);
+        if (overlay) {  // the left view is read only here: it may be NULL for a heat map alone
+            const uint8_t lc = (uint8_t)((a[c] + a[3 + c] + b[c] + b[3 + c] + 2) >> 2);
+            overlay[3 * i + c] = add_weighted(lc, 0.7f, hc, 0.3f);
+        }
     }
 }
 
