@@ -783,6 +783,92 @@ int sdr_find_planes(const void* disp, int disp_type, size_t stride, size_t frame
                     sdr_plane* planes, int32_t* count, sdr_plane_search_round* rounds,
                     uint8_t* labels);
 
+/* ---- the relief of a region: a surface's height statistics above a fitted plane ----
+ * sdr_plane_relief* measures every pixel of a rectangle against a plane record (of sdr_fit_planes*
+ * or sdr_find_planes*), optionally only the pixels that carry one label of sdr_find_planes*'
+ * label map, and reports counts, extremes, means and order statistics of the heights.  Every output
+ * is a count, an exact integer sum, an extreme or an element of the set: none depends on the grid
+ * shape or on the order the workgroups finish in, and every one is defined to the bit.
+ *   - Query {frame, x0, y0, x1, y1, plane, label, 0}.  Region: the plane fit's rule (corners in
+ *     any order, xs / xe / ys / ye, area).  A frame outside [0, F) or a corner outside the image,
+ *     a label outside -1..255, or a label >= 0 without a label map: SDR_RELIEF_OUT_OF_RANGE,
+ *     nothing read, every count (area too) 0, both sums 0, every float and double the canonical NaN.
+ *     Otherwise `plane` outside [0, P) or a record without SDR_PLANE_OK: SDR_RELIEF_NO_PLANE, the
+ *     maps are not read, area is the region's, the other counts and the sums 0, the floats NaN.
+ *   - Pixel (x, y) of the rectangle, in this order:
+ *     1. masked in iff label < 0 or labels[frame][y][x] == label (n_masked counts these);
+ *     2. valid by the ruler's rule for a radius-0, min_count-1 sample: d finite, d > min_disp, and
+ *        with a confidence map conf >= conf_min; int16 read as (float)v * 0.0625f (n_valid counts
+ *        the masked-in pixels that are valid);
+ *     3. XYZ in float by reprojectImageTo3D's pixel formula at (x, y, d), handleMissing off (the
+ *        ruler's sample);
+ *     4. h = ((nx*X + ny*Y) + nz*Z) + offset in double from the float XYZ, no contraction
+ *        (sdr_plane_distance's expression); hf = (float)h + 0.0f (a negative zero becomes +0);
+ *     5. member iff X, Y and Z are finite and fabsf(hf) < 1048576.0f (n counts the members;
+ *        n_rejected = n_valid - n).
+ *   - Over the members: n_above counts hf > band, n_below hf < -band (float comparisons); h_min and
+ *     h_max are the extreme hf; e = llrint((double)hf * 256.0) (the product is exact, |e| < 2^28:
+ *     2^24 pixels cannot overflow int64); sum256 the sum of e, sum256_above the same over hf > band;
+ *     mean = ((double)sum256 / (double)n) / 256.0, mean_above likewise over n_above (NaN with none).
+ *   - Quantile j < nq: k = ((int64)(n - 1) * permille[j]) / 1000 and q[j] is element k (0-based) of
+ *     the members' hf in ascending order: 500 is the lower median, element (n-1)/2, 0 is h_min,
+ *     1000 is h_max.  q[j] for j >= nq is the canonical NaN.
+ *   - n == 0: SDR_RELIEF_EMPTY, the counts as found, the sums 0, every float and double NaN.
+ *     Otherwise SDR_RELIEF_VALID.  Every NaN written is the canonical quiet NaN.
+ *   - frame, plane and label of a record are its query's in every case. */
+typedef struct sdr_relief_query { /* 32 bytes */
+    int32_t frame, x0, y0, x1, y1; /* the rectangle, the plane fit's region rule */
+    int32_t plane;                 /* index into the P plane records */
+    int32_t label;                 /* -1: no mask; 0..255: only pixels whose label equals it */
+    int32_t reserved;              /* 0 */
+} sdr_relief_query;
+
+typedef struct sdr_relief_params { /* 64 bytes */
+    float min_disp, conf_min;      /* the ruler's validity rule */
+    float band;                    /* finite, >= 0, in Q's units (mm) */
+    int32_t nq;                    /* quantiles asked for, 0..8 */
+    int32_t permille[8];           /* each 0..1000; any order, repeats allowed; entries >= nq ignored */
+    int32_t reserved[4];           /* 0 */
+} sdr_relief_params;
+
+enum { SDR_RELIEF_VALID = 1, SDR_RELIEF_OUT_OF_RANGE = 2, SDR_RELIEF_NO_PLANE = 4, SDR_RELIEF_EMPTY = 8 };
+
+typedef struct sdr_relief { /* 128 bytes */
+    float q[8];                    /* the quantiles; entries >= nq the canonical NaN */
+    float h_min, h_max;
+    double mean, mean_above;
+    int64_t sum256, sum256_above;  /* the exact sums the means come from */
+    int32_t area, n_masked, n_valid, n, n_above, n_below, n_rejected;
+    int32_t frame, plane, label;   /* the query's */
+    uint32_t flags;                /* SDR_RELIEF_* */
+    int32_t reserved[3];           /* 0 */
+} sdr_relief;
+
+/* {-1.0f, 0.0f, 0.0f, 3, {50, 500, 950, 0, 0, 0, 0, 0}, {0, 0, 0, 0}} */
+void sdr_relief_params_default(sdr_relief_params* p);
+/* K queries on device maps against the P records of d_planes (arguments as
+ * sdr_plane_distance_device), asynchronous on `stream`: a fixed sequence of launches with no host
+ * synchronisation, a radix selection over the members' ordered keys in three passes of 11, 11 and
+ * 10 bits; the histograms and accumulators are stream-ordered scratch.  d_labels (nullable) is a
+ * dense uint8 [F][H][W]; with F = 1 it is exactly what sdr_find_planes_device writes.  d_out: K
+ * sdr_relief.  K == 0 is SDR_OK with no launch.  The host refuses, before any device call and with
+ * SDR_ERR_ARG: what sdr_fit_planes_device refuses of the maps (nulls, sizes, strides, disp_type,
+ * width or height > 8192, width * height > 2^24), K < 0, P < 0 or P > 0 without d_planes, nq
+ * outside 0..8, one of the first nq permille outside 0..1000, a band that is not finite or
+ * negative, a non-zero reserved field of the parameters.  The queries are device memory: what is
+ * wrong with one is refused per record (above). */
+int sdr_plane_relief_device(const void* d_disp, int disp_type, size_t stride, size_t frame_stride,
+                            int width, int height, int nframes, const float* d_conf,
+                            const uint8_t* d_labels, const double Q[16],
+                            const sdr_relief_params* params, const sdr_plane* d_planes, int P,
+                            const sdr_relief_query* d_queries, int K, sdr_relief* d_out,
+                            void* stream);
+/* Host-pointer version (synchronous; per-thread persistent device buffers as sdr_fit_planes). */
+int sdr_plane_relief(const void* disp, int disp_type, size_t stride, size_t frame_stride, int width,
+                     int height, int nframes, const float* conf, const uint8_t* labels,
+                     const double Q[16], const sdr_relief_params* params, const sdr_plane* planes,
+                     int P, const sdr_relief_query* queries, int K, sdr_relief* out);
+
 /* Bytes of device scratch the handle holds for the given frame shape (for capacity planning);
  * 0 when compute would refuse the shape or parameters.  sdr_sgbm_scratch_bytes is the CV_8UC1
  * figure, sdr_sgbm_scratch_bytes_cn takes the channel count (1 or 3: colour input holds three

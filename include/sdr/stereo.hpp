@@ -446,6 +446,7 @@ private:
 using Measurement = sdr_measurement;
 using Plane = sdr_plane;
 using PlaneDistance = struct sdr_plane_distance;  // the C record shares its name with a function
+using Relief = sdr_relief;
 struct Point {
     int x = 0, y = 0;
 };
@@ -596,6 +597,41 @@ public:
     PlaneDistance plane_distance(const Mat& disparity, const Plane& plane, Point at,
                                  const Mat* conf = nullptr) const {
         return plane_distance(disparity, std::vector<Plane>{plane}, {sdr_plane_query{0, at.x, at.y, 0}}, conf)[0];
+    }
+    // The relief of rectangles {frame, x0, y0, x1, y1, plane, label, 0} above `planes` (sdr.h, "the
+    // relief of a region"): counts, extremes, exact means and the quantiles (permille, at most 8) of
+    // the pixels' heights; labels (optional): a continuous CV_8UC1 map of the disparity's size as
+    // find_planes returns it, for queries with label >= 0; band: n_above / n_below count beyond it
+    std::vector<Relief> relief(const Mat& disparity, const std::vector<Plane>& planes,
+                               const std::vector<sdr_relief_query>& regions, const Mat* labels = nullptr,
+                               const Mat* conf = nullptr, const std::vector<int>& quantiles = {50, 500, 950},
+                               float band = 0.0f) const {
+        check_maps(disparity, conf, "relief");
+        if (labels && (labels->type != CV_8UC1 || labels->rows != disparity.rows || labels->cols != disparity.cols ||
+                       labels->step != (size_t)labels->cols))
+            throw Exception(SDR_ERR_TYPE, "labels must be a continuous CV_8U map of the disparity's size");
+        if (quantiles.size() > 8) throw Exception(SDR_ERR_ARG, "relief takes at most 8 quantiles");
+        const size_t es = elem_size(disparity.type);
+        sdr_relief_params rp;
+        sdr_relief_params_default(&rp);
+        rp.min_disp = p_.min_disp;
+        rp.conf_min = p_.conf_min;
+        rp.band = band;
+        rp.nq = (int)quantiles.size();
+        for (size_t j = 0; j < 8; j++) rp.permille[j] = j < quantiles.size() ? quantiles[j] : 0;
+        std::vector<Relief> out(regions.size());
+        check(sdr_plane_relief(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16,
+                               disparity.step / es, disparity.step / es * disparity.rows, disparity.cols,
+                               disparity.rows, 1, conf ? conf->ptr<float>(0) : nullptr,
+                               labels ? labels->data : nullptr, q_, &rp, planes.empty() ? nullptr : planes.data(),
+                               (int)planes.size(), regions.empty() ? nullptr : regions.data(), (int)regions.size(),
+                               out.empty() ? nullptr : out.data()));
+        return out;
+    }
+    Relief relief(const Mat& disparity, const Plane& plane, Point a, Point b, const Mat* labels = nullptr,
+                  int label = -1, const Mat* conf = nullptr) const {
+        return relief(disparity, std::vector<Plane>{plane}, {sdr_relief_query{0, a.x, a.y, b.x, b.y, 0, label, 0}},
+                      labels, conf)[0];
     }
 
 private:

@@ -18,6 +18,7 @@ from .ruler import (  # noqa: F401
     PLANE_DISTANCE_DTYPE, PLANE_DTYPE, PLANE_NONFINITE, PLANE_OK, PLANE_OUT_OF_RANGE,
     PLANE_SEARCH_ROUND_DTYPE, SEARCH_FEW_INLIERS, SEARCH_LOW_SCORE, SEARCH_NO_HYPOTHESIS, SEARCH_NOT_RUN,
     SEARCH_RAN, SEARCH_REFIT_DEGENERATE, MeasurementLog, Ruler, plane_angle_deg,
+    RELIEF_DTYPE, RELIEF_EMPTY, RELIEF_NO_PLANE, RELIEF_OUT_OF_RANGE, RELIEF_VALID, as_relief_queries,
 )
 from .stereo_disparity import StereoDisparity  # noqa: F401
 
@@ -31,4 +32,5 @@ __all__ = [
     "PLANE_OK", "PLANE_DEGENERATE", "PLANE_NONFINITE", "PLANE_OUT_OF_RANGE", "PDIST_VALID",
     "PDIST_OUT_OF_RANGE", "PDIST_NO_PLANE", "plane_angle_deg", "PLANE_SEARCH_ROUND_DTYPE", "SEARCH_RAN",
     "SEARCH_NO_HYPOTHESIS", "SEARCH_LOW_SCORE", "SEARCH_REFIT_DEGENERATE", "SEARCH_FEW_INLIERS", "SEARCH_NOT_RUN",
+    "RELIEF_DTYPE", "RELIEF_VALID", "RELIEF_OUT_OF_RANGE", "RELIEF_NO_PLANE", "RELIEF_EMPTY", "as_relief_queries",
 ]

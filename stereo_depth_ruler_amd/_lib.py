@@ -143,6 +143,27 @@ class PlaneSearchRound(ctypes.Structure):
                 ("stop", ctypes.c_uint32)]
 
 
+class ReliefQuery(ctypes.Structure):
+    """sdr_relief_query (32 bytes)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("frame", "x0", "y0", "x1", "y1", "plane", "label", "reserved")]
+
+
+class ReliefParams(ctypes.Structure):
+    """sdr_relief_params (64 bytes)."""
+    _fields_ = [("min_disp", ctypes.c_float), ("conf_min", ctypes.c_float), ("band", ctypes.c_float),
+                ("nq", ctypes.c_int32), ("permille", ctypes.c_int32 * 8), ("reserved", ctypes.c_int32 * 4)]
+
+
+class Relief(ctypes.Structure):
+    """sdr_relief (128 bytes)."""
+    _fields_ = [("q", ctypes.c_float * 8), ("h_min", ctypes.c_float), ("h_max", ctypes.c_float),
+                ("mean", ctypes.c_double), ("mean_above", ctypes.c_double),
+                ("sum256", ctypes.c_int64), ("sum256_above", ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ("area", "n_masked", "n_valid", "n", "n_above", "n_below",
+                                              "n_rejected", "frame", "plane", "label")] + \
+               [("flags", ctypes.c_uint32), ("reserved", ctypes.c_int32 * 3)]
+
+
 _lib = None
 _path = LIB_PATH
 
@@ -279,6 +300,11 @@ SIGNATURES = [
                                     _c.POINTER(PlaneSearchParams), _vp, _vp, _vp, _vp, _vp, _vp]),
     ("sdr_find_planes", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _c.POINTER(_c.c_double),
                              _c.POINTER(PlaneSearchParams), _vp, _vp, _vp, _vp, _vp]),
+    ("sdr_relief_params_default", None, [_c.POINTER(ReliefParams)]),
+    ("sdr_plane_relief_device", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _vp, _c.POINTER(_c.c_double),
+                                     _c.POINTER(ReliefParams), _vp, _i, _vp, _i, _vp, _vp]),
+    ("sdr_plane_relief", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _vp, _c.POINTER(_c.c_double),
+                              _c.POINTER(ReliefParams), _vp, _i, _vp, _i, _vp]),
     ("sdr_build_id", _c.c_char_p, []),
     ("sdr_last_error", _c.c_char_p, []),
     ("sdr_abi_version", _i, []),

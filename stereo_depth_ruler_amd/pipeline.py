@@ -151,6 +151,16 @@ class LiveLoop:
             raise RuntimeError("LiveLoop was built without ruler=")
         return self.ruler.plane_distance_device(self.disp, planes, points, conf=self.conf, stream=stream)
 
+    def relief(self, planes, regions, stream, labels=None, quantiles=(50, 500, 950), band: float = 0.0):
+        """Ruler.relief_device on the same frames: `planes` (and `labels`) the tensors find_planes or
+        fit_plane returned (or host records), regions rows {frame, x0, y0, x1, y1, plane, label}: the
+        (K, 128) relief records tensor, no synchronise in between.  A label map of one frame (what
+        find_planes writes) serves a batch of one frame; a batch takes a (batch, H, W) map."""
+        if self.ruler is None:
+            raise RuntimeError("LiveLoop was built without ruler=")
+        return self.ruler.relief_device(self.disp, planes, regions, labels=labels, conf=self.conf,
+                                        quantiles=quantiles, band=band, stream=stream)
+
     def close(self):
         for o in (self.left, self.right, self.wls, self.display):
             if o is not None:

@@ -13,6 +13,10 @@ engine (csrc/sdr_ruler.hip; the definition is in include/sdr/sdr.h).
   integer moments, a coarse-to-fine inlier refit) and ``Ruler.plane_distance(disparity, planes,
   points)`` gives the signed distance of sampled points to those planes, positive towards the
   camera: heights above a table, steps, distances from a wall.
+* ``Ruler.relief(disparity, planes, regions, labels=None)`` measures a whole surface against a plane:
+  the heights of a rectangle's pixels (optionally only those with one label of ``find_planes``' map)
+  above a plane record, as counts, extremes, exact means and order statistics (a radix selection on
+  the device, csrc/sdr_relief.hip): the height of a box above the table, the depth of a step.
 * ``Ruler.find_planes(disparity, region=None)`` finds a region's dominant planes without a prior (a
   box on a table in front of a wall): rounds of seeded three-point hypotheses scored in exact
   integer arithmetic on the pixels no earlier plane has claimed, the winner refitted as
@@ -33,7 +37,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import DISP_F32, DISP_S16, PlaneParams, PlaneSearchParams, RulerParams, SDRError, check, lib
+from ._lib import (DISP_F32, DISP_S16, PlaneParams, PlaneSearchParams, ReliefParams, RulerParams, SDRError, check,
+                   lib)
 from .sgbm import _Q, _is_cuda, torch
 
 MEASUREMENT_DTYPE = np.dtype([
@@ -65,6 +70,34 @@ PLANE_SEARCH_ROUND_DTYPE = np.dtype([("hypothesis", "<i4"), ("score", "<i4"), ("
 assert PLANE_SEARCH_ROUND_DTYPE.itemsize == 16
 (SEARCH_RAN, SEARCH_NO_HYPOTHESIS, SEARCH_LOW_SCORE, SEARCH_REFIT_DEGENERATE, SEARCH_FEW_INLIERS,
  SEARCH_NOT_RUN) = range(6)
+
+
+# sdr_relief and its flags (SDR_RELIEF_*)
+RELIEF_DTYPE = np.dtype([
+    ("q", "<f4", (8,)), ("h_min", "<f4"), ("h_max", "<f4"), ("mean", "<f8"), ("mean_above", "<f8"),
+    ("sum256", "<i8"), ("sum256_above", "<i8"), ("area", "<i4"), ("n_masked", "<i4"), ("n_valid", "<i4"),
+    ("n", "<i4"), ("n_above", "<i4"), ("n_below", "<i4"), ("n_rejected", "<i4"), ("frame", "<i4"),
+    ("plane", "<i4"), ("label", "<i4"), ("flags", "<u4"), ("reserved", "<i4", (3,))])
+assert RELIEF_DTYPE.itemsize == 128
+RELIEF_VALID, RELIEF_OUT_OF_RANGE, RELIEF_NO_PLANE, RELIEF_EMPTY = 1, 2, 4, 8
+
+
+def as_relief_queries(regions) -> np.ndarray:
+    """(K, 8) int32 {frame, x0, y0, x1, y1, plane, label, 0} from rows of 7
+    {frame, x0, y0, x1, y1, plane, label}, of 6 (label -1) or of 5 (plane 0, label -1) / one tuple."""
+    r = np.asarray(regions)
+    if r.size == 0:
+        return np.zeros((0, 8), np.int32)
+    if r.ndim == 1:
+        r = r[None, :]
+    if r.ndim != 2 or r.shape[1] not in (5, 6, 7):
+        raise SDRError(-1, "regions must be (K, 7) {frame, x0, y0, x1, y1, plane, label}, (K, 6) or (K, 5)")
+    if r.dtype.kind not in "iu":
+        raise SDRError(-1, "regions must be integers")
+    q = np.zeros((r.shape[0], 8), np.int32)
+    q[:, 6] = -1
+    q[:, :r.shape[1]] = r
+    return q
 
 
 def as_queries(points) -> np.ndarray:
@@ -517,6 +550,107 @@ class Ruler:
                 conf.data_ptr() if conf is not None else None, _Q(self.Q), ctypes.byref(p),
                 pl.data_ptr() if P else None, P, qs.data_ptr() if K else None, K,
                 out.data_ptr() if K else None, ctypes.c_void_p(s.cuda_stream)))
+        return out
+
+    # ---- the relief of a region (sdr.h, "the relief of a region") ----
+    def _relief_params(self, quantiles, band) -> ReliefParams:
+        qs = [int(v) for v in quantiles]
+        if len(qs) > 8:
+            raise SDRError(-1, "at most 8 quantiles")
+        if any(v < 0 or v > 1000 for v in qs) or any(int(v) != v for v in quantiles):
+            raise SDRError(-1, "quantiles are integers in 0..1000 (permille)")
+        band = float(band)
+        if not (np.isfinite(band) and band >= 0.0):
+            raise SDRError(-1, "band must be finite and >= 0")
+        p = ReliefParams(self.min_disp, self.conf_min, band, len(qs))
+        for j, v in enumerate(qs):
+            p.permille[j] = v
+        return p
+
+    def relief(self, disparity, planes, regions, labels=None, conf=None, quantiles=(50, 500, 950),
+               band: float = 0.0):
+        """The heights of K rectangles' pixels above plane records: a RELIEF_DTYPE array of K.
+        planes: PLANE_DTYPE records or a device tensor of them; regions: rows
+        {frame, x0, y0, x1, y1, plane, label} (rows of 5 or 6: plane 0, label -1 = no mask);
+        labels: a uint8 (H, W) / (F, H, W) map as find_planes returns it, a query with label >= 0
+        takes only the pixels that carry it; quantiles: up to 8 permille values, q[j] the element
+        (n-1)*permille/1000 of the heights in ascending order; band: n_above / n_below count the
+        heights beyond +-band (Q's units)."""
+        if _is_cuda(disparity):
+            out = self.relief_device(disparity, planes, regions, labels, conf, quantiles, band)
+            return out.cpu().numpy().reshape(-1).view(RELIEF_DTYPE)
+        p = self._relief_params(quantiles, band)
+        if _is_cuda(planes):
+            planes = planes.cpu().numpy()
+        pl = np.ascontiguousarray(planes).reshape(-1).view(np.uint8).view(PLANE_DTYPE)
+        d, c, rs, fs = self._host_maps(disparity, conf)
+        F, H, W = d.shape
+        lab = None
+        if labels is not None:
+            if _is_cuda(labels):
+                labels = labels.cpu().numpy()
+            lab = np.asarray(labels)
+            if lab.dtype != np.uint8:
+                raise SDRError(-5, "labels must be uint8")
+            lab = np.ascontiguousarray(_frames3(lab, "labels"))
+            if lab.shape != d.shape:
+                raise SDRError(-1, "labels must have the disparity's shape")
+        qs = as_relief_queries(regions)
+        K, P = qs.shape[0], pl.shape[0]
+        out = np.zeros(K, RELIEF_DTYPE)
+        with _on_device(self.device):
+            rc = lib().sdr_plane_relief(
+                d.ctypes.data, DISP_F32 if d.dtype == np.float32 else DISP_S16, rs, fs, W, H, F,
+                c.ctypes.data if c is not None else None, lab.ctypes.data if lab is not None else None,
+                _Q(self.Q), ctypes.byref(p), pl.ctypes.data if P else None, P,
+                qs.ctypes.data if K else None, K, out.ctypes.data if K else None)
+        check(rc)
+        return out
+
+    def relief_device(self, disparity, planes, regions, labels=None, conf=None, quantiles=(50, 500, 950),
+                      band: float = 0.0, stream=None):
+        """Enqueues the reliefs on `stream` (default: the current stream) and returns a uint8 tensor
+        (K, 128) without synchronising (view its host copy as RELIEF_DTYPE).  planes and labels: as
+        find_planes_device returns them (a search and its relief then chain on one stream with no
+        host round trip) or host arrays; regions: host rows or a CUDA int32 (K, 8)."""
+        if not _is_cuda(disparity):
+            raise SDRError(-5, "relief_device expects a CUDA float32 or int16 tensor")
+        p = self._relief_params(quantiles, band)
+        dev = disparity.device
+        s = stream if stream is not None else torch.cuda.current_stream(dev.index)
+        with torch.cuda.stream(s):
+            d, conf = self._device_maps(disparity, conf)
+            F, H, W = d.shape
+            if _is_cuda(planes):
+                if planes.dtype != torch.uint8 or planes.numel() % 128:
+                    raise SDRError(-5, "device planes must be a uint8 tensor (P, 128)")
+                pl = planes.contiguous()
+                P = pl.numel() // 128
+            else:
+                host = np.ascontiguousarray(planes).reshape(-1).view(np.uint8).reshape(-1, 128)
+                P = host.shape[0]
+                pl = torch.from_numpy(host.copy()).to(dev) if P else None
+            lab = None
+            if labels is not None:
+                lab = labels if _is_cuda(labels) else torch.from_numpy(np.ascontiguousarray(labels)).to(dev)
+                if lab.dtype != torch.uint8 or lab.numel() != d.numel():
+                    raise SDRError(-5, "labels must be a uint8 map of the disparity's shape")
+                lab = lab.contiguous()
+            if _is_cuda(regions):
+                if regions.dtype != torch.int32 or regions.dim() != 2 or regions.shape[1] != 8:
+                    raise SDRError(-5, "device regions must be an int32 tensor (K, 8)")
+                qs = regions.contiguous()
+            else:
+                qs = self._upload_segments(as_relief_queries(regions), dev, s)
+            K = qs.shape[0]
+            out = torch.empty((K, 128), dtype=torch.uint8, device=dev)
+            check(lib().sdr_plane_relief_device(
+                d.data_ptr(), DISP_F32 if d.dtype == torch.float32 else DISP_S16, d.stride(1),
+                d.stride(1) * H if F == 1 else d.stride(0), W, H, F,
+                conf.data_ptr() if conf is not None else None, lab.data_ptr() if lab is not None else None,
+                _Q(self.Q), ctypes.byref(p), pl.data_ptr() if P else None, P,
+                qs.data_ptr() if K else None, K, out.data_ptr() if K else None,
+                ctypes.c_void_p(s.cuda_stream)))
         return out
 
     # ---- XYZ-map mode (the reference's measurement) ----
