@@ -869,6 +869,111 @@ int sdr_plane_relief(const void* disp, int disp_type, size_t stride, size_t fram
                      const double Q[16], const sdr_relief_params* params, const sdr_plane* planes,
                      int P, const sdr_relief_query* queries, int K, sdr_relief* out);
 
+/* ---- the footprint of a region: a surface's oriented length and width on a plane ----
+ * sdr_plane_footprint* takes the pixels of a rectangle (optionally only those carrying one label,
+ * optionally only those in a band of heights), bins them on a grid of square cells IN a plane
+ * record's plane, drops the cells that stray pixels occupy alone, and reports the minimum-area
+ * bounding rectangle of the kept cells over 90 whole-degree orientations: two sides, the angle and
+ * four 3-D corners.  Every step is a count, an integer extreme or a correctly rounded double
+ * operation (no contraction): no output depends on the grid shape or on the order the workgroups
+ * finish in, and every one is defined to the bit.
+ *   - Query: an sdr_relief_query under the relief's rules.  SDR_FOOTPRINT_OUT_OF_RANGE (a frame or
+ *     corner outside, a label outside -1..255, a label >= 0 without a label map): nothing read,
+ *     every count (area too) 0.  Otherwise SDR_FOOTPRINT_NO_PLANE (`plane` outside [0, P), a record
+ *     without SDR_PLANE_OK, or a basis below that is not finite): the maps are not read, area is
+ *     the region's, the other counts 0.
+ *   - Basis, once a query, in double: n = the record's normal; the camera X axis if
+ *     fabs(nx) <= fabs(ny), else the Y axis, minus its component along n:
+ *     X axis: (a, b, c) = (1 - nx*nx, -(nx*ny), -(nx*nz)); Y axis: (-(nx*ny), 1 - ny*ny, -(ny*nz));
+ *     len = sqrt((a*a + b*b) + c*c); e_s = (a/len, b/len, c/len); e_t = n x e_s by the plane fit's
+ *     expressions: tx = ny*esz - nz*esy, ty = nz*esx - nx*esz, tz = nx*esy - ny*esx.
+ *   - Member: a pixel that passes the relief's steps 1 to 5 (mask, validity, float XYZ, h, hf,
+ *     X / Y / Z finite and fabsf(hf) < 1048576.0f; n_masked and n_valid count as there), then
+ *     h_lo <= hf && hf <= h_hi (float comparisons), then with
+ *     s = (esx*X + esy*Y) + esz*Z, t likewise with e_t (double, from the float XYZ),
+ *     qs = s / (double)cell, qt = t / (double)cell: fabs(qs) < 2^30 and fabs(qt) < 2^30.
+ *     si = (int64)floor(qs), ti = (int64)floor(qt).  n counts the members.
+ *   - Grid: i0 = min si, j0 = min ti over the members; a member's cell is (si - i0, ti - j0), inside
+ *     iff both indices are < grid.  n_outside counts the members outside; n_outside > 0 sets
+ *     SDR_FOOTPRINT_CLIPPED beside the record's other flag.  count[i][j] = the inside members of
+ *     the cell.  span_s = max si - i0 + 1, span_t = max ti - j0 + 1 (int64, saturated to int32).
+ *   - Kept cells: count[i][j] >= 1 and the sum of count over the cell's 3 x 3 neighbourhood (cells
+ *     outside the grid count 0) >= support.  n_cells_raw = the cells with count >= 1, n_cells = the
+ *     kept ones.  n_cells == 0 (n == 0 too): SDR_FOOTPRINT_EMPTY, the counts, i0, j0 and the spans
+ *     as found (0 with no member).  Otherwise SDR_FOOTPRINT_VALID.
+ *   - Directions: the table c_k = lrint(16384 * cos(k deg)), s_k = lrint(16384 * sin(k deg)),
+ *     k = 0..89, a literal in the source (sdr_footprint_direction returns it).  c_k*c_k + s_k*s_k
+ *     is 2^28 only to about 6e-5 of it: a direction's length is 1 to about 3e-5, and so is a side.
+ *   - Extents of direction k over the kept cells (i, j), int32 (grid <= 1024: |p|, |r| < 2^25):
+ *     p = c_k*i + s_k*j, r = -s_k*i + c_k*j; the unit cell square projects to [p, p + c_k + s_k] and
+ *     [r - s_k, r + c_k]: U0 = min p, U1 = max p + c_k + s_k, V0 = min r - s_k, V1 = max r + c_k;
+ *     A_k = (int64)(U1 - U0) * (int64)(V1 - V0).  The answer is the k of the smallest A_k, ties to
+ *     the lowest k; angle_deg = k: side[0] runs along e_s turned by k degrees towards e_t.
+ *   - side[0] = ((double)(U1 - U0) / 16384.0) * (double)cell, side[1] likewise from V;
+ *     fill = (double)n_cells / (((double)(U1 - U0) / 16384.0) * ((double)(V1 - V0) / 16384.0)).
+ *   - Corners, in the order (U0, V0), (U1, V0), (U1, V1), (U0, V1): a = U / 16384.0,
+ *     b = V / 16384.0, ch = c_k / 16384.0, sh = s_k / 16384.0; gi = ch*a - sh*b; gj = sh*a + ch*b;
+ *     S = ((double)i0 + gi) * (double)cell; T = ((double)j0 + gj) * (double)cell; each component
+ *     corner[x] = (S*es[x] + T*et[x]) - offset*n[x]: the point of the plane at (S, T).
+ *   - A record that is not VALID: every double the canonical NaN, angle_deg -1.  frame, plane and
+ *     label are the query's in every case.  Occupied area and volume are deliberately not reported:
+ *     holes and the aliasing of pixel spacing against the cell put them 10 to 35 % off; n_cells and
+ *     fill are quality indicators only. */
+typedef struct sdr_footprint_params { /* 64 bytes */
+    float min_disp, conf_min;      /* the ruler's validity rule */
+    float cell;                    /* cell side in Q's units (mm): finite, 0.0625 .. 65536 */
+    float h_lo, h_hi;              /* members have h_lo <= hf <= h_hi; not NaN, h_lo <= h_hi */
+    int32_t grid;                  /* cells a side, 16..1024 */
+    int32_t support;               /* members a kept cell's 3 x 3 neighbourhood holds, 1..255 */
+    int32_t reserved[9];           /* 0 */
+} sdr_footprint_params;
+
+enum {
+    SDR_FOOTPRINT_VALID = 1, SDR_FOOTPRINT_OUT_OF_RANGE = 2, SDR_FOOTPRINT_NO_PLANE = 4,
+    SDR_FOOTPRINT_EMPTY = 8, SDR_FOOTPRINT_CLIPPED = 16
+};
+
+typedef struct sdr_footprint { /* 256 bytes */
+    double side[2];                /* along the direction angle_deg and across it, Q's units */
+    double fill;                   /* kept cells / the rectangle's area in cells */
+    double corner[4][3];           /* the rectangle's corners in 3-D, on the plane */
+    double basis_s[3], basis_t[3]; /* e_s, e_t */
+    int64_t i0, j0;                /* the grid's origin in cells */
+    int32_t angle_deg;             /* k, 0..89; -1 without a rectangle */
+    int32_t span_s, span_t;        /* the members' extent in cells, before the grid clips it */
+    int32_t area, n_masked, n_valid, n, n_outside, n_cells_raw, n_cells;
+    int32_t frame, plane, label;   /* the query's */
+    uint32_t flags;                /* SDR_FOOTPRINT_* */
+    int32_t reserved[4];           /* 0 */
+} sdr_footprint;
+
+/* {-1.0f, 0.0f, 4.0f, -1048576.0f, 1048576.0f, 512, 4, {0, ...}} */
+void sdr_footprint_params_default(sdr_footprint_params* p);
+/* The direction table: *c = c_k, *s = s_k and SDR_OK for k in 0..89, else SDR_ERR_ARG (also for a
+ * null pointer).  Pure host code. */
+int sdr_footprint_direction(int k, int32_t* c, int32_t* s);
+/* K queries on device maps against the P records of d_planes (arguments as
+ * sdr_plane_relief_device), asynchronous on `stream`: a fixed sequence of launches a batch of
+ * queries with no host synchronisation (setup, a sweep for the counts and the origin, a sweep that
+ * bins, a pass over the cells, the record).  The grids and accumulators are stream-ordered scratch;
+ * the queries run in batches so that the grids take at most 64 MiB.  K == 0 is SDR_OK with no
+ * launch.  The host refuses, before any device call and with SDR_ERR_ARG: what
+ * sdr_plane_relief_device refuses of the maps, K < 0, P < 0 or P > 0 without d_planes, a cell that
+ * is not finite or outside [0.0625, 65536], grid outside 16..1024, support outside 1..255, h_lo or
+ * h_hi NaN or h_lo > h_hi, a non-zero reserved field of the parameters. */
+int sdr_plane_footprint_device(const void* d_disp, int disp_type, size_t stride, size_t frame_stride,
+                               int width, int height, int nframes, const float* d_conf,
+                               const uint8_t* d_labels, const double Q[16],
+                               const sdr_footprint_params* params, const sdr_plane* d_planes, int P,
+                               const sdr_relief_query* d_queries, int K, sdr_footprint* d_out,
+                               void* stream);
+/* Host-pointer version (synchronous; per-thread persistent device buffers as sdr_fit_planes). */
+int sdr_plane_footprint(const void* disp, int disp_type, size_t stride, size_t frame_stride, int width,
+                        int height, int nframes, const float* conf, const uint8_t* labels,
+                        const double Q[16], const sdr_footprint_params* params,
+                        const sdr_plane* planes, int P, const sdr_relief_query* queries, int K,
+                        sdr_footprint* out);
+
 /* Bytes of device scratch the handle holds for the given frame shape (for capacity planning);
  * 0 when compute would refuse the shape or parameters.  sdr_sgbm_scratch_bytes is the CV_8UC1
  * figure, sdr_sgbm_scratch_bytes_cn takes the channel count (1 or 3: colour input holds three

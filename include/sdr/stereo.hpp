@@ -447,6 +447,7 @@ using Measurement = sdr_measurement;
 using Plane = sdr_plane;
 using PlaneDistance = struct sdr_plane_distance;  // the C record shares its name with a function
 using Relief = sdr_relief;
+using Footprint = sdr_footprint;
 struct Point {
     int x = 0, y = 0;
 };
@@ -632,6 +633,43 @@ public:
                   int label = -1, const Mat* conf = nullptr) const {
         return relief(disparity, std::vector<Plane>{plane}, {sdr_relief_query{0, a.x, a.y, b.x, b.y, 0, label, 0}},
                       labels, conf)[0];
+    }
+    // The footprint of rectangles {frame, x0, y0, x1, y1, plane, label, 0} in the planes of `planes`
+    // (sdr.h, "the footprint of a region"): the minimum-area bounding rectangle, over 90 whole-degree
+    // directions, of the plane's cells of `cell` (Q's units) that the pixels occupy with `support`
+    // members in their 3 x 3 neighbourhood, on a grid of `grid` cells a side; h_lo / h_hi: only the
+    // pixels whose height above the plane lies between them; labels and conf as in relief
+    std::vector<Footprint> footprint(const Mat& disparity, const std::vector<Plane>& planes,
+                                     const std::vector<sdr_relief_query>& regions, const Mat* labels = nullptr,
+                                     const Mat* conf = nullptr, float cell = 4.0f, int grid = 512, int support = 4,
+                                     float h_lo = -1048576.0f, float h_hi = 1048576.0f) const {
+        check_maps(disparity, conf, "footprint");
+        if (labels && (labels->type != CV_8UC1 || labels->rows != disparity.rows || labels->cols != disparity.cols ||
+                       labels->step != (size_t)labels->cols))
+            throw Exception(SDR_ERR_TYPE, "labels must be a continuous CV_8U map of the disparity's size");
+        const size_t es = elem_size(disparity.type);
+        sdr_footprint_params fp;
+        sdr_footprint_params_default(&fp);
+        fp.min_disp = p_.min_disp;
+        fp.conf_min = p_.conf_min;
+        fp.cell = cell;
+        fp.grid = grid;
+        fp.support = support;
+        fp.h_lo = h_lo;
+        fp.h_hi = h_hi;
+        std::vector<Footprint> out(regions.size());
+        check(sdr_plane_footprint(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16,
+                                  disparity.step / es, disparity.step / es * disparity.rows, disparity.cols,
+                                  disparity.rows, 1, conf ? conf->ptr<float>(0) : nullptr,
+                                  labels ? labels->data : nullptr, q_, &fp, planes.empty() ? nullptr : planes.data(),
+                                  (int)planes.size(), regions.empty() ? nullptr : regions.data(),
+                                  (int)regions.size(), out.empty() ? nullptr : out.data()));
+        return out;
+    }
+    Footprint footprint(const Mat& disparity, const Plane& plane, Point a, Point b, const Mat* labels = nullptr,
+                        int label = -1, const Mat* conf = nullptr) const {
+        return footprint(disparity, std::vector<Plane>{plane},
+                         {sdr_relief_query{0, a.x, a.y, b.x, b.y, 0, label, 0}}, labels, conf)[0];
     }
 
 private:

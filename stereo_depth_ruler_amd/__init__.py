@@ -19,6 +19,8 @@ from .ruler import (  # noqa: F401
     PLANE_SEARCH_ROUND_DTYPE, SEARCH_FEW_INLIERS, SEARCH_LOW_SCORE, SEARCH_NO_HYPOTHESIS, SEARCH_NOT_RUN,
     SEARCH_RAN, SEARCH_REFIT_DEGENERATE, MeasurementLog, Ruler, plane_angle_deg,
     RELIEF_DTYPE, RELIEF_EMPTY, RELIEF_NO_PLANE, RELIEF_OUT_OF_RANGE, RELIEF_VALID, as_relief_queries,
+    FOOTPRINT_CLIPPED, FOOTPRINT_DTYPE, FOOTPRINT_EMPTY, FOOTPRINT_NO_PLANE, FOOTPRINT_OUT_OF_RANGE, FOOTPRINT_VALID,
+    footprint_length_width,
 )
 from .stereo_disparity import StereoDisparity  # noqa: F401
 
@@ -33,4 +35,6 @@ __all__ = [
     "PDIST_OUT_OF_RANGE", "PDIST_NO_PLANE", "plane_angle_deg", "PLANE_SEARCH_ROUND_DTYPE", "SEARCH_RAN",
     "SEARCH_NO_HYPOTHESIS", "SEARCH_LOW_SCORE", "SEARCH_REFIT_DEGENERATE", "SEARCH_FEW_INLIERS", "SEARCH_NOT_RUN",
     "RELIEF_DTYPE", "RELIEF_VALID", "RELIEF_OUT_OF_RANGE", "RELIEF_NO_PLANE", "RELIEF_EMPTY", "as_relief_queries",
+    "FOOTPRINT_DTYPE", "FOOTPRINT_VALID", "FOOTPRINT_OUT_OF_RANGE", "FOOTPRINT_NO_PLANE", "FOOTPRINT_EMPTY",
+    "FOOTPRINT_CLIPPED", "footprint_length_width",
 ]

@@ -164,6 +164,22 @@ class Relief(ctypes.Structure):
                [("flags", ctypes.c_uint32), ("reserved", ctypes.c_int32 * 3)]
 
 
+class FootprintParams(ctypes.Structure):
+    """sdr_footprint_params (64 bytes)."""
+    _fields_ = [(n, ctypes.c_float) for n in ("min_disp", "conf_min", "cell", "h_lo", "h_hi")] + \
+               [("grid", ctypes.c_int32), ("support", ctypes.c_int32), ("reserved", ctypes.c_int32 * 9)]
+
+
+class Footprint(ctypes.Structure):
+    """sdr_footprint (256 bytes)."""
+    _fields_ = [("side", ctypes.c_double * 2), ("fill", ctypes.c_double), ("corner", (ctypes.c_double * 3) * 4),
+                ("basis_s", ctypes.c_double * 3), ("basis_t", ctypes.c_double * 3),
+                ("i0", ctypes.c_int64), ("j0", ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ("angle_deg", "span_s", "span_t", "area", "n_masked", "n_valid", "n",
+                                              "n_outside", "n_cells_raw", "n_cells", "frame", "plane", "label")] + \
+               [("flags", ctypes.c_uint32), ("reserved", ctypes.c_int32 * 4)]
+
+
 _lib = None
 _path = LIB_PATH
 
@@ -305,6 +321,12 @@ SIGNATURES = [
                                      _c.POINTER(ReliefParams), _vp, _i, _vp, _i, _vp, _vp]),
     ("sdr_plane_relief", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _vp, _c.POINTER(_c.c_double),
                               _c.POINTER(ReliefParams), _vp, _i, _vp, _i, _vp]),
+    ("sdr_footprint_params_default", None, [_c.POINTER(FootprintParams)]),
+    ("sdr_footprint_direction", _i, [_i, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32)]),
+    ("sdr_plane_footprint_device", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _vp, _c.POINTER(_c.c_double),
+                                        _c.POINTER(FootprintParams), _vp, _i, _vp, _i, _vp, _vp]),
+    ("sdr_plane_footprint", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _vp, _c.POINTER(_c.c_double),
+                                 _c.POINTER(FootprintParams), _vp, _i, _vp, _i, _vp]),
     ("sdr_build_id", _c.c_char_p, []),
     ("sdr_last_error", _c.c_char_p, []),
     ("sdr_abi_version", _i, []),

@@ -1,0 +1,586 @@
+// sdr_footprint.hip -- the footprint of a region: the pixels of a rectangle binned on a grid of
+// square cells in a fitted plane, the cells that stray pixels occupy alone dropped by a 3 x 3
+// support rule, and the minimum-area bounding rectangle of the kept cells over 90 whole-degree
+// directions.  The definition is in include/sdr/sdr.h ("the footprint of a region").
+#include <limits.h>
+#include <math.h>
+#include <string.h>
+
+#include <cmath>
+
+#include <algorithm>
+#include <string>
+#include <type_traits>
+
+#include "sdr_device.hpp"
+#include "sdr_internal.hpp"
+#include "sdr_ruler_shared.hpp"
+
+// c_k = lrint(16384 * cos(k deg)), s_k = lrint(16384 * sin(k deg)), k = 0..89
+#define SDR_FOOT_DIRS                                                                          \
+    {16384, 0}, {16382, 286}, {16374, 572}, {16362, 857}, {16344, 1143},                       \
+    {16322, 1428}, {16294, 1713}, {16262, 1997}, {16225, 2280}, {16182, 2563},                 \
+    {16135, 2845}, {16083, 3126}, {16026, 3406}, {15964, 3686}, {15897, 3964},                 \
+    {15826, 4240}, {15749, 4516}, {15668, 4790}, {15582, 5063}, {15491, 5334},                 \
+    {15396, 5604}, {15296, 5872}, {15191, 6138}, {15082, 6402}, {14968, 6664},                 \
+    {14849, 6924}, {14726, 7182}, {14598, 7438}, {14466, 7692}, {14330, 7943},                 \
+    {14189, 8192}, {14044, 8438}, {13894, 8682}, {13741, 8923}, {13583, 9162},                 \
+    {13421, 9397}, {13255, 9630}, {13085, 9860}, {12911, 10087}, {12733, 10311},               \
+    {12551, 10531}, {12365, 10749}, {12176, 10963}, {11982, 11174}, {11786, 11381},            \
+    {11585, 11585}, {11381, 11786}, {11174, 11982}, {10963, 12176}, {10749, 12365},            \
+    {10531, 12551}, {10311, 12733}, {10087, 12911}, {9860, 13085}, {9630, 13255},              \
+    {9397, 13421}, {9162, 13583}, {8923, 13741}, {8682, 13894}, {8438, 14044},                 \
+    {8192, 14189}, {7943, 14330}, {7692, 14466}, {7438, 14598}, {7182, 14726},                 \
+    {6924, 14849}, {6664, 14968}, {6402, 15082}, {6138, 15191}, {5872, 15296},                 \
+    {5604, 15396}, {5334, 15491}, {5063, 15582}, {4790, 15668}, {4516, 15749},                 \
+    {4240, 15826}, {3964, 15897}, {3686, 15964}, {3406, 16026}, {3126, 16083},                 \
+    {2845, 16135}, {2563, 16182}, {2280, 16225}, {1997, 16262}, {1713, 16294},                 \
+    {1428, 16322}, {1143, 16344}, {857, 16362}, {572, 16374}, {286, 16382}
+
+namespace sdr {
+
+static_assert(sizeof(sdr_footprint_params) == 64, "sdr_footprint_params is 64 bytes");
+static_assert(sizeof(sdr_footprint) == 256, "sdr_footprint is 256 bytes");
+
+constexpr int kFootDirs = 90;
+constexpr int kFootThreads = 256;
+constexpr int kFootWaves = kFootThreads / 64;
+constexpr int kFootPix = 8;  // pixels a thread
+// A region is cut into slices of kFootSlice pixels of its row-major order, a workgroup a slice, as
+// the relief's sweeps are.  Counts and integer extremes only: the slice size does not show.
+constexpr int kFootSlice = kFootThreads * kFootPix;
+constexpr int kFootTile = 16;               // the cell pass: a workgroup a tile of 16 x 16 cells
+constexpr int kFootHalo = kFootTile + 4;    // counts two cells around it
+constexpr int kFootKept = kFootTile + 2;    // kept flags one cell around it
+constexpr int kFootFinish = 128;            // threads of the last launch (>= kFootDirs)
+static_assert(kFootTile * kFootTile == kFootThreads, "a thread a cell of the tile");
+
+__constant__ int c_foot_dirs[kFootDirs][2] = {SDR_FOOT_DIRS};
+
+struct FootBasis {
+    double es[3], et[3], n[3], off;
+};
+
+// A query's state: the setup launch writes all of it.
+struct FootState {
+    FootBasis b;
+    unsigned flags;   // 0, or the flag that refuses the query
+    unsigned cnt[3];  // n_masked, n_valid, n
+    int smin, smax, tmin, tmax;
+    unsigned n_outside, n_raw, n_kept, pad;
+    int ext[kFootDirs][4];  // over the kept cells: min p, max p, min r, max r
+};
+static_assert(sizeof(FootState) == 128 + kFootDirs * 16, "FootState's layout");
+
+__device__ __forceinline__ sdr_segment foot_segment(const sdr_relief_query& q) {
+    return sdr_segment{q.frame, q.x0, q.y0, q.x1, q.y1};
+}
+
+// Setup, a workgroup a query: the checks, the basis, the accumulators at their start values.
+__global__ __launch_bounds__(kFootFinish) void k_foot_setup(int W, int H, int F, int has_labels,
+                                                            const sdr_plane* __restrict__ planes, int NP,
+                                                            const sdr_relief_query* __restrict__ queries,
+                                                            FootState* __restrict__ states) {
+#pragma clang fp contract(off)
+    const int k = blockIdx.x, tid = threadIdx.x;
+    FootState* S = states + k;
+    if (tid < kFootDirs) {
+        S->ext[tid][0] = INT_MAX;
+        S->ext[tid][1] = INT_MIN;
+        S->ext[tid][2] = INT_MAX;
+        S->ext[tid][3] = INT_MIN;
+    }
+    if (tid != 0) return;
+    const sdr_relief_query q = queries[k];
+    unsigned flags = 0;
+    double es[3] = {0, 0, 0}, et[3] = {0, 0, 0}, n[3] = {0, 0, 0}, off = 0;
+    if (!segment_in_range(foot_segment(q), W, H, F) || q.label < -1 || q.label > 255 ||
+        (q.label >= 0 && !has_labels))
+        flags = SDR_FOOTPRINT_OUT_OF_RANGE;
+    else if (q.plane < 0 || q.plane >= NP || !(planes[q.plane].flags & SDR_PLANE_OK))
+        flags = SDR_FOOTPRINT_NO_PLANE;
+    else {
+        const sdr_plane* p = planes + q.plane;
+        n[0] = p->normal[0];
+        n[1] = p->normal[1];
+        n[2] = p->normal[2];
+        off = p->offset;
+        double a, b, c;
+        if (fabs(n[0]) <= fabs(n[1])) {
+            a = 1.0 - n[0] * n[0];
+            b = -(n[0] * n[1]);
+            c = -(n[0] * n[2]);
+        } else {
+            a = -(n[0] * n[1]);
+            b = 1.0 - n[1] * n[1];
+            c = -(n[1] * n[2]);
+        }
+        const double len = sqrt((a * a + b * b) + c * c);
+        es[0] = a / len;
+        es[1] = b / len;
+        es[2] = c / len;
+        et[0] = n[1] * es[2] - n[2] * es[1];
+        et[1] = n[2] * es[0] - n[0] * es[2];
+        et[2] = n[0] * es[1] - n[1] * es[0];
+        for (int i = 0; i < 3; i++)
+            if (!isfinite(es[i]) || !isfinite(et[i])) flags = SDR_FOOTPRINT_NO_PLANE;
+    }
+    for (int i = 0; i < 3; i++) {
+        S->b.es[i] = es[i];
+        S->b.et[i] = et[i];
+        S->b.n[i] = n[i];
+        S->cnt[i] = 0;
+    }
+    S->b.off = off;
+    S->flags = flags;
+    S->smin = S->tmin = INT_MAX;
+    S->smax = S->tmax = INT_MIN;
+    S->n_outside = S->n_raw = S->n_kept = S->pad = 0;
+}
+
+struct FootPix {
+    bool masked, valid, member;
+    int si, ti;
+};
+
+// Pixel (u, v) of the region whose origin (xs, ys) fd, fc and fl point at: the relief's steps 1 to
+// 5, the band of heights, the cell.  Both sweeps repeat it: the same bits in each.
+template <typename T>
+__device__ __forceinline__ FootPix foot_pixel(const T* __restrict__ fd, size_t stride, const float* __restrict__ fc,
+                                              const uint8_t* __restrict__ fl, int W, const Q16& Q,
+                                              const FootBasis& B, const sdr_footprint_params& P, int label, int xs,
+                                              int ys, unsigned u, unsigned v) {
+#pragma clang fp contract(off)
+    FootPix r = {false, false, false, 0, 0};
+    r.masked = label < 0 || fl[(size_t)v * W + u] == (uint8_t)label;
+    if (!r.masked) return r;
+    const float d = load_disp(fd + (size_t)v * stride + u);
+    const float c = fc ? fc[(size_t)v * W + u] : 0.f;
+    r.valid = isfinite(d) && d > P.min_disp && (!fc || c >= P.conf_min);  // a NaN confidence fails
+    if (!r.valid) return r;
+    float xyz[3];
+    reproject_px(Q, xs + (int)u, ys + (int)v, (double)d, 0.0, 0, xyz);
+    const double X = (double)xyz[0], Y = (double)xyz[1], Z = (double)xyz[2];
+    const double h = ((B.n[0] * X + B.n[1] * Y) + B.n[2] * Z) + B.off;
+    const float hf = (float)h + 0.0f;
+    if (!(finite3(xyz) && fabsf(hf) < 1048576.0f)) return r;
+    if (!(P.h_lo <= hf && hf <= P.h_hi)) return r;
+    const double s = (B.es[0] * X + B.es[1] * Y) + B.es[2] * Z;
+    const double t = (B.et[0] * X + B.et[1] * Y) + B.et[2] * Z;
+    const double qs = s / (double)P.cell, qt = t / (double)P.cell;
+    if (!(fabs(qs) < 1073741824.0 && fabs(qt) < 1073741824.0)) return r;
+    r.si = (int)floor(qs);  // in [-2^30, 2^30)
+    r.ti = (int)floor(qt);
+    r.member = true;
+    return r;
+}
+
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// One sweep over the queries' pixels: grid (slices of a W x H frame, queries).  Pass 1 counts the
+// masked, valid and member pixels and takes the extremes of the members' cells; pass 2 recomputes
+// the members and adds each to its cell of the query's G x G grid (cleared before), or to n_outside.
+// A refused query and a slice past the area leave at once (block-uniform).
+template <typename T, int PASS>
+__global__ __launch_bounds__(kFootThreads) void k_foot_sweep(
+    const T* __restrict__ disp, size_t stride, size_t fstride, int W, int H, int F, const float* __restrict__ conf,
+    const uint8_t* __restrict__ labels, Q16 Q, sdr_footprint_params P, const sdr_relief_query* __restrict__ queries,
+    FootState* __restrict__ states, unsigned* __restrict__ grids) {
+    __shared__ int red[kFootWaves][8];
+    const int k = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    FootState* S = states + k;
+    if (S->flags) return;                    // block-uniform
+    if (PASS == 2 && S->cnt[2] == 0) return;  // no member
+    const sdr_relief_query q = queries[k];
+    const PlaneRect R = plane_rect(foot_segment(q));
+    const unsigned area = (unsigned)R.rw * (unsigned)R.rh;  // <= W * H <= 2^24
+    const unsigned base = blockIdx.x * (unsigned)kFootSlice;
+    if (base >= area) return;
+    const FootBasis B = S->b;
+    const int si0 = PASS == 2 ? S->smin : 0, ti0 = PASS == 2 ? S->tmin : 0;  // pass 1 is complete
+    const unsigned G = (unsigned)P.grid;
+
+    const size_t org = (size_t)R.ys * W + (size_t)R.xs;
+    const T* fd = disp + (size_t)q.frame * fstride + (size_t)R.ys * stride + (size_t)R.xs;
+    const float* fc = conf ? conf + (size_t)q.frame * H * W + org : nullptr;
+    const uint8_t* fl = labels ? labels + (size_t)q.frame * H * W + org : nullptr;
+    unsigned* g = grids + (size_t)k * G * G;
+
+    int m[3] = {0, 0, 0};
+    int smin = INT_MAX, smax = INT_MIN, tmin = INT_MAX, tmax = INT_MIN;
+    int outside = 0;
+#pragma unroll
+    for (int j = 0; j < kFootPix; j++) {
+        const unsigned p = base + (unsigned)(j * kFootThreads + tid);
+        if (p >= area) continue;
+        const unsigned v = p / (unsigned)R.rw, u = p - v * (unsigned)R.rw;
+        const FootPix px = foot_pixel(fd, stride, fc, fl, W, Q, B, P, q.label, R.xs, R.ys, u, v);
+        if (PASS == 1) {
+            m[0] += px.masked ? 1 : 0;
+            m[1] += px.valid ? 1 : 0;
+            if (!px.member) continue;
+            m[2] += 1;
+            smin = min(smin, px.si);
+            smax = max(smax, px.si);
+            tmin = min(tmin, px.ti);
+            tmax = max(tmax, px.ti);
+        } else {
+            if (!px.member) continue;
+            // both differences are in [0, 2^31): unsigned, and a value below G indexes the grid
+            const unsigned di = (unsigned)px.si - (unsigned)si0, dj = (unsigned)px.ti - (unsigned)ti0;
+            if (di < G && dj < G)
+                atomicAdd(g + (size_t)di * G + dj, 1u);
+            else
+                outside += 1;
+        }
+    }
+    if constexpr (PASS == 1) {
+        int w[7];
+        w[0] = (int)wave_sum((long long)m[0]);
+        w[1] = (int)wave_sum((long long)m[1]);
+        w[2] = (int)wave_sum((long long)m[2]);
+        w[3] = wave_min(smin);
+        w[4] = wave_max(smax);
+        w[5] = wave_min(tmin);
+        w[6] = wave_max(tmax);
+        if (lane == 0)
+            for (int i = 0; i < 7; i++) red[wave][i] = w[i];
+        __syncthreads();
+        if (tid < 7) {
+            int a = red[0][tid];
+            for (int x = 1; x < kFootWaves; x++) {
+                const int b = red[x][tid];
+                a = tid < 3 ? a + b : ((tid == 3 || tid == 5) ? min(a, b) : max(a, b));
+            }
+            if (tid < 3) {
+                if (a) atomicAdd(&S->cnt[tid], (unsigned)a);
+            } else if (tid == 3) {
+                if (a != INT_MAX) atomicMin(&S->smin, a);
+            } else if (tid == 4) {
+                if (a != INT_MIN) atomicMax(&S->smax, a);
+            } else if (tid == 5) {
+                if (a != INT_MAX) atomicMin(&S->tmin, a);
+            } else {
+                if (a != INT_MIN) atomicMax(&S->tmax, a);
+            }
+        }
+    } else {
+        const int o = (int)wave_sum((long long)outside);
+        if (lane == 0) red[wave][0] = o;
+        __syncthreads();
+        if (tid == 0) {
+            int a = 0;
+            for (int x = 0; x < kFootWaves; x++) a += red[x][0];
+            if (a) atomicAdd(&S->n_outside, (unsigned)a);
+        }
+    }
+}
+
+// The pass over the cells: grid (tiles of 16 x 16 cells along j, along i, queries).  The counts of
+// the tile and two cells around it go to LDS, the kept flags of the tile and one cell around it
+// follow from them, and the tile's kept cells that have a neighbour (of the four) that is not kept
+// are compacted into a list: c_k > 0 for every k, so for a kept cell whose four neighbours are
+// kept each of the four extremes is reached by a neighbour too, and skipping it is exact.  Lane k
+// of the first 90 threads then walks the list (broadcast LDS reads) with its direction and adds
+// its four extremes to the query's with one atomic each.
+__global__ __launch_bounds__(kFootThreads) void k_foot_cells(sdr_footprint_params P,
+                                                             FootState* __restrict__ states,
+                                                             const unsigned* __restrict__ grids) {
+    __shared__ unsigned cnt[kFootHalo][kFootHalo + 1];
+    __shared__ unsigned char kept[kFootKept][kFootKept + 2];
+    __shared__ unsigned list[kFootThreads];
+    __shared__ unsigned tot[3];  // raw, kept, listed
+    const int k = blockIdx.z, tid = threadIdx.x, lane = tid & 63;
+    FootState* S = states + k;
+    if (S->flags || S->cnt[2] == 0) return;  // block-uniform
+    const int G = P.grid;
+    const int i0 = (int)blockIdx.y * kFootTile, j0 = (int)blockIdx.x * kFootTile;
+    // the members' cells end at the spans (each at least 1, in int64: up to 2^31)
+    const long long span_s = (long long)S->smax - (long long)S->smin + 1;
+    const long long span_t = (long long)S->tmax - (long long)S->tmin + 1;
+    if (i0 >= span_s || j0 >= span_t) return;  // an empty tile keeps no cell (block-uniform)
+    const unsigned* g = grids + (size_t)k * (size_t)G * (size_t)G;
+    if (tid < 3) tot[tid] = 0;
+    for (int x = tid; x < kFootHalo * kFootHalo; x += kFootThreads) {
+        const int li = x / kFootHalo, lj = x - li * kFootHalo;
+        const int gi = i0 + li - 2, gj = j0 + lj - 2;
+        cnt[li][lj] = (gi >= 0 && gi < G && gj >= 0 && gj < G) ? g[(size_t)gi * G + gj] : 0u;
+    }
+    __syncthreads();
+    for (int x = tid; x < kFootKept * kFootKept; x += kFootThreads) {
+        const int li = x / kFootKept, lj = x - li * kFootKept;  // cnt's (li + 1, lj + 1)
+        unsigned sum = 0;  // at most 2^24 members a query
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+            for (int b = 0; b < 3; b++) sum += cnt[li + a][lj + b];
+        kept[li][lj] = (cnt[li + 1][lj + 1] >= 1u && sum >= (unsigned)P.support) ? 1 : 0;
+    }
+    __syncthreads();
+    const int li = tid >> 4, lj = tid & 15;
+    const bool raw = cnt[li + 2][lj + 2] >= 1u;  // a cell outside the grid holds 0
+    const bool kp = kept[li + 1][lj + 1] != 0;
+    const bool edge = kp && !(kept[li][lj + 1] && kept[li + 2][lj + 1] && kept[li + 1][lj] && kept[li + 1][lj + 2]);
+    const unsigned long long braw = __ballot(raw), bkept = __ballot(kp), bedge = __ballot(edge);
+    unsigned at = 0;
+    if (lane == 0) {
+        if (braw) atomicAdd(&tot[0], (unsigned)__popcll(braw));
+        if (bkept) atomicAdd(&tot[1], (unsigned)__popcll(bkept));
+        if (bedge) at = atomicAdd(&tot[2], (unsigned)__popcll(bedge));
+    }
+    at = (unsigned)__shfl((int)at, 0, 64);
+    if (edge)  // at most kFootThreads entries: one a thread
+        list[at + (unsigned)__popcll(bedge & ((1ull << lane) - 1ull))] = ((unsigned)(i0 + li) << 16) | (unsigned)(j0 + lj);
+    __syncthreads();
+    if (tid == 0) {
+        if (tot[0]) atomicAdd(&S->n_raw, tot[0]);
+        if (tot[1]) atomicAdd(&S->n_kept, tot[1]);
+    }
+    const int nl = (int)tot[2];
+    if (tid >= kFootDirs || nl == 0) return;
+    const int c = c_foot_dirs[tid][0], s = c_foot_dirs[tid][1];
+    int pmin = INT_MAX, pmax = INT_MIN, rmin = INT_MAX, rmax = INT_MIN;
+    for (int x = 0; x < nl; x++) {
+        const unsigned e = list[x];
+        const int i = (int)(e >> 16), j = (int)(e & 0xffffu);
+        const int p = c * i + s * j, r = c * j - s * i;  // below 2^25
+        pmin = min(pmin, p);
+        pmax = max(pmax, p);
+        rmin = min(rmin, r);
+        rmax = max(rmax, r);
+    }
+    atomicMin(&S->ext[tid][0], pmin);
+    atomicMax(&S->ext[tid][1], pmax);
+    atomicMin(&S->ext[tid][2], rmin);
+    atomicMax(&S->ext[tid][3], rmax);
+}
+
+__device__ __forceinline__ int foot_sat(long long v) {
+    return v > (long long)INT_MAX ? INT_MAX : (int)v;
+}
+
+// The record, a workgroup a query: the area of each direction's rectangle, the smallest one, the
+// sides, the fill and the corners.
+__global__ __launch_bounds__(kFootFinish) void k_foot_finish(sdr_footprint_params P,
+                                                             const sdr_relief_query* __restrict__ queries,
+                                                             const FootState* __restrict__ states,
+                                                             sdr_footprint* __restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ long long areas[kFootDirs];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const FootState* S = states + k;
+    const bool ran = S->flags == 0;
+    const bool valid = ran && S->n_kept > 0;  // block-uniform
+    if (valid && tid < kFootDirs) {
+        const int c = c_foot_dirs[tid][0], s = c_foot_dirs[tid][1];
+        const int U0 = S->ext[tid][0], U1 = S->ext[tid][1] + c + s;
+        const int V0 = S->ext[tid][2] - s, V1 = S->ext[tid][3] + c;
+        areas[tid] = (long long)(U1 - U0) * (long long)(V1 - V0);
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    const sdr_relief_query q = queries[k];
+    sdr_footprint r;
+    const double nan = __builtin_nan("");
+    r.side[0] = r.side[1] = r.fill = nan;
+    for (int i = 0; i < 3; i++) {
+        for (int x = 0; x < 4; x++) r.corner[x][i] = nan;
+        r.basis_s[i] = r.basis_t[i] = nan;
+    }
+    r.i0 = r.j0 = 0;
+    r.angle_deg = -1;
+    r.span_s = r.span_t = 0;
+    r.area = r.n_masked = r.n_valid = r.n = r.n_outside = r.n_cells_raw = r.n_cells = 0;
+    r.frame = q.frame;
+    r.plane = q.plane;
+    r.label = q.label;
+    r.flags = S->flags;
+    r.reserved[0] = r.reserved[1] = r.reserved[2] = r.reserved[3] = 0;
+    if (S->flags != SDR_FOOTPRINT_OUT_OF_RANGE) {
+        const PlaneRect R = plane_rect(foot_segment(q));
+        r.area = R.rw * R.rh;
+    }
+    if (ran) {
+        r.n_masked = (int)S->cnt[0];
+        r.n_valid = (int)S->cnt[1];
+        r.n = (int)S->cnt[2];
+        r.n_outside = (int)S->n_outside;
+        r.n_cells_raw = (int)S->n_raw;
+        r.n_cells = (int)S->n_kept;
+        if (r.n > 0) {
+            r.i0 = S->smin;
+            r.j0 = S->tmin;
+            r.span_s = foot_sat((long long)S->smax - (long long)S->smin + 1);
+            r.span_t = foot_sat((long long)S->tmax - (long long)S->tmin + 1);
+        }
+        r.flags = (valid ? SDR_FOOTPRINT_VALID : SDR_FOOTPRINT_EMPTY) | (r.n_outside > 0 ? SDR_FOOTPRINT_CLIPPED : 0);
+    }
+    if (valid) {
+        int best = 0;
+        for (int d = 1; d < kFootDirs; d++)
+            if (areas[d] < areas[best]) best = d;
+        const int c = c_foot_dirs[best][0], s = c_foot_dirs[best][1];
+        const int U[2] = {S->ext[best][0], S->ext[best][1] + c + s};
+        const int V[2] = {S->ext[best][2] - s, S->ext[best][3] + c};
+        const double cell = (double)P.cell;
+        const double du = (double)(U[1] - U[0]) / 16384.0, dv = (double)(V[1] - V[0]) / 16384.0;
+        r.angle_deg = best;
+        r.side[0] = canon(du * cell);
+        r.side[1] = canon(dv * cell);
+        r.fill = canon((double)r.n_cells / (du * dv));
+        const double ch = (double)c / 16384.0, sh = (double)s / 16384.0;
+        const int cu[4] = {0, 1, 1, 0}, cv[4] = {0, 0, 1, 1};
+        for (int x = 0; x < 4; x++) {
+            const double a = (double)U[cu[x]] / 16384.0, b = (double)V[cv[x]] / 16384.0;
+            const double gi = ch * a - sh * b, gj = sh * a + ch * b;
+            const double Sx = ((double)S->smin + gi) * cell, Tx = ((double)S->tmin + gj) * cell;
+            for (int i = 0; i < 3; i++) r.corner[x][i] = canon((Sx * S->b.es[i] + Tx * S->b.et[i]) - S->b.off * S->b.n[i]);
+        }
+        for (int i = 0; i < 3; i++) {
+            r.basis_s[i] = S->b.es[i];
+            r.basis_t[i] = S->b.et[i];
+        }
+    }
+    out[k] = r;
+}
+
+}  // namespace sdr
+
+namespace {
+
+using namespace sdr::ruler_host;
+
+const int32_t kFootDirsHost[sdr::kFootDirs][2] = {SDR_FOOT_DIRS};
+
+constexpr int kFootBatch = 256;                          // queries a batch at most
+constexpr size_t kFootGridBytes = (size_t)64 << 20;      // and their grids take at most this
+
+int check_footprint_params(const sdr_footprint_params* p, const void* planes, int P) {
+    if (P < 0 || (P > 0 && !planes)) return rfail(SDR_ERR_ARG, "bad plane count or null planes");
+    if (!(std::isfinite(p->cell) && p->cell >= 0.0625f && p->cell <= 65536.0f))
+        return rfail(SDR_ERR_ARG, "cell must be finite and in 0.0625..65536");
+    if (p->grid < 16 || p->grid > 1024) return rfail(SDR_ERR_ARG, "grid must be in 16..1024");
+    if (p->support < 1 || p->support > 255) return rfail(SDR_ERR_ARG, "support must be in 1..255");
+    if (std::isnan(p->h_lo) || std::isnan(p->h_hi) || p->h_lo > p->h_hi)
+        return rfail(SDR_ERR_ARG, "h_lo and h_hi must not be NaN, and h_lo <= h_hi");
+    for (int i = 0; i < 9; i++)
+        if (p->reserved[i]) return rfail(SDR_ERR_ARG, "reserved fields must be 0");
+    return SDR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void sdr_footprint_params_default(sdr_footprint_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->min_disp = -1.0f;
+    p->conf_min = 0.0f;
+    p->cell = 4.0f;
+    p->h_lo = -1048576.0f;
+    p->h_hi = 1048576.0f;
+    p->grid = 512;
+    p->support = 4;
+}
+
+int sdr_footprint_direction(int k, int32_t* c, int32_t* s) {
+    if (k < 0 || k >= sdr::kFootDirs || !c || !s) return rfail(SDR_ERR_ARG, "direction must be in 0..89");
+    *c = kFootDirsHost[k][0];
+    *s = kFootDirsHost[k][1];
+    return SDR_OK;
+}
+
+int sdr_plane_footprint_device(const void* d_disp, int disp_type, size_t stride, size_t frame_stride, int W, int H,
+                               int F, const float* d_conf, const uint8_t* d_labels, const double Q[16],
+                               const sdr_footprint_params* params, const sdr_plane* d_planes, int P,
+                               const sdr_relief_query* d_queries, int K, sdr_footprint* d_out, void* stream) {
+    int rc = check_plane_maps(d_disp, disp_type, stride, frame_stride, W, H, F, Q, params, d_queries, K, d_out);
+    if (rc || (rc = check_footprint_params(params, d_planes, P))) return rc;
+    if (K == 0) return SDR_OK;
+    hipStream_t st = (hipStream_t)stream;
+    sdr::Q16 q;
+    for (int i = 0; i < 16; i++) q.q[i] = Q[i];
+    const sdr_footprint_params FP = *params;
+    const size_t G = (size_t)FP.grid, gbytes = G * G * sizeof(unsigned);  // 1 KiB .. 4 MiB a query
+    const int KB = std::min(K, std::min(kFootBatch, (int)(kFootGridBytes / gbytes)));  // >= 1
+    // scratch of a batch: {grids, states}
+    const size_t o_st = (size_t)KB * gbytes;
+    char* sc = nullptr;
+    RULER_HIP(sdr::scratch_alloc((void**)&sc, o_st + (size_t)KB * sizeof(sdr::FootState), st));
+    unsigned* grids = (unsigned*)sc;
+    sdr::FootState* states = (sdr::FootState*)(sc + o_st);
+    const unsigned slices = (unsigned)(((size_t)W * H + sdr::kFootSlice - 1) / sdr::kFootSlice);
+    const unsigned tiles = (unsigned)((G + sdr::kFootTile - 1) / sdr::kFootTile);
+    const dim3 block(sdr::kFootThreads), small(sdr::kFootFinish);
+    hipError_t e = hipSuccess;
+    auto batch = [&](auto* disp, int k0, int kb) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(disp)>>;
+        const sdr_relief_query* qs = d_queries + k0;
+        const dim3 sgrid(slices, (unsigned)kb), cgrid(tiles, tiles, (unsigned)kb), pgrid((unsigned)kb);
+        if ((e = hipMemsetAsync(grids, 0, (size_t)kb * gbytes, st)) != hipSuccess) return;
+        hipLaunchKernelGGL(sdr::k_foot_setup, pgrid, small, 0, st, W, H, F, d_labels ? 1 : 0, d_planes, P, qs, states);
+        hipLaunchKernelGGL((sdr::k_foot_sweep<T, 1>), sgrid, block, 0, st, disp, stride, frame_stride, W, H, F, d_conf,
+                           d_labels, q, FP, qs, states, grids);
+        hipLaunchKernelGGL((sdr::k_foot_sweep<T, 2>), sgrid, block, 0, st, disp, stride, frame_stride, W, H, F, d_conf,
+                           d_labels, q, FP, qs, states, grids);
+        hipLaunchKernelGGL(sdr::k_foot_cells, cgrid, block, 0, st, FP, states, (const unsigned*)grids);
+        hipLaunchKernelGGL(sdr::k_foot_finish, pgrid, small, 0, st, FP, qs, (const sdr::FootState*)states,
+                           d_out + k0);
+    };
+    for (int k0 = 0; k0 < K && e == hipSuccess; k0 += KB) {
+        const int kb = std::min(K - k0, KB);
+        if (disp_type == SDR_DISP_F32)
+            batch((const float*)d_disp, k0, kb);
+        else
+            batch((const int16_t*)d_disp, k0, kb);
+    }
+    const hipError_t le = hipGetLastError();
+    RULER_HIP(sdr::scratch_free(sc, st));
+    RULER_HIP(e);
+    RULER_HIP(le);
+    return SDR_OK;
+}
+
+int sdr_plane_footprint(const void* disp, int disp_type, size_t stride, size_t frame_stride, int W, int H, int F,
+                        const float* conf, const uint8_t* labels, const double Q[16],
+                        const sdr_footprint_params* params, const sdr_plane* planes, int P,
+                        const sdr_relief_query* queries, int K, sdr_footprint* out) {
+    int rc = check_plane_maps(disp, disp_type, stride, frame_stride, W, H, F, Q, params, queries, K, out);
+    if (rc || (rc = check_footprint_params(params, planes, P))) return rc;
+    if (K == 0) return SDR_OK;
+    HostState* S = nullptr;
+    if ((rc = host_state(&S))) return rc;
+    const size_t px = (size_t)W * H;
+    // segs: the queries; prof: the labels
+    if ((rc = upload_maps(S, disp, disp_type, stride, frame_stride, W, H, F, conf)) ||
+        (rc = sdr::ensure(S->segs, (size_t)K * sizeof(sdr_relief_query))) ||
+        (rc = sdr::ensure(S->planes, (size_t)P * sizeof(sdr_plane))) ||
+        (rc = sdr::ensure(S->prof, labels ? (size_t)F * px : 0)) ||
+        (rc = sdr::ensure(S->out, (size_t)K * sizeof(sdr_footprint))))
+        return rc;
+    RULER_HIP(hipMemcpyAsync(S->segs.p, queries, (size_t)K * sizeof(sdr_relief_query), hipMemcpyHostToDevice, S->st));
+    if (P) RULER_HIP(hipMemcpyAsync(S->planes.p, planes, (size_t)P * sizeof(sdr_plane), hipMemcpyHostToDevice, S->st));
+    if (labels) RULER_HIP(hipMemcpyAsync(S->prof.p, labels, (size_t)F * px, hipMemcpyHostToDevice, S->st));
+    rc = sdr_plane_footprint_device(S->map.p, disp_type, (size_t)W, px, W, H, F,
+                                    conf ? (const float*)S->conf.p : nullptr,
+                                    labels ? (const uint8_t*)S->prof.p : nullptr, Q, params,
+                                    P ? (const sdr_plane*)S->planes.p : nullptr, P,
+                                    (const sdr_relief_query*)S->segs.p, K, (sdr_footprint*)S->out.p, S->st);
+    if (rc) return rc;
+    RULER_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(sdr_footprint), hipMemcpyDeviceToHost, S->st));
+    RULER_HIP(hipStreamSynchronize(S->st));
+    return SDR_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// sdr_ruler_shared.hpp -- what the ruler's units (sdr_ruler.hip, sdr_relief.hip) share: the device
+// sdr_ruler_shared.hpp -- what the ruler's units (sdr_ruler.hip, sdr_relief.hip, sdr_footprint.hip) share: the device
 // helpers of the region rule, the disparity loads and the canonical NaN, and the host side of the
 // host-pointer calls (the argument guards of the maps, the per-thread persistent buffers).
 #pragma once

@@ -161,6 +161,15 @@ class LiveLoop:
         return self.ruler.relief_device(self.disp, planes, regions, labels=labels, conf=self.conf,
                                         quantiles=quantiles, band=band, stream=stream)
 
+    def footprint(self, planes, regions, stream, labels=None, cell: float = 4.0, grid: int = 512, support: int = 4,
+                  h_range=None):
+        """Ruler.footprint_device on the same frames, chained like relief(): the (K, 256) footprint
+        records tensor, no synchronise in between."""
+        if self.ruler is None:
+            raise RuntimeError("LiveLoop was built without ruler=")
+        return self.ruler.footprint_device(self.disp, planes, regions, labels=labels, conf=self.conf, cell=cell,
+                                           grid=grid, support=support, h_range=h_range, stream=stream)
+
     def close(self):
         for o in (self.left, self.right, self.wls, self.display):
             if o is not None:

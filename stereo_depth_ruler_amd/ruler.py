@@ -17,6 +17,11 @@ engine (csrc/sdr_ruler.hip; the definition is in include/sdr/sdr.h).
   the heights of a rectangle's pixels (optionally only those with one label of ``find_planes``' map)
   above a plane record, as counts, extremes, exact means and order statistics (a radix selection on
   the device, csrc/sdr_relief.hip): the height of a box above the table, the depth of a step.
+* ``Ruler.footprint(disparity, planes, regions, labels=None)`` measures a surface IN a plane: the
+  pixels of a rectangle (optionally one label, optionally a band of heights) binned on square cells
+  of the plane, stray cells dropped by a 3 x 3 support rule, and the minimum-area bounding rectangle
+  over 90 whole-degree directions (csrc/sdr_footprint.hip): the length and width of a box on a
+  table at whatever angle it lies, with its four 3-D corners.
 * ``Ruler.find_planes(disparity, region=None)`` finds a region's dominant planes without a prior (a
   box on a table in front of a wall): rounds of seeded three-point hypotheses scored in exact
   integer arithmetic on the pixels no earlier plane has claimed, the winner refitted as
@@ -37,8 +42,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (DISP_F32, DISP_S16, PlaneParams, PlaneSearchParams, ReliefParams, RulerParams, SDRError, check,
-                   lib)
+from ._lib import (DISP_F32, DISP_S16, FootprintParams, PlaneParams, PlaneSearchParams, ReliefParams, RulerParams,
+                   SDRError, check, lib)
 from .sgbm import _Q, _is_cuda, torch
 
 MEASUREMENT_DTYPE = np.dtype([
@@ -80,6 +85,23 @@ RELIEF_DTYPE = np.dtype([
     ("plane", "<i4"), ("label", "<i4"), ("flags", "<u4"), ("reserved", "<i4", (3,))])
 assert RELIEF_DTYPE.itemsize == 128
 RELIEF_VALID, RELIEF_OUT_OF_RANGE, RELIEF_NO_PLANE, RELIEF_EMPTY = 1, 2, 4, 8
+
+
+# sdr_footprint and its flags (SDR_FOOTPRINT_*)
+FOOTPRINT_DTYPE = np.dtype([
+    ("side", "<f8", (2,)), ("fill", "<f8"), ("corner", "<f8", (4, 3)), ("basis_s", "<f8", (3,)),
+    ("basis_t", "<f8", (3,)), ("i0", "<i8"), ("j0", "<i8"), ("angle_deg", "<i4"), ("span_s", "<i4"),
+    ("span_t", "<i4"), ("area", "<i4"), ("n_masked", "<i4"), ("n_valid", "<i4"), ("n", "<i4"),
+    ("n_outside", "<i4"), ("n_cells_raw", "<i4"), ("n_cells", "<i4"), ("frame", "<i4"), ("plane", "<i4"),
+    ("label", "<i4"), ("flags", "<u4"), ("reserved", "<i4", (4,))])
+assert FOOTPRINT_DTYPE.itemsize == 256
+FOOTPRINT_VALID, FOOTPRINT_OUT_OF_RANGE, FOOTPRINT_NO_PLANE, FOOTPRINT_EMPTY, FOOTPRINT_CLIPPED = 1, 2, 4, 8, 16
+
+
+def footprint_length_width(records):
+    """(length, width) = (max, min) of each FOOTPRINT_DTYPE record's sides (NaN without a rectangle)."""
+    side = np.asarray(records)["side"]
+    return side.max(axis=-1), side.min(axis=-1)
 
 
 def as_relief_queries(regions) -> np.ndarray:
@@ -645,6 +667,103 @@ class Ruler:
             K = qs.shape[0]
             out = torch.empty((K, 128), dtype=torch.uint8, device=dev)
             check(lib().sdr_plane_relief_device(
+                d.data_ptr(), DISP_F32 if d.dtype == torch.float32 else DISP_S16, d.stride(1),
+                d.stride(1) * H if F == 1 else d.stride(0), W, H, F,
+                conf.data_ptr() if conf is not None else None, lab.data_ptr() if lab is not None else None,
+                _Q(self.Q), ctypes.byref(p), pl.data_ptr() if P else None, P,
+                qs.data_ptr() if K else None, K, out.data_ptr() if K else None,
+                ctypes.c_void_p(s.cuda_stream)))
+        return out
+
+    # ---- the footprint of a region (sdr.h, "the footprint of a region") ----
+    def _footprint_params(self, cell, grid, support, h_range) -> FootprintParams:
+        lo, hi = (-1048576.0, 1048576.0) if h_range is None else (float(h_range[0]), float(h_range[1]))
+        cell = float(cell)
+        if not (np.isfinite(cell) and 0.0625 <= cell <= 65536.0):
+            raise SDRError(-1, "cell must be finite and in 0.0625..65536")
+        if int(grid) != grid or not 16 <= grid <= 1024:
+            raise SDRError(-1, "grid must be an integer in 16..1024")
+        if int(support) != support or not 1 <= support <= 255:
+            raise SDRError(-1, "support must be an integer in 1..255")
+        if np.isnan(lo) or np.isnan(hi) or lo > hi:
+            raise SDRError(-1, "h_range must be (lo, hi) with lo <= hi, neither NaN")
+        return FootprintParams(self.min_disp, self.conf_min, cell, lo, hi, int(grid), int(support))
+
+    def footprint(self, disparity, planes, regions, labels=None, conf=None, cell: float = 4.0, grid: int = 512,
+                  support: int = 4, h_range=None):
+        """The oriented bounding rectangles of K rectangles' pixels in plane records' planes: a
+        FOOTPRINT_DTYPE array of K.  planes, regions and labels: as relief() takes them; cell: the
+        side of a grid cell in Q's units; grid: cells a side (members beyond it set
+        FOOTPRINT_CLIPPED); support: the members a kept cell's 3 x 3 neighbourhood must hold;
+        h_range: (lo, hi), only pixels whose height above the plane lies in it."""
+        if _is_cuda(disparity):
+            out = self.footprint_device(disparity, planes, regions, labels, conf, cell, grid, support, h_range)
+            return out.cpu().numpy().reshape(-1).view(FOOTPRINT_DTYPE)
+        p = self._footprint_params(cell, grid, support, h_range)
+        if _is_cuda(planes):
+            planes = planes.cpu().numpy()
+        pl = np.ascontiguousarray(planes).reshape(-1).view(np.uint8).view(PLANE_DTYPE)
+        d, c, rs, fs = self._host_maps(disparity, conf)
+        F, H, W = d.shape
+        lab = None
+        if labels is not None:
+            if _is_cuda(labels):
+                labels = labels.cpu().numpy()
+            lab = np.asarray(labels)
+            if lab.dtype != np.uint8:
+                raise SDRError(-5, "labels must be uint8")
+            lab = np.ascontiguousarray(_frames3(lab, "labels"))
+            if lab.shape != d.shape:
+                raise SDRError(-1, "labels must have the disparity's shape")
+        qs = as_relief_queries(regions)
+        K, P = qs.shape[0], pl.shape[0]
+        out = np.zeros(K, FOOTPRINT_DTYPE)
+        with _on_device(self.device):
+            rc = lib().sdr_plane_footprint(
+                d.ctypes.data, DISP_F32 if d.dtype == np.float32 else DISP_S16, rs, fs, W, H, F,
+                c.ctypes.data if c is not None else None, lab.ctypes.data if lab is not None else None,
+                _Q(self.Q), ctypes.byref(p), pl.ctypes.data if P else None, P,
+                qs.ctypes.data if K else None, K, out.ctypes.data if K else None)
+        check(rc)
+        return out
+
+    def footprint_device(self, disparity, planes, regions, labels=None, conf=None, cell: float = 4.0,
+                         grid: int = 512, support: int = 4, h_range=None, stream=None):
+        """Enqueues the footprints on `stream` (default: the current stream) and returns a uint8
+        tensor (K, 256) without synchronising (view its host copy as FOOTPRINT_DTYPE).  The argument
+        forms are relief_device's."""
+        if not _is_cuda(disparity):
+            raise SDRError(-5, "footprint_device expects a CUDA float32 or int16 tensor")
+        p = self._footprint_params(cell, grid, support, h_range)
+        dev = disparity.device
+        s = stream if stream is not None else torch.cuda.current_stream(dev.index)
+        with torch.cuda.stream(s):
+            d, conf = self._device_maps(disparity, conf)
+            F, H, W = d.shape
+            if _is_cuda(planes):
+                if planes.dtype != torch.uint8 or planes.numel() % 128:
+                    raise SDRError(-5, "device planes must be a uint8 tensor (P, 128)")
+                pl = planes.contiguous()
+                P = pl.numel() // 128
+            else:
+                host = np.ascontiguousarray(planes).reshape(-1).view(np.uint8).reshape(-1, 128)
+                P = host.shape[0]
+                pl = torch.from_numpy(host.copy()).to(dev) if P else None
+            lab = None
+            if labels is not None:
+                lab = labels if _is_cuda(labels) else torch.from_numpy(np.ascontiguousarray(labels)).to(dev)
+                if lab.dtype != torch.uint8 or lab.numel() != d.numel():
+                    raise SDRError(-5, "labels must be a uint8 map of the disparity's shape")
+                lab = lab.contiguous()
+            if _is_cuda(regions):
+                if regions.dtype != torch.int32 or regions.dim() != 2 or regions.shape[1] != 8:
+                    raise SDRError(-5, "device regions must be an int32 tensor (K, 8)")
+                qs = regions.contiguous()
+            else:
+                qs = self._upload_segments(as_relief_queries(regions), dev, s)
+            K = qs.shape[0]
+            out = torch.empty((K, 256), dtype=torch.uint8, device=dev)
+            check(lib().sdr_plane_footprint_device(
                 d.data_ptr(), DISP_F32 if d.dtype == torch.float32 else DISP_S16, d.stride(1),
                 d.stride(1) * H if F == 1 else d.stride(0), W, H, F,
                 conf.data_ptr() if conf is not None else None, lab.data_ptr() if lab is not None else None,
