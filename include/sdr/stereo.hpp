@@ -608,9 +608,7 @@ public:
                                const Mat* conf = nullptr, const std::vector<int>& quantiles = {50, 500, 950},
                                float band = 0.0f) const {
         check_maps(disparity, conf, "relief");
-        if (labels && (labels->type != CV_8UC1 || labels->rows != disparity.rows || labels->cols != disparity.cols ||
-                       labels->step != (size_t)labels->cols))
-            throw Exception(SDR_ERR_TYPE, "labels must be a continuous CV_8U map of the disparity's size");
+        check_labels(disparity, labels);
         if (quantiles.size() > 8) throw Exception(SDR_ERR_ARG, "relief takes at most 8 quantiles");
         const size_t es = elem_size(disparity.type);
         sdr_relief_params rp;
@@ -644,9 +642,7 @@ public:
                                      const Mat* conf = nullptr, float cell = 4.0f, int grid = 512, int support = 4,
                                      float h_lo = -1048576.0f, float h_hi = 1048576.0f) const {
         check_maps(disparity, conf, "footprint");
-        if (labels && (labels->type != CV_8UC1 || labels->rows != disparity.rows || labels->cols != disparity.cols ||
-                       labels->step != (size_t)labels->cols))
-            throw Exception(SDR_ERR_TYPE, "labels must be a continuous CV_8U map of the disparity's size");
+        check_labels(disparity, labels);
         const size_t es = elem_size(disparity.type);
         sdr_footprint_params fp;
         sdr_footprint_params_default(&fp);
@@ -673,6 +669,11 @@ public:
     }
 
 private:
+    static void check_labels(const Mat& disparity, const Mat* labels) {
+        if (labels && (labels->type != CV_8UC1 || labels->rows != disparity.rows || labels->cols != disparity.cols ||
+                       labels->step != (size_t)labels->cols))
+            throw Exception(SDR_ERR_TYPE, "labels must be a continuous CV_8U map of the disparity's size");
+    }
     static void check_maps(const Mat& disparity, const Mat* conf, const char* what) {
         if (disparity.type != CV_32FC1 && disparity.type != CV_16SC1)
             throw Exception(SDR_ERR_TYPE, std::string(what) + " expects a CV_32F or CV_16S disparity");

@@ -14,6 +14,7 @@
 
 #include "sdr_device.hpp"
 #include "sdr_internal.hpp"
+#include "sdr_region.hpp"
 #include "sdr_ruler_shared.hpp"
 
 // c_k = lrint(16384 * cos(k deg)), s_k = lrint(16384 * sin(k deg)), k = 0..89
@@ -43,22 +44,17 @@ static_assert(sizeof(sdr_footprint_params) == 64, "sdr_footprint_params is 64 by
 static_assert(sizeof(sdr_footprint) == 256, "sdr_footprint is 256 bytes");
 
 constexpr int kFootDirs = 90;
-constexpr int kFootThreads = 256;
-constexpr int kFootWaves = kFootThreads / 64;
-constexpr int kFootPix = 8;  // pixels a thread
-// A region is cut into slices of kFootSlice pixels of its row-major order, a workgroup a slice, as
-// the relief's sweeps are.  Counts and integer extremes only: the slice size does not show.
-constexpr int kFootSlice = kFootThreads * kFootPix;
 constexpr int kFootTile = 16;               // the cell pass: a workgroup a tile of 16 x 16 cells
 constexpr int kFootHalo = kFootTile + 4;    // counts two cells around it
 constexpr int kFootKept = kFootTile + 2;    // kept flags one cell around it
 constexpr int kFootFinish = 128;            // threads of the last launch (>= kFootDirs)
-static_assert(kFootTile * kFootTile == kFootThreads, "a thread a cell of the tile");
+static_assert(kFootTile * kFootTile == kRegionThreads, "a thread a cell of the tile");
 
 __constant__ int c_foot_dirs[kFootDirs][2] = {SDR_FOOT_DIRS};
 
 struct FootBasis {
-    double es[3], et[3], n[3], off;
+    double es[3], et[3];
+    RegionPlane pl;
 };
 
 // A query's state: the setup launch writes all of it.
@@ -71,10 +67,6 @@ struct FootState {
     int ext[kFootDirs][4];  // over the kept cells: min p, max p, min r, max r
 };
 static_assert(sizeof(FootState) == 128 + kFootDirs * 16, "FootState's layout");
-
-__device__ __forceinline__ sdr_segment foot_segment(const sdr_relief_query& q) {
-    return sdr_segment{q.frame, q.x0, q.y0, q.x1, q.y1};
-}
 
 // Setup, a workgroup a query: the checks, the basis, the accumulators at their start values.
 __global__ __launch_bounds__(kFootFinish) void k_foot_setup(int W, int H, int F, int has_labels,
@@ -92,19 +84,11 @@ __global__ __launch_bounds__(kFootFinish) void k_foot_setup(int W, int H, int F,
     }
     if (tid != 0) return;
     const sdr_relief_query q = queries[k];
-    unsigned flags = 0;
-    double es[3] = {0, 0, 0}, et[3] = {0, 0, 0}, n[3] = {0, 0, 0}, off = 0;
-    if (!segment_in_range(foot_segment(q), W, H, F) || q.label < -1 || q.label > 255 ||
-        (q.label >= 0 && !has_labels))
-        flags = SDR_FOOTPRINT_OUT_OF_RANGE;
-    else if (q.plane < 0 || q.plane >= NP || !(planes[q.plane].flags & SDR_PLANE_OK))
-        flags = SDR_FOOTPRINT_NO_PLANE;
-    else {
-        const sdr_plane* p = planes + q.plane;
-        n[0] = p->normal[0];
-        n[1] = p->normal[1];
-        n[2] = p->normal[2];
-        off = p->offset;
+    double es[3] = {0, 0, 0}, et[3] = {0, 0, 0};
+    RegionPlane pl = {{0, 0, 0}, 0};
+    unsigned flags = region_refusal(q, W, H, F, has_labels != 0, planes, NP, &pl);
+    if (!flags) {
+        const double* n = pl.n;
         double a, b, c;
         if (fabs(n[0]) <= fabs(n[1])) {
             a = 1.0 - n[0] * n[0];
@@ -128,10 +112,9 @@ __global__ __launch_bounds__(kFootFinish) void k_foot_setup(int W, int H, int F,
     for (int i = 0; i < 3; i++) {
         S->b.es[i] = es[i];
         S->b.et[i] = et[i];
-        S->b.n[i] = n[i];
         S->cnt[i] = 0;
     }
-    S->b.off = off;
+    S->b.pl = pl;
     S->flags = flags;
     S->smin = S->tmin = INT_MAX;
     S->smax = S->tmax = INT_MIN;
@@ -143,28 +126,19 @@ struct FootPix {
     int si, ti;
 };
 
-// Pixel (u, v) of the region whose origin (xs, ys) fd, fc and fl point at: the relief's steps 1 to
-// 5, the band of heights, the cell.  Both sweeps repeat it: the same bits in each.
+// Pixel (u, v) of the slice's region: the region rule's member, the band of heights, the cell.
+// Both sweeps repeat it: the same bits in each.
 template <typename T>
-__device__ __forceinline__ FootPix foot_pixel(const T* __restrict__ fd, size_t stride, const float* __restrict__ fc,
-                                              const uint8_t* __restrict__ fl, int W, const Q16& Q,
-                                              const FootBasis& B, const sdr_footprint_params& P, int label, int xs,
-                                              int ys, unsigned u, unsigned v) {
+__device__ __forceinline__ FootPix foot_pixel(const RegionSlice<T, const uint8_t>& sl, size_t stride, int W,
+                                              const Q16& Q, const FootBasis& B, const sdr_footprint_params& P,
+                                              int label, unsigned u, unsigned v) {
 #pragma clang fp contract(off)
-    FootPix r = {false, false, false, 0, 0};
-    r.masked = label < 0 || fl[(size_t)v * W + u] == (uint8_t)label;
-    if (!r.masked) return r;
-    const float d = load_disp(fd + (size_t)v * stride + u);
-    const float c = fc ? fc[(size_t)v * W + u] : 0.f;
-    r.valid = isfinite(d) && d > P.min_disp && (!fc || c >= P.conf_min);  // a NaN confidence fails
-    if (!r.valid) return r;
-    float xyz[3];
-    reproject_px(Q, xs + (int)u, ys + (int)v, (double)d, 0.0, 0, xyz);
-    const double X = (double)xyz[0], Y = (double)xyz[1], Z = (double)xyz[2];
-    const double h = ((B.n[0] * X + B.n[1] * Y) + B.n[2] * Z) + B.off;
-    const float hf = (float)h + 0.0f;
-    if (!(finite3(xyz) && fabsf(hf) < 1048576.0f)) return r;
-    if (!(P.h_lo <= hf && hf <= P.h_hi)) return r;
+    const RegionPix px = region_pixel(sl.fd, stride, sl.fc, sl.fl, W, Q, B.pl, P.min_disp, P.conf_min, label,
+                                      sl.R.xs, sl.R.ys, u, v);
+    FootPix r = {px.masked, px.valid, false, 0, 0};
+    if (!px.member) return r;
+    if (!(P.h_lo <= px.hf && px.hf <= P.h_hi)) return r;
+    const double X = (double)px.xyz[0], Y = (double)px.xyz[1], Z = (double)px.xyz[2];
     const double s = (B.es[0] * X + B.es[1] * Y) + B.es[2] * Z;
     const double t = (B.et[0] * X + B.et[1] * Y) + B.et[2] * Z;
     const double qs = s / (double)P.cell, qt = t / (double)P.cell;
@@ -175,67 +149,47 @@ __device__ __forceinline__ FootPix foot_pixel(const T* __restrict__ fd, size_t s
     return r;
 }
 
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // One sweep over the queries' pixels: grid (slices of a W x H frame, queries).  Pass 1 counts the
 // masked, valid and member pixels and takes the extremes of the members' cells; pass 2 recomputes
 // the members and adds each to its cell of the query's G x G grid (cleared before), or to n_outside.
 // A refused query and a slice past the area leave at once (block-uniform).
 template <typename T, int PASS>
-__global__ __launch_bounds__(kFootThreads) void k_foot_sweep(
+__global__ __launch_bounds__(kRegionThreads) void k_foot_sweep(
     const T* __restrict__ disp, size_t stride, size_t fstride, int W, int H, int F, const float* __restrict__ conf,
     const uint8_t* __restrict__ labels, Q16 Q, sdr_footprint_params P, const sdr_relief_query* __restrict__ queries,
     FootState* __restrict__ states, unsigned* __restrict__ grids) {
-    __shared__ int red[kFootWaves][8];
+    __shared__ int red[kRegionWaves][8];
     const int k = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     FootState* S = states + k;
     if (S->flags) return;                    // block-uniform
     if (PASS == 2 && S->cnt[2] == 0) return;  // no member
     const sdr_relief_query q = queries[k];
-    const PlaneRect R = plane_rect(foot_segment(q));
-    const unsigned area = (unsigned)R.rw * (unsigned)R.rh;  // <= W * H <= 2^24
-    const unsigned base = blockIdx.x * (unsigned)kFootSlice;
-    if (base >= area) return;
+    RegionSlice<T, const uint8_t> sl;
+    if (!region_slice(region_segment(q), disp, stride, fstride, W, H, conf,
+                      labels ? labels + (size_t)q.frame * H * W : nullptr, &sl))
+        return;
     const FootBasis B = S->b;
     const int si0 = PASS == 2 ? S->smin : 0, ti0 = PASS == 2 ? S->tmin : 0;  // pass 1 is complete
     const unsigned G = (unsigned)P.grid;
-
-    const size_t org = (size_t)R.ys * W + (size_t)R.xs;
-    const T* fd = disp + (size_t)q.frame * fstride + (size_t)R.ys * stride + (size_t)R.xs;
-    const float* fc = conf ? conf + (size_t)q.frame * H * W + org : nullptr;
-    const uint8_t* fl = labels ? labels + (size_t)q.frame * H * W + org : nullptr;
     unsigned* g = grids + (size_t)k * G * G;
 
     int m[3] = {0, 0, 0};
     int smin = INT_MAX, smax = INT_MIN, tmin = INT_MAX, tmax = INT_MIN;
     int outside = 0;
-#pragma unroll
-    for (int j = 0; j < kFootPix; j++) {
-        const unsigned p = base + (unsigned)(j * kFootThreads + tid);
-        if (p >= area) continue;
-        const unsigned v = p / (unsigned)R.rw, u = p - v * (unsigned)R.rw;
-        const FootPix px = foot_pixel(fd, stride, fc, fl, W, Q, B, P, q.label, R.xs, R.ys, u, v);
+    sl.each([&](unsigned u, unsigned v) __attribute__((always_inline)) {
+        const FootPix px = foot_pixel(sl, stride, W, Q, B, P, q.label, u, v);
         if (PASS == 1) {
             m[0] += px.masked ? 1 : 0;
             m[1] += px.valid ? 1 : 0;
-            if (!px.member) continue;
+            if (!px.member) return;
             m[2] += 1;
             smin = min(smin, px.si);
             smax = max(smax, px.si);
             tmin = min(tmin, px.ti);
             tmax = max(tmax, px.ti);
         } else {
-            if (!px.member) continue;
+            if (!px.member) return;
             // both differences are in [0, 2^31): unsigned, and a value below G indexes the grid
             const unsigned di = (unsigned)px.si - (unsigned)si0, dj = (unsigned)px.ti - (unsigned)ti0;
             if (di < G && dj < G)
@@ -243,7 +197,7 @@ __global__ __launch_bounds__(kFootThreads) void k_foot_sweep(
             else
                 outside += 1;
         }
-    }
+    });
     if constexpr (PASS == 1) {
         int w[7];
         w[0] = (int)wave_sum((long long)m[0]);
@@ -258,7 +212,7 @@ __global__ __launch_bounds__(kFootThreads) void k_foot_sweep(
         __syncthreads();
         if (tid < 7) {
             int a = red[0][tid];
-            for (int x = 1; x < kFootWaves; x++) {
+            for (int x = 1; x < kRegionWaves; x++) {
                 const int b = red[x][tid];
                 a = tid < 3 ? a + b : ((tid == 3 || tid == 5) ? min(a, b) : max(a, b));
             }
@@ -280,7 +234,7 @@ __global__ __launch_bounds__(kFootThreads) void k_foot_sweep(
         __syncthreads();
         if (tid == 0) {
             int a = 0;
-            for (int x = 0; x < kFootWaves; x++) a += red[x][0];
+            for (int x = 0; x < kRegionWaves; x++) a += red[x][0];
             if (a) atomicAdd(&S->n_outside, (unsigned)a);
         }
     }
@@ -293,12 +247,12 @@ __global__ __launch_bounds__(kFootThreads) void k_foot_sweep(
 // kept each of the four extremes is reached by a neighbour too, and skipping it is exact.  Lane k
 // of the first 90 threads then walks the list (broadcast LDS reads) with its direction and adds
 // its four extremes to the query's with one atomic each.
-__global__ __launch_bounds__(kFootThreads) void k_foot_cells(sdr_footprint_params P,
+__global__ __launch_bounds__(kRegionThreads) void k_foot_cells(sdr_footprint_params P,
                                                              FootState* __restrict__ states,
                                                              const unsigned* __restrict__ grids) {
     __shared__ unsigned cnt[kFootHalo][kFootHalo + 1];
     __shared__ unsigned char kept[kFootKept][kFootKept + 2];
-    __shared__ unsigned list[kFootThreads];
+    __shared__ unsigned list[kRegionThreads];
     __shared__ unsigned tot[3];  // raw, kept, listed
     const int k = blockIdx.z, tid = threadIdx.x, lane = tid & 63;
     FootState* S = states + k;
@@ -311,13 +265,13 @@ __global__ __launch_bounds__(kFootThreads) void k_foot_cells(sdr_footprint_param
     if (i0 >= span_s || j0 >= span_t) return;  // an empty tile keeps no cell (block-uniform)
     const unsigned* g = grids + (size_t)k * (size_t)G * (size_t)G;
     if (tid < 3) tot[tid] = 0;
-    for (int x = tid; x < kFootHalo * kFootHalo; x += kFootThreads) {
+    for (int x = tid; x < kFootHalo * kFootHalo; x += kRegionThreads) {
         const int li = x / kFootHalo, lj = x - li * kFootHalo;
         const int gi = i0 + li - 2, gj = j0 + lj - 2;
         cnt[li][lj] = (gi >= 0 && gi < G && gj >= 0 && gj < G) ? g[(size_t)gi * G + gj] : 0u;
     }
     __syncthreads();
-    for (int x = tid; x < kFootKept * kFootKept; x += kFootThreads) {
+    for (int x = tid; x < kFootKept * kFootKept; x += kRegionThreads) {
         const int li = x / kFootKept, lj = x - li * kFootKept;  // cnt's (li + 1, lj + 1)
         unsigned sum = 0;  // at most 2^24 members a query
 #pragma unroll
@@ -339,7 +293,7 @@ __global__ __launch_bounds__(kFootThreads) void k_foot_cells(sdr_footprint_param
         if (bedge) at = atomicAdd(&tot[2], (unsigned)__popcll(bedge));
     }
     at = (unsigned)__shfl((int)at, 0, 64);
-    if (edge)  // at most kFootThreads entries: one a thread
+    if (edge)  // at most kRegionThreads entries: one a thread
         list[at + (unsigned)__popcll(bedge & ((1ull << lane) - 1ull))] = ((unsigned)(i0 + li) << 16) | (unsigned)(j0 + lj);
     __syncthreads();
     if (tid == 0) {
@@ -407,7 +361,7 @@ __global__ __launch_bounds__(kFootFinish) void k_foot_finish(sdr_footprint_param
     r.flags = S->flags;
     r.reserved[0] = r.reserved[1] = r.reserved[2] = r.reserved[3] = 0;
     if (S->flags != SDR_FOOTPRINT_OUT_OF_RANGE) {
-        const PlaneRect R = plane_rect(foot_segment(q));
+        const PlaneRect R = plane_rect(region_segment(q));
         r.area = R.rw * R.rh;
     }
     if (ran) {
@@ -444,7 +398,7 @@ __global__ __launch_bounds__(kFootFinish) void k_foot_finish(sdr_footprint_param
             const double a = (double)U[cu[x]] / 16384.0, b = (double)V[cv[x]] / 16384.0;
             const double gi = ch * a - sh * b, gj = sh * a + ch * b;
             const double Sx = ((double)S->smin + gi) * cell, Tx = ((double)S->tmin + gj) * cell;
-            for (int i = 0; i < 3; i++) r.corner[x][i] = canon((Sx * S->b.es[i] + Tx * S->b.et[i]) - S->b.off * S->b.n[i]);
+            for (int i = 0; i < 3; i++) r.corner[x][i] = canon((Sx * S->b.es[i] + Tx * S->b.et[i]) - S->b.pl.off * S->b.pl.n[i]);
         }
         for (int i = 0; i < 3; i++) {
             r.basis_s[i] = S->b.es[i];
@@ -466,7 +420,7 @@ constexpr int kFootBatch = 256;                          // queries a batch at m
 constexpr size_t kFootGridBytes = (size_t)64 << 20;      // and their grids take at most this
 
 int check_footprint_params(const sdr_footprint_params* p, const void* planes, int P) {
-    if (P < 0 || (P > 0 && !planes)) return rfail(SDR_ERR_ARG, "bad plane count or null planes");
+    if (int rc = check_planes_arg(planes, P)) return rc;
     if (!(std::isfinite(p->cell) && p->cell >= 0.0625f && p->cell <= 65536.0f))
         return rfail(SDR_ERR_ARG, "cell must be finite and in 0.0625..65536");
     if (p->grid < 16 || p->grid > 1024) return rfail(SDR_ERR_ARG, "grid must be in 16..1024");
@@ -509,8 +463,7 @@ int sdr_plane_footprint_device(const void* d_disp, int disp_type, size_t stride,
     if (rc || (rc = check_footprint_params(params, d_planes, P))) return rc;
     if (K == 0) return SDR_OK;
     hipStream_t st = (hipStream_t)stream;
-    sdr::Q16 q;
-    for (int i = 0; i < 16; i++) q.q[i] = Q[i];
+    const sdr::Q16 q = make_q16(Q);
     const sdr_footprint_params FP = *params;
     const size_t G = (size_t)FP.grid, gbytes = G * G * sizeof(unsigned);  // 1 KiB .. 4 MiB a query
     const int KB = std::min(K, std::min(kFootBatch, (int)(kFootGridBytes / gbytes)));  // >= 1
@@ -520,12 +473,12 @@ int sdr_plane_footprint_device(const void* d_disp, int disp_type, size_t stride,
     RULER_HIP(sdr::scratch_alloc((void**)&sc, o_st + (size_t)KB * sizeof(sdr::FootState), st));
     unsigned* grids = (unsigned*)sc;
     sdr::FootState* states = (sdr::FootState*)(sc + o_st);
-    const unsigned slices = (unsigned)(((size_t)W * H + sdr::kFootSlice - 1) / sdr::kFootSlice);
+    const unsigned slices = sdr::region_slices(W, H);
     const unsigned tiles = (unsigned)((G + sdr::kFootTile - 1) / sdr::kFootTile);
-    const dim3 block(sdr::kFootThreads), small(sdr::kFootFinish);
+    const dim3 block(sdr::kRegionThreads), small(sdr::kFootFinish);
     hipError_t e = hipSuccess;
     auto batch = [&](auto* disp, int k0, int kb) {
-        using T = std::remove_cv_t<std::remove_pointer_t<decltype(disp)>>;
+        using T = disp_elem_t<decltype(disp)>;
         const sdr_relief_query* qs = d_queries + k0;
         const dim3 sgrid(slices, (unsigned)kb), cgrid(tiles, tiles, (unsigned)kb), pgrid((unsigned)kb);
         if ((e = hipMemsetAsync(grids, 0, (size_t)kb * gbytes, st)) != hipSuccess) return;
@@ -538,13 +491,8 @@ int sdr_plane_footprint_device(const void* d_disp, int disp_type, size_t stride,
         hipLaunchKernelGGL(sdr::k_foot_finish, pgrid, small, 0, st, FP, qs, (const sdr::FootState*)states,
                            d_out + k0);
     };
-    for (int k0 = 0; k0 < K && e == hipSuccess; k0 += KB) {
-        const int kb = std::min(K - k0, KB);
-        if (disp_type == SDR_DISP_F32)
-            batch((const float*)d_disp, k0, kb);
-        else
-            batch((const int16_t*)d_disp, k0, kb);
-    }
+    for (int k0 = 0; k0 < K && e == hipSuccess; k0 += KB)
+        with_disp(disp_type, d_disp, [&](auto* disp) { batch(disp, k0, std::min(K - k0, KB)); });
     const hipError_t le = hipGetLastError();
     RULER_HIP(sdr::scratch_free(sc, st));
     RULER_HIP(e);
@@ -556,31 +504,8 @@ int sdr_plane_footprint(const void* disp, int disp_type, size_t stride, size_t f
                         const float* conf, const uint8_t* labels, const double Q[16],
                         const sdr_footprint_params* params, const sdr_plane* planes, int P,
                         const sdr_relief_query* queries, int K, sdr_footprint* out) {
-    int rc = check_plane_maps(disp, disp_type, stride, frame_stride, W, H, F, Q, params, queries, K, out);
-    if (rc || (rc = check_footprint_params(params, planes, P))) return rc;
-    if (K == 0) return SDR_OK;
-    HostState* S = nullptr;
-    if ((rc = host_state(&S))) return rc;
-    const size_t px = (size_t)W * H;
-    // segs: the queries; prof: the labels
-    if ((rc = upload_maps(S, disp, disp_type, stride, frame_stride, W, H, F, conf)) ||
-        (rc = sdr::ensure(S->segs, (size_t)K * sizeof(sdr_relief_query))) ||
-        (rc = sdr::ensure(S->planes, (size_t)P * sizeof(sdr_plane))) ||
-        (rc = sdr::ensure(S->prof, labels ? (size_t)F * px : 0)) ||
-        (rc = sdr::ensure(S->out, (size_t)K * sizeof(sdr_footprint))))
-        return rc;
-    RULER_HIP(hipMemcpyAsync(S->segs.p, queries, (size_t)K * sizeof(sdr_relief_query), hipMemcpyHostToDevice, S->st));
-    if (P) RULER_HIP(hipMemcpyAsync(S->planes.p, planes, (size_t)P * sizeof(sdr_plane), hipMemcpyHostToDevice, S->st));
-    if (labels) RULER_HIP(hipMemcpyAsync(S->prof.p, labels, (size_t)F * px, hipMemcpyHostToDevice, S->st));
-    rc = sdr_plane_footprint_device(S->map.p, disp_type, (size_t)W, px, W, H, F,
-                                    conf ? (const float*)S->conf.p : nullptr,
-                                    labels ? (const uint8_t*)S->prof.p : nullptr, Q, params,
-                                    P ? (const sdr_plane*)S->planes.p : nullptr, P,
-                                    (const sdr_relief_query*)S->segs.p, K, (sdr_footprint*)S->out.p, S->st);
-    if (rc) return rc;
-    RULER_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(sdr_footprint), hipMemcpyDeviceToHost, S->st));
-    RULER_HIP(hipStreamSynchronize(S->st));
-    return SDR_OK;
+    return region_host_call(check_footprint_params, sdr_plane_footprint_device, disp, disp_type, stride, frame_stride,
+                            W, H, F, conf, labels, Q, params, planes, P, queries, K, out);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 
 #include "sdr_device.hpp"
 #include "sdr_internal.hpp"
+#include "sdr_region.hpp"
 #include "sdr_ruler_shared.hpp"
 
 namespace sdr {
@@ -21,13 +22,6 @@ static_assert(sizeof(sdr_relief_query) == 32, "sdr_relief_query is 32 bytes");
 static_assert(sizeof(sdr_relief_params) == 64, "sdr_relief_params is 64 bytes");
 static_assert(sizeof(sdr_relief) == 128, "sdr_relief is 128 bytes");
 
-// A region is cut into slices of kReliefSlice pixels of its row-major order, a workgroup a slice,
-// as the plane fit's sweeps are.  Counts, integer sums, extremes and histogram bins only: neither
-// the slice size nor the order the workgroups finish in shows in the result.
-constexpr int kReliefThreads = 256;
-constexpr int kReliefWaves = kReliefThreads / 64;
-constexpr int kReliefPix = 8;  // pixels a thread
-constexpr int kReliefSlice = kReliefThreads * kReliefPix;
 constexpr int kReliefBins = 2048;      // passes 1 and 2: 11 bits
 constexpr int kReliefLastBins = 1024;  // pass 3: 10 bits
 constexpr int kReliefQ = 8;            // quantiles a call, and so distinct prefixes a pass
@@ -46,10 +40,6 @@ struct ReliefState {
 };
 static_assert(sizeof(ReliefState) == 272, "ReliefState is 272 bytes");
 
-struct ReliefPlane {
-    double nx, ny, nz, off;
-};
-
 // float -> key with the floats' order (no NaN among the members); and back
 __device__ __forceinline__ unsigned relief_key(float hf) {
     const unsigned b = __float_as_uint(hf);
@@ -57,55 +47,6 @@ __device__ __forceinline__ unsigned relief_key(float hf) {
 }
 __device__ __forceinline__ float relief_unkey(unsigned k) {
     return __uint_as_float(k ^ ((k & 0x80000000u) ? 0x80000000u : 0xffffffffu));
-}
-
-__device__ __forceinline__ sdr_segment relief_segment(const sdr_relief_query& q) {
-    return sdr_segment{q.frame, q.x0, q.y0, q.x1, q.y1};
-}
-
-// 0, or the flag that refuses the query without a read of the maps; the plane of one that runs
-__device__ __forceinline__ uint32_t relief_refusal(const sdr_relief_query& q, int W, int H, int F, bool has_labels,
-                                                   const sdr_plane* __restrict__ planes, int NP, ReliefPlane* pl) {
-    if (!segment_in_range(relief_segment(q), W, H, F) || q.label < -1 || q.label > 255 ||
-        (q.label >= 0 && !has_labels))
-        return SDR_RELIEF_OUT_OF_RANGE;
-    if (q.plane < 0 || q.plane >= NP) return SDR_RELIEF_NO_PLANE;
-    const sdr_plane* p = planes + q.plane;
-    if (!(p->flags & SDR_PLANE_OK)) return SDR_RELIEF_NO_PLANE;
-    pl->nx = p->normal[0];
-    pl->ny = p->normal[1];
-    pl->nz = p->normal[2];
-    pl->off = p->offset;
-    return 0;
-}
-
-struct ReliefPix {
-    bool masked, valid, member;
-    float hf;
-};
-
-// Pixel (u, v) of the region whose origin (xs, ys) fd, fc and fl point at: the definition's steps
-// 1 to 5.  Every sweep repeats it: the same bits in every pass.
-template <typename T>
-__device__ __forceinline__ ReliefPix relief_pixel(const T* __restrict__ fd, size_t stride,
-                                                  const float* __restrict__ fc, const uint8_t* __restrict__ fl,
-                                                  int W, const Q16& Q, const ReliefPlane& pl,
-                                                  const sdr_relief_params& P, int label, int xs, int ys,
-                                                  unsigned u, unsigned v) {
-#pragma clang fp contract(off)
-    ReliefPix r = {false, false, false, 0.f};
-    r.masked = label < 0 || fl[(size_t)v * W + u] == (uint8_t)label;
-    if (!r.masked) return r;
-    const float d = load_disp(fd + (size_t)v * stride + u);
-    const float c = fc ? fc[(size_t)v * W + u] : 0.f;
-    r.valid = isfinite(d) && d > P.min_disp && (!fc || c >= P.conf_min);  // a NaN confidence fails
-    if (!r.valid) return r;
-    float xyz[3];
-    reproject_px(Q, xs + (int)u, ys + (int)v, (double)d, 0.0, 0, xyz);
-    const double h = ((pl.nx * (double)xyz[0] + pl.ny * (double)xyz[1]) + pl.nz * (double)xyz[2]) + pl.off;
-    r.hf = (float)h + 0.0f;
-    r.member = finite3(xyz) && fabsf(r.hf) < 1048576.0f;
-    return r;
 }
 
 // One sweep over the queries' pixels: grid (slices of a W x H frame, queries), `hist` the pass's
@@ -117,7 +58,7 @@ __device__ __forceinline__ ReliefPix relief_pixel(const T* __restrict__ fd, size
 // query that is refused or empty and a slice past the area leave at once (block-uniform); no
 // workgroup waits on another.
 template <typename T, int PASS>
-__global__ __launch_bounds__(kReliefThreads) void k_relief_sweep(
+__global__ __launch_bounds__(kRegionThreads) void k_relief_sweep(
     const T* __restrict__ disp, size_t stride, size_t fstride, int W, int H, int F, const float* __restrict__ conf,
     const uint8_t* __restrict__ labels, Q16 Q, sdr_relief_params P, const sdr_plane* __restrict__ planes, int NP,
     const sdr_relief_query* __restrict__ queries, ReliefState* __restrict__ states, unsigned* __restrict__ hist) {
@@ -129,40 +70,32 @@ __global__ __launch_bounds__(kReliefThreads) void k_relief_sweep(
     ReliefState* S = states + k;
     if (PASS > 1 && S->status) return;  // block-uniform
     const sdr_relief_query q = queries[k];
-    ReliefPlane pl;
-    if (relief_refusal(q, W, H, F, labels != nullptr, planes, NP, &pl)) return;
-    const PlaneRect R = plane_rect(relief_segment(q));
-    const unsigned area = (unsigned)R.rw * (unsigned)R.rh;  // <= W * H <= 2^24
-    const unsigned base = blockIdx.x * (unsigned)kReliefSlice;
-    if (base >= area) return;
+    RegionPlane pl;
+    if (region_refusal(q, W, H, F, labels != nullptr, planes, NP, &pl)) return;
+    RegionSlice<T, const uint8_t> sl;
+    if (!region_slice(region_segment(q), disp, stride, fstride, W, H, conf,
+                      labels ? labels + (size_t)q.frame * H * W : nullptr, &sl))
+        return;
     const int nslot = PASS == 1 ? 1 : S->nslot[PASS - 2];  // 1..nq
     const int slots = PASS == 1 ? 1 : P.nq;                 // the query's histograms of this pass
     unsigned pre[kReliefQ];
 #pragma unroll
     for (int s = 0; s < kReliefQ; s++) pre[s] = (PASS > 1 && s < nslot) ? S->prefix[PASS - 2][s] : 0u;
-    for (int i = tid; i < nslot * kBins; i += kReliefThreads) lh[i] = 0;
+    for (int i = tid; i < nslot * kBins; i += kRegionThreads) lh[i] = 0;
     __syncthreads();
-
-    const size_t org = (size_t)R.ys * W + (size_t)R.xs;
-    const T* fd = disp + (size_t)q.frame * fstride + (size_t)R.ys * stride + (size_t)R.xs;
-    const float* fc = conf ? conf + (size_t)q.frame * H * W + org : nullptr;
-    const uint8_t* fl = labels ? labels + (size_t)q.frame * H * W + org : nullptr;
 
     long long m[kReliefSums];
 #pragma unroll
     for (int i = 0; i < kReliefSums; i++) m[i] = 0;
     unsigned kmax = 0, kmin_inv = 0;
-#pragma unroll
-    for (int j = 0; j < kReliefPix; j++) {
-        const unsigned p = base + (unsigned)(j * kReliefThreads + tid);
-        if (p >= area) continue;
-        const unsigned v = p / (unsigned)R.rw, u = p - v * (unsigned)R.rw;
-        const ReliefPix px = relief_pixel(fd, stride, fc, fl, W, Q, pl, P, q.label, R.xs, R.ys, u, v);
+    sl.each([&](unsigned u, unsigned v) __attribute__((always_inline)) {
+        const RegionPix px = region_pixel(sl.fd, stride, sl.fc, sl.fl, W, Q, pl, P.min_disp, P.conf_min, q.label,
+                                          sl.R.xs, sl.R.ys, u, v);
         const unsigned key = relief_key(px.hf);
         if (PASS == 1) {
             m[0] += px.masked ? 1 : 0;
             m[1] += px.valid ? 1 : 0;
-            if (!px.member) continue;
+            if (!px.member) return;
             const bool above = px.hf > P.band;
             const long long e = llrint((double)px.hf * 256.0);
             m[2] += 1;
@@ -174,28 +107,25 @@ __global__ __launch_bounds__(kReliefThreads) void k_relief_sweep(
             kmin_inv = max(kmin_inv, ~key);
             atomicAdd(&lh[key >> 21], 1u);
         } else {
-            if (!px.member) continue;
+            if (!px.member) return;
             const unsigned top = PASS == 2 ? key >> 21 : key >> 10;
             const unsigned bin = PASS == 2 ? (key >> 10) & 2047u : key & 1023u;
 #pragma unroll
             for (int s = 0; s < kReliefQ; s++)  // the prefixes differ: one slot at most
                 if (s < nslot && top == pre[s]) atomicAdd(&lh[s * kBins + (int)bin], 1u);
         }
-    }
+    });
     if constexpr (PASS == 1) {
         // wave butterflies, then the waves' sums through LDS, as the plane fit's sweep
-        __shared__ long long red[kReliefWaves][kReliefSums];
-        __shared__ unsigned redk[kReliefWaves][2];
+        __shared__ long long red[kRegionWaves][kReliefSums];
+        __shared__ unsigned redk[kRegionWaves][2];
 #pragma unroll
         for (int i = 0; i < kReliefSums; i++) {
             const long long s = wave_sum(m[i]);
             if (lane == 0) red[wave][i] = s;
         }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, o, 64));
-            kmin_inv = max(kmin_inv, (unsigned)__shfl_xor((int)kmin_inv, o, 64));
-        }
+        kmax = wave_max(kmax);
+        kmin_inv = wave_max(kmin_inv);
         if (lane == 0) {
             redk[wave][0] = kmax;
             redk[wave][1] = kmin_inv;
@@ -204,19 +134,19 @@ __global__ __launch_bounds__(kReliefThreads) void k_relief_sweep(
         if (tid < kReliefSums) {
             long long s = 0;
 #pragma unroll
-            for (int w = 0; w < kReliefWaves; w++) s += red[w][tid];
+            for (int w = 0; w < kRegionWaves; w++) s += red[w][tid];
             if (s) atomicAdd((unsigned long long*)S->acc + tid, (unsigned long long)s);
         } else if (tid < kReliefSums + 2) {
             const int i = tid - kReliefSums;
             unsigned b = 0;
 #pragma unroll
-            for (int w = 0; w < kReliefWaves; w++) b = max(b, redk[w][i]);
+            for (int w = 0; w < kRegionWaves; w++) b = max(b, redk[w][i]);
             if (b) atomicMax(i ? &S->kmin_inv : &S->kmax, b);  // a member's key and ~key are never 0
         }
     }
     __syncthreads();
     unsigned* gh = hist + (size_t)k * (size_t)slots * kBins;
-    for (int i = tid; i < nslot * kBins; i += kReliefThreads) {
+    for (int i = tid; i < nslot * kBins; i += kRegionThreads) {
         const unsigned c = lh[i];
         if (c) atomicAdd(gh + i, c);
     }
@@ -227,7 +157,7 @@ __global__ __launch_bounds__(kReliefThreads) void k_relief_sweep(
 template <int BINS>
 __device__ __forceinline__ void relief_locate(const unsigned* __restrict__ h, unsigned k, unsigned* sh_wave,
                                               unsigned* sh_res, unsigned* bin, unsigned* rank) {
-    constexpr int kPer = BINS / kReliefThreads;
+    constexpr int kPer = BINS / kRegionThreads;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     unsigned c[kPer], sum = 0;
 #pragma unroll
@@ -317,24 +247,24 @@ __device__ __forceinline__ void relief_write(sdr_relief* o, const sdr_relief_que
 // Behind sweep 1, a workgroup a query: the record of a query that is refused or has no member
 // (the later kernels then leave it), else for each quantile the bin of the first histogram its
 // rank falls in and the rank inside the bin.
-__global__ __launch_bounds__(kReliefThreads) void k_relief_pick1(int W, int H, int F, int has_labels,
+__global__ __launch_bounds__(kRegionThreads) void k_relief_pick1(int W, int H, int F, int has_labels,
                                                                  sdr_relief_params P,
                                                                  const sdr_plane* __restrict__ planes, int NP,
                                                                  const sdr_relief_query* __restrict__ queries,
                                                                  ReliefState* __restrict__ states,
                                                                  const unsigned* __restrict__ hist1,
                                                                  sdr_relief* __restrict__ out) {
-    __shared__ unsigned sh_wave[kReliefWaves], sh_res[2];
+    __shared__ unsigned sh_wave[kRegionWaves], sh_res[2];
     const int k = blockIdx.x, tid = threadIdx.x;
     const sdr_relief_query q = queries[k];
     ReliefState* S = states + k;
-    ReliefPlane pl;
-    uint32_t flags = relief_refusal(q, W, H, F, has_labels != 0, planes, NP, &pl);
+    RegionPlane pl;
+    uint32_t flags = region_refusal(q, W, H, F, has_labels != 0, planes, NP, &pl);
     const long long n = S->acc[2];
     if (!flags && n == 0) flags = SDR_RELIEF_EMPTY;
     if (flags) {  // block-uniform
         if (tid == 0) {
-            const PlaneRect R = plane_rect(relief_segment(q));
+            const PlaneRect R = plane_rect(region_segment(q));
             relief_write(out + k, q, flags, flags == SDR_RELIEF_OUT_OF_RANGE ? 0 : R.rw * R.rh, S, P, nullptr);
             S->status = 1;
         }
@@ -351,10 +281,10 @@ __global__ __launch_bounds__(kReliefThreads) void k_relief_pick1(int W, int H, i
 }
 
 // Behind sweep 2: the next 11 bits of each quantile from its slot's histogram.
-__global__ __launch_bounds__(kReliefThreads) void k_relief_pick2(sdr_relief_params P,
+__global__ __launch_bounds__(kRegionThreads) void k_relief_pick2(sdr_relief_params P,
                                                                  ReliefState* __restrict__ states,
                                                                  const unsigned* __restrict__ hist2) {
-    __shared__ unsigned sh_wave[kReliefWaves], sh_res[2];
+    __shared__ unsigned sh_wave[kRegionWaves], sh_res[2];
     const int k = blockIdx.x, tid = threadIdx.x;
     ReliefState* S = states + k;
     if (S->status) return;  // block-uniform
@@ -370,12 +300,12 @@ __global__ __launch_bounds__(kReliefThreads) void k_relief_pick2(sdr_relief_para
 }
 
 // Behind sweep 3: the last 10 bits, each quantile's float from its 32 key bits, the record.
-__global__ __launch_bounds__(kReliefThreads) void k_relief_finish(sdr_relief_params P,
+__global__ __launch_bounds__(kRegionThreads) void k_relief_finish(sdr_relief_params P,
                                                                   const sdr_relief_query* __restrict__ queries,
                                                                   const ReliefState* __restrict__ states,
                                                                   const unsigned* __restrict__ hist3,
                                                                   sdr_relief* __restrict__ out) {
-    __shared__ unsigned sh_wave[kReliefWaves], sh_res[2];
+    __shared__ unsigned sh_wave[kRegionWaves], sh_res[2];
     __shared__ float qv[kReliefQ];
     const int k = blockIdx.x, tid = threadIdx.x;
     const ReliefState* S = states + k;
@@ -389,7 +319,7 @@ __global__ __launch_bounds__(kReliefThreads) void k_relief_finish(sdr_relief_par
     }
     if (tid != 0) return;
     const sdr_relief_query q = queries[k];
-    const PlaneRect R = plane_rect(relief_segment(q));
+    const PlaneRect R = plane_rect(region_segment(q));
     relief_write(out + k, q, SDR_RELIEF_VALID, R.rw * R.rh, S, P, qv);
 }
 
@@ -404,7 +334,7 @@ using namespace sdr::ruler_host;
 constexpr int kReliefBatch = 256;
 
 int check_relief_params(const sdr_relief_params* p, const void* planes, int P) {
-    if (P < 0 || (P > 0 && !planes)) return rfail(SDR_ERR_ARG, "bad plane count or null planes");
+    if (int rc = check_planes_arg(planes, P)) return rc;
     if (p->nq < 0 || p->nq > 8) return rfail(SDR_ERR_ARG, "nq must be in 0..8");
     for (int j = 0; j < p->nq; j++)
         if (p->permille[j] < 0 || p->permille[j] > 1000) return rfail(SDR_ERR_ARG, "permille must be in 0..1000");
@@ -438,8 +368,7 @@ int sdr_plane_relief_device(const void* d_disp, int disp_type, size_t stride, si
     if (rc || (rc = check_relief_params(params, d_planes, P))) return rc;
     if (K == 0) return SDR_OK;
     hipStream_t st = (hipStream_t)stream;
-    sdr::Q16 q;
-    for (int i = 0; i < 16; i++) q.q[i] = Q[i];
+    const sdr::Q16 q = make_q16(Q);
     const sdr_relief_params RP = *params;
     const int nq = RP.nq, KB = std::min(K, kReliefBatch);
     // scratch of a batch, all of it zeroed: {states, pass 1's histograms, pass 2's, pass 3's}
@@ -453,13 +382,13 @@ int sdr_plane_relief_device(const void* d_disp, int disp_type, size_t stride, si
     unsigned* h1 = (unsigned*)(sc + o_h1);
     unsigned* h2 = (unsigned*)(sc + o_h2);
     unsigned* h3 = (unsigned*)(sc + o_h3);
-    const unsigned slices = (unsigned)(((size_t)W * H + sdr::kReliefSlice - 1) / sdr::kReliefSlice);
-    const dim3 block(sdr::kReliefThreads);
+    const unsigned slices = sdr::region_slices(W, H);
+    const dim3 block(sdr::kRegionThreads);
     const size_t lds1 = sdr::kReliefBins * sizeof(unsigned), lds2 = (size_t)nq * lds1,
                  lds3 = (size_t)nq * sdr::kReliefLastBins * sizeof(unsigned);
     hipError_t e = hipSuccess;
     auto batch = [&](auto* disp, int k0, int kb) {
-        using T = std::remove_cv_t<std::remove_pointer_t<decltype(disp)>>;
+        using T = disp_elem_t<decltype(disp)>;
         const sdr_relief_query* qs = d_queries + k0;
         const dim3 sgrid(slices, (unsigned)kb), pgrid((unsigned)kb);
         if ((e = hipMemsetAsync(sc, 0, bytes, st)) != hipSuccess) return;
@@ -477,13 +406,8 @@ int sdr_plane_relief_device(const void* d_disp, int disp_type, size_t stride, si
         hipLaunchKernelGGL(sdr::k_relief_finish, pgrid, block, 0, st, RP, qs, (const sdr::ReliefState*)states,
                            (const unsigned*)h3, d_out + k0);
     };
-    for (int k0 = 0; k0 < K && e == hipSuccess; k0 += KB) {
-        const int kb = std::min(K - k0, KB);
-        if (disp_type == SDR_DISP_F32)
-            batch((const float*)d_disp, k0, kb);
-        else
-            batch((const int16_t*)d_disp, k0, kb);
-    }
+    for (int k0 = 0; k0 < K && e == hipSuccess; k0 += KB)
+        with_disp(disp_type, d_disp, [&](auto* disp) { batch(disp, k0, std::min(K - k0, KB)); });
     const hipError_t le = hipGetLastError();
     RULER_HIP(sdr::scratch_free(sc, st));
     RULER_HIP(e);
@@ -494,30 +418,8 @@ int sdr_plane_relief_device(const void* d_disp, int disp_type, size_t stride, si
 int sdr_plane_relief(const void* disp, int disp_type, size_t stride, size_t frame_stride, int W, int H, int F,
                      const float* conf, const uint8_t* labels, const double Q[16], const sdr_relief_params* params,
                      const sdr_plane* planes, int P, const sdr_relief_query* queries, int K, sdr_relief* out) {
-    int rc = check_plane_maps(disp, disp_type, stride, frame_stride, W, H, F, Q, params, queries, K, out);
-    if (rc || (rc = check_relief_params(params, planes, P))) return rc;
-    if (K == 0) return SDR_OK;
-    HostState* S = nullptr;
-    if ((rc = host_state(&S))) return rc;
-    const size_t px = (size_t)W * H;
-    // segs: the queries; prof: the labels
-    if ((rc = upload_maps(S, disp, disp_type, stride, frame_stride, W, H, F, conf)) ||
-        (rc = sdr::ensure(S->segs, (size_t)K * sizeof(sdr_relief_query))) ||
-        (rc = sdr::ensure(S->planes, (size_t)P * sizeof(sdr_plane))) ||
-        (rc = sdr::ensure(S->prof, labels ? (size_t)F * px : 0)) ||
-        (rc = sdr::ensure(S->out, (size_t)K * sizeof(sdr_relief))))
-        return rc;
-    RULER_HIP(hipMemcpyAsync(S->segs.p, queries, (size_t)K * sizeof(sdr_relief_query), hipMemcpyHostToDevice, S->st));
-    if (P) RULER_HIP(hipMemcpyAsync(S->planes.p, planes, (size_t)P * sizeof(sdr_plane), hipMemcpyHostToDevice, S->st));
-    if (labels) RULER_HIP(hipMemcpyAsync(S->prof.p, labels, (size_t)F * px, hipMemcpyHostToDevice, S->st));
-    rc = sdr_plane_relief_device(S->map.p, disp_type, (size_t)W, px, W, H, F, conf ? (const float*)S->conf.p : nullptr,
-                                 labels ? (const uint8_t*)S->prof.p : nullptr, Q, params,
-                                 P ? (const sdr_plane*)S->planes.p : nullptr, P, (const sdr_relief_query*)S->segs.p,
-                                 K, (sdr_relief*)S->out.p, S->st);
-    if (rc) return rc;
-    RULER_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(sdr_relief), hipMemcpyDeviceToHost, S->st));
-    RULER_HIP(hipStreamSynchronize(S->st));
-    return SDR_OK;
+    return region_host_call(check_relief_params, sdr_plane_relief_device, disp, disp_type, stride, frame_stride, W, H,
+                            F, conf, labels, Q, params, planes, P, queries, K, out);
 }
 
 }  // extern "C"

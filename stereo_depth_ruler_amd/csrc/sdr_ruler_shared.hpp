@@ -1,8 +1,12 @@
-// sdr_ruler_shared.hpp -- what the ruler's units (sdr_ruler.hip, sdr_relief.hip, sdr_footprint.hip) share: the device
-// helpers of the region rule, the disparity loads and the canonical NaN, and the host side of the
-// host-pointer calls (the argument guards of the maps, the per-thread persistent buffers).
+// sdr_ruler_shared.hpp -- what the ruler's units (sdr_ruler.hip, sdr_plane.hip, sdr_relief.hip,
+// sdr_footprint.hip) share: on the device the disparity loads, the canonical NaN, the wave
+// reductions, a rectangle's range test and the ruler's sample; on the host (ruler_host) the argument
+// guards, the Q and disparity-type plumbing of a launch, the per-thread persistent buffers and the
+// host-pointer path of the calls that take plane records and queries.  The region rule of the
+// relief and the footprint is in sdr_region.hpp.
 #pragma once
 #include <string>
+#include <type_traits>
 
 #include "sdr_device.hpp"
 #include "sdr_internal.hpp"
@@ -50,6 +54,85 @@ __device__ __forceinline__ long long wave_sum(long long v) {
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+template <typename V>
+__device__ __forceinline__ V wave_min(V v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    return v;
+}
+template <typename V>
+__device__ __forceinline__ V wave_max(V v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+struct RulerSample {
+    float xyz[3];
+    float d;
+    int n;
+    bool valid;
+};
+
+// One sample by one wave (every lane returns the same values): the window's <= 81 values two a
+// lane, the valid mask as two ballots, the lower median by counting, for each lane's values, the
+// valid values that sort before them (ties by window index), then the reprojection.
+template <typename T>
+__device__ __forceinline__ RulerSample ruler_sample(const T* __restrict__ disp, size_t stride,
+                                                    const float* __restrict__ conf, int W, int H,
+                                                    const Q16& Q, const sdr_ruler_params& P, int x,
+                                                    int y, int lane) {
+    const int r = P.radius;
+    const int xs = max(x - r, 0), xe = min(x + r, W - 1);
+    const int ys = max(y - r, 0), ye = min(y + r, H - 1);
+    const int ww = xe - xs + 1, cnt = ww * (ye - ys + 1);
+    float v[2];
+    bool ok[2];
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const int j = lane + 64 * k;
+        v[k] = 0.f;
+        ok[k] = false;
+        if (j < cnt) {
+            const int wy = j / ww, wx = j - wy * ww;
+            const size_t py = (size_t)(ys + wy), px = (size_t)(xs + wx);
+            // both loads issue before either is used (a NaN confidence fails the comparison)
+            const float d = load_disp(disp + py * stride + px);
+            const float c = conf ? conf[py * (size_t)W + px] : 0.f;
+            v[k] = d;
+            ok[k] = isfinite(d) && d > P.min_disp && (!conf || c >= P.conf_min);
+        }
+    }
+    const unsigned long long m0 = __ballot(ok[0]), m1 = __ballot(ok[1]);
+    RulerSample s;
+    s.n = __popcll(m0) + __popcll(m1);
+    s.d = s.xyz[0] = s.xyz[1] = s.xyz[2] = ruler_nan();
+    s.valid = false;
+    if (s.n < P.min_count || s.n == 0) return s;
+    int rank[2] = {0, 0};
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        unsigned long long m = k ? m1 : m0;
+        while (m) {
+            const int c = __builtin_ctzll(m);
+            m &= m - 1;
+            const float vc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v[k]), c));
+            const int jc = c + 64 * k;
+            rank[0] += (vc < v[0] || (vc == v[0] && jc < lane)) ? 1 : 0;
+            if (cnt > 64) rank[1] += (vc < v[1] || (vc == v[1] && jc < lane + 64)) ? 1 : 0;  // radius 4 only
+        }
+    }
+    const int want = (s.n - 1) >> 1;
+    const unsigned long long h0 = __ballot(ok[0] && rank[0] == want);
+    const unsigned long long h1 = __ballot(ok[1] && rank[1] == want);
+    // exactly one valid value has rank `want`
+    const float dmed = h0 ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v[0]), __builtin_ctzll(h0)))
+                          : __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v[1]), __builtin_ctzll(h1 | (1ull << 63))));
+    s.d = dmed;
+    reproject_px(Q, x, y, (double)dmed, 0.0, 0, s.xyz);
+    s.valid = finite3(s.xyz);
+    return s;
+}
 
 // ---- host side ----
 namespace ruler_host {
@@ -62,6 +145,29 @@ namespace ruler_host {
     } while (0)
 
 inline int rfail(int code, const char* msg) { return sdr::set_error(code, msg); }
+
+inline sdr::Q16 make_q16(const double* Q) {
+    sdr::Q16 q;
+    for (int i = 0; i < 16; i++) q.q[i] = Q[i];
+    return q;
+}
+
+// f(the map as const float* or const int16_t*): the launches of a checked disp_type
+template <typename F>
+inline void with_disp(int disp_type, const void* disp, F&& f) {
+    if (disp_type == SDR_DISP_F32)
+        f((const float*)disp);
+    else
+        f((const int16_t*)disp);
+}
+// the map's element type from with_disp's pointer
+template <typename P>
+using disp_elem_t = std::remove_cv_t<std::remove_pointer_t<P>>;
+
+inline int check_planes_arg(const void* planes, int P) {
+    if (P < 0 || (P > 0 && !planes)) return rfail(SDR_ERR_ARG, "bad plane count or null planes");
+    return SDR_OK;
+}
 
 // argument guards shared by the plane fit, the point query and the relief (host only):
 // check_disp_args' rules for the maps, with a bad disp_type an argument error too, and the sizes the
@@ -135,6 +241,46 @@ inline int upload_maps(HostState* S, const void* disp, int disp_type, size_t str
         return rc;
     if ((rc = upload_rows(S->map.p, disp, (size_t)W * es, stride * es, fstride * es, H, F, S->st))) return rc;
     if (conf) RULER_HIP(hipMemcpyAsync(S->conf.p, conf, (size_t)F * px * 4, hipMemcpyHostToDevice, S->st));
+    return SDR_OK;
+}
+
+// the plane records, the queries and the optional label maps of a host-pointer call into the
+// thread's buffers (planes; segs; prof), and room for its records (out)
+inline int upload_queries(HostState* S, const sdr_plane* planes, int P, const void* queries, size_t query_bytes,
+                          const uint8_t* labels, size_t label_bytes, size_t out_bytes) {
+    int rc;
+    if ((rc = sdr::ensure(S->segs, query_bytes)) || (rc = sdr::ensure(S->planes, (size_t)P * sizeof(sdr_plane))) ||
+        (rc = sdr::ensure(S->prof, labels ? label_bytes : 0)) || (rc = sdr::ensure(S->out, out_bytes)))
+        return rc;
+    RULER_HIP(hipMemcpyAsync(S->segs.p, queries, query_bytes, hipMemcpyHostToDevice, S->st));
+    if (P) RULER_HIP(hipMemcpyAsync(S->planes.p, planes, (size_t)P * sizeof(sdr_plane), hipMemcpyHostToDevice, S->st));
+    if (labels) RULER_HIP(hipMemcpyAsync(S->prof.p, labels, label_bytes, hipMemcpyHostToDevice, S->st));
+    return SDR_OK;
+}
+
+// The host-pointer form of an entry that measures regions against plane records (the relief, the
+// footprint): `check` is the entry's parameter guard, `entry` its device form.
+template <typename Params, typename Rec, typename Check, typename Entry>
+inline int region_host_call(Check check, Entry entry, const void* disp, int disp_type, size_t stride,
+                            size_t frame_stride, int W, int H, int F, const float* conf, const uint8_t* labels,
+                            const double* Q, const Params* params, const sdr_plane* planes, int P,
+                            const sdr_relief_query* queries, int K, Rec* out) {
+    int rc = check_plane_maps(disp, disp_type, stride, frame_stride, W, H, F, Q, params, queries, K, out);
+    if (rc || (rc = check(params, planes, P))) return rc;
+    if (K == 0) return SDR_OK;
+    HostState* S = nullptr;
+    if ((rc = host_state(&S))) return rc;
+    const size_t px = (size_t)W * H;
+    if ((rc = upload_maps(S, disp, disp_type, stride, frame_stride, W, H, F, conf)) ||
+        (rc = upload_queries(S, planes, P, queries, (size_t)K * sizeof(sdr_relief_query), labels, (size_t)F * px,
+                             (size_t)K * sizeof(Rec))))
+        return rc;
+    rc = entry(S->map.p, disp_type, (size_t)W, px, W, H, F, conf ? (const float*)S->conf.p : nullptr,
+               labels ? (const uint8_t*)S->prof.p : nullptr, Q, params, P ? (const sdr_plane*)S->planes.p : nullptr, P,
+               (const sdr_relief_query*)S->segs.p, K, (Rec*)S->out.p, S->st);
+    if (rc) return rc;
+    RULER_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(Rec), hipMemcpyDeviceToHost, S->st));
+    RULER_HIP(hipStreamSynchronize(S->st));
     return SDR_OK;
 }
 

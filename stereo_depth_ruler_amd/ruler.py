@@ -1,6 +1,7 @@
 """The ruler: the reference's two-point measurement (StereoDisplayer::onMouseMeasure,
 stereo_vision/src/stereo_displayer.cpp:24-63) and its CSV log (save_csvFile, :74-102) on the HIP
-engine (csrc/sdr_ruler.hip; the definition is in include/sdr/sdr.h).
+engine (csrc/sdr_ruler.hip; the plane fit, the plane search and the point query: csrc/sdr_plane.hip;
+the definition is in include/sdr/sdr.h).
 
 * ``Ruler.measure_xyz(depth_map, segments)`` is the reference's own: the computeDepth map read at
   the two pixels, ``cv::norm`` of the difference.
@@ -16,7 +17,8 @@ engine (csrc/sdr_ruler.hip; the definition is in include/sdr/sdr.h).
 * ``Ruler.relief(disparity, planes, regions, labels=None)`` measures a whole surface against a plane:
   the heights of a rectangle's pixels (optionally only those with one label of ``find_planes``' map)
   above a plane record, as counts, extremes, exact means and order statistics (a radix selection on
-  the device, csrc/sdr_relief.hip): the height of a box above the table, the depth of a step.
+  the device, csrc/sdr_relief.hip, on the region rule of csrc/sdr_region.hpp): the height of a box
+  above the table, the depth of a step.
 * ``Ruler.footprint(disparity, planes, regions, labels=None)`` measures a surface IN a plane: the
   pixels of a rectangle (optionally one label, optionally a band of heights) binned on square cells
   of the plane, stray cells dropped by a 3 x 3 support rule, and the minimum-area bounding rectangle
@@ -156,6 +158,13 @@ def as_segments(segments) -> np.ndarray:
     return np.ascontiguousarray(s, dtype=np.int32)
 
 
+# the query rows of the device calls: (host converter, name in messages, int32 columns)
+_RECTANGLES = (as_segments, "regions", 5)
+_POINTS = (as_queries, "points", 4)
+_REGIONS = (as_relief_queries, "regions", 8)
+_NO_LABELS = object()  # an entry that takes no label map
+
+
 def _frames3(a, what):
     """a as (F, H, W)."""
     if a.ndim == 2:
@@ -170,6 +179,48 @@ def _on_device(index: int):
     if torch is not None and torch.cuda.is_available():
         return torch.cuda.device(index)
     return contextlib.nullcontext()
+
+
+def _host_planes(planes) -> np.ndarray:
+    """Plane records (PLANE_DTYPE, or a tensor of them) as a host PLANE_DTYPE array."""
+    if _is_cuda(planes):
+        planes = planes.cpu().numpy()
+    return np.ascontiguousarray(planes).reshape(-1).view(np.uint8).view(PLANE_DTYPE)
+
+
+def _device_planes(planes, dev):
+    """Plane records as a contiguous uint8 tensor (P, 128) on `dev`; None for no record."""
+    if _is_cuda(planes):
+        if planes.dtype != torch.uint8 or planes.numel() % 128:
+            raise SDRError(-5, "device planes must be a uint8 tensor (P, 128)")
+        return planes.contiguous()
+    host = np.ascontiguousarray(planes).reshape(-1).view(np.uint8).reshape(-1, 128)
+    return torch.from_numpy(host.copy()).to(dev) if host.shape[0] else None
+
+
+def _host_labels(labels, shape):
+    """A label map (host or tensor, or None) as a contiguous host uint8 array of `shape` (F, H, W)."""
+    if labels is None:
+        return None
+    if _is_cuda(labels):
+        labels = labels.cpu().numpy()
+    lab = np.asarray(labels)
+    if lab.dtype != np.uint8:
+        raise SDRError(-5, "labels must be uint8")
+    lab = np.ascontiguousarray(_frames3(lab, "labels"))
+    if lab.shape != shape:
+        raise SDRError(-1, "labels must have the disparity's shape")
+    return lab
+
+
+def _device_labels(labels, d, dev):
+    """A label map (host or tensor, or None) as a contiguous uint8 tensor of d's size on `dev`."""
+    if labels is None:
+        return None
+    lab = labels if _is_cuda(labels) else torch.from_numpy(np.ascontiguousarray(labels)).to(dev)
+    if lab.dtype != torch.uint8 or lab.numel() != d.numel():
+        raise SDRError(-5, "labels must be a uint8 map of the disparity's shape")
+    return lab.contiguous()
 
 
 class _SegmentStaging:
@@ -237,7 +288,7 @@ class Ruler:
             rec, prof = self.measure_device(disparity, segments, conf)
             out = _records(rec.cpu().numpy())
             return (out, prof.cpu().numpy()) if self.profile else out
-        d, c, rs, fs = self._host_maps(disparity, conf)
+        d, c, a = self._host_maps(disparity, conf)
         F, H, W = d.shape
         segs = as_segments(segments)
         K = segs.shape[0]
@@ -246,11 +297,9 @@ class Ruler:
         prof = np.full((K, cap, 4), np.nan, np.float32) if self.profile else None
         p = self._params(cap)
         with _on_device(self.device):
-            rc = lib().sdr_measure_disp(
-                d.ctypes.data, DISP_F32 if d.dtype == np.float32 else DISP_S16, rs, fs, W, H, F,
-                c.ctypes.data if c is not None else None, _Q(self.Q), ctypes.byref(p),
-                segs.ctypes.data if K else None, K, rec.ctypes.data if K else None,
-                prof.ctypes.data if prof is not None and prof.size else None)
+            rc = lib().sdr_measure_disp(*a, _Q(self.Q), ctypes.byref(p), segs.ctypes.data if K else None, K,
+                                        rec.ctypes.data if K else None,
+                                        prof.ctypes.data if prof is not None and prof.size else None)
         check(rc)
         return (rec, prof) if self.profile else rec
 
@@ -280,7 +329,7 @@ class Ruler:
         dev = disparity.device
         s = stream if stream is not None else torch.cuda.current_stream(dev.index)
         with torch.cuda.stream(s):
-            d, conf = self._device_maps(disparity, conf)  # copies, if any, on `s`, ahead of the kernel
+            d, conf, a = self._device_maps(disparity, conf)  # copies, if any, on `s`, ahead of the kernel
             F, H, W = d.shape
             if _is_cuda(segments):
                 if segments.dtype != torch.int32 or segments.dim() != 2 or segments.shape[1] != 5:
@@ -307,18 +356,15 @@ class Ruler:
                     prof = torch.full((K, cap, 4), float("nan"), dtype=torch.float32, device=dev)
             p = self._params(cap)
             check(lib().sdr_measure_disp_device(
-                d.data_ptr(), DISP_F32 if d.dtype == torch.float32 else DISP_S16, d.stride(1),
-                d.stride(1) * H if F == 1 else d.stride(0), W, H, F,
-                conf.data_ptr() if conf is not None else None, _Q(self.Q), ctypes.byref(p),
-                segs.data_ptr() if K else None, K, rec.data_ptr() if K else None,
-                prof.data_ptr() if prof is not None and prof.numel() else None,
-                ctypes.c_void_p(s.cuda_stream)))
+                *a, _Q(self.Q), ctypes.byref(p), segs.data_ptr() if K else None, K, rec.data_ptr() if K else None,
+                prof.data_ptr() if prof is not None and prof.numel() else None, ctypes.c_void_p(s.cuda_stream)))
         return rec, prof
 
     # ---- the maps of the disparity-mode calls ----
     @staticmethod
     def _host_maps(disparity, conf):
-        """(d (F, H, W), conf or None, row stride, frame stride) of host maps for the host ABI."""
+        """(d (F, H, W), conf or None, the host ABI's argument run (disp, disp_type, stride,
+        frame_stride, W, H, F, conf)) of host maps."""
         d = np.asarray(disparity)
         if d.dtype not in (np.float32, np.int16):
             raise SDRError(-5, "disparity must be float32 (px) or int16 (1/16 px)")
@@ -333,11 +379,14 @@ class Ruler:
             if c.shape != d.shape:
                 raise SDRError(-1, "conf must have the disparity's shape")
         rs = d.strides[1] // d.itemsize
-        return d, c, rs, (rs * H if F == 1 else d.strides[0] // d.itemsize)
+        return d, c, (d.ctypes.data, DISP_F32 if d.dtype == np.float32 else DISP_S16, rs,
+                      rs * H if F == 1 else d.strides[0] // d.itemsize, W, H, F,
+                      c.ctypes.data if c is not None else None)
 
     @staticmethod
     def _device_maps(disparity, conf):
-        """(d (F, H, W), conf or None) of CUDA maps, made contiguous on the current stream."""
+        """(d (F, H, W), conf or None, the device ABI's argument run as _host_maps gives the host's)
+        of CUDA maps, made contiguous on the current stream."""
         d = disparity
         if not _is_cuda(d) or d.dtype not in (torch.float32, torch.int16):
             raise SDRError(-5, "expected a CUDA float32 or int16 disparity tensor")
@@ -351,7 +400,10 @@ class Ruler:
             if not _is_cuda(conf) or conf.dtype != torch.float32 or conf.numel() != d.numel():
                 raise SDRError(-5, "conf must be a CUDA float32 tensor of the disparity's shape")
             conf = conf.contiguous()
-        return d, conf
+        F, H, W = d.shape
+        return d, conf, (d.data_ptr(), DISP_F32 if d.dtype == torch.float32 else DISP_S16, d.stride(1),
+                         d.stride(1) * H if F == 1 else d.stride(0), W, H, F,
+                         conf.data_ptr() if conf is not None else None)
 
     # ---- against a surface: plane fit and point-to-plane distance ----
     def _plane_params(self, iterations, inlier_px, min_inliers) -> PlaneParams:
@@ -364,17 +416,14 @@ class Ruler:
         if _is_cuda(disparity):
             rec = self.fit_plane_device(disparity, regions, conf, iterations, inlier_px, min_inliers)
             return rec.cpu().numpy().reshape(-1).view(PLANE_DTYPE)
-        d, c, rs, fs = self._host_maps(disparity, conf)
-        F, H, W = d.shape
+        d, c, a = self._host_maps(disparity, conf)
         regs = as_segments(regions)
         K = regs.shape[0]
         rec = np.zeros(K, PLANE_DTYPE)
         p = self._plane_params(iterations, inlier_px, min_inliers)
         with _on_device(self.device):
-            rc = lib().sdr_fit_planes(
-                d.ctypes.data, DISP_F32 if d.dtype == np.float32 else DISP_S16, rs, fs, W, H, F,
-                c.ctypes.data if c is not None else None, _Q(self.Q), ctypes.byref(p),
-                regs.ctypes.data if K else None, K, rec.ctypes.data if K else None)
+            rc = lib().sdr_fit_planes(*a, _Q(self.Q), ctypes.byref(p), regs.ctypes.data if K else None, K,
+                                      rec.ctypes.data if K else None)
         check(rc)
         return rec
 
@@ -388,23 +437,13 @@ class Ruler:
         dev = disparity.device
         s = stream if stream is not None else torch.cuda.current_stream(dev.index)
         with torch.cuda.stream(s):
-            d, conf = self._device_maps(disparity, conf)
-            F, H, W = d.shape
-            if _is_cuda(regions):
-                if regions.dtype != torch.int32 or regions.dim() != 2 or regions.shape[1] != 5:
-                    raise SDRError(-5, "device regions must be an int32 tensor (K, 5)")
-                regs = regions.contiguous()
-            else:
-                regs = self._upload_segments(as_segments(regions), dev, s)
+            d, conf, a = self._device_maps(disparity, conf)
+            regs = self._device_rows(regions, _RECTANGLES, dev, s)
             K = regs.shape[0]
             rec = torch.empty((K, 128), dtype=torch.uint8, device=dev)
             p = self._plane_params(iterations, inlier_px, min_inliers)
-            check(lib().sdr_fit_planes_device(
-                d.data_ptr(), DISP_F32 if d.dtype == torch.float32 else DISP_S16, d.stride(1),
-                d.stride(1) * H if F == 1 else d.stride(0), W, H, F,
-                conf.data_ptr() if conf is not None else None, _Q(self.Q), ctypes.byref(p),
-                regs.data_ptr() if K else None, K, rec.data_ptr() if K else None,
-                ctypes.c_void_p(s.cuda_stream)))
+            check(lib().sdr_fit_planes_device(*a, _Q(self.Q), ctypes.byref(p), regs.data_ptr() if K else None, K,
+                                              rec.data_ptr() if K else None, ctypes.c_void_p(s.cuda_stream)))
         return rec
 
     # ---- the dominant planes of a region (sdr.h, "the dominant planes of a region") ----
@@ -448,7 +487,7 @@ class Ruler:
                          labels: bool = False):
         """find_planes on host maps with everything the search writes: (all max_planes records, count,
         the rounds as a PLANE_SEARCH_ROUND_DTYPE array, the labels or None)."""
-        d, c, rs, fs = self._host_maps(disparity, conf)
+        d, c, a = self._host_maps(disparity, conf)
         F, H, W = d.shape
         reg = self._search_region(region, W, H)
         p = self._search_params(max_planes, hypotheses, seed, iterations, inlier_px, min_inliers)
@@ -458,11 +497,9 @@ class Ruler:
         count = np.zeros(1, np.int32)
         lab = np.full((H, W), 255, np.uint8) if labels else None
         with _on_device(self.device):
-            rc = lib().sdr_find_planes(
-                d.ctypes.data, DISP_F32 if d.dtype == np.float32 else DISP_S16, rs, fs, W, H, F,
-                c.ctypes.data if c is not None else None, _Q(self.Q), ctypes.byref(p), reg.ctypes.data,
-                rec.ctypes.data if n else None, count.ctypes.data, rounds.ctypes.data if n else None,
-                lab.ctypes.data if lab is not None else None)
+            rc = lib().sdr_find_planes(*a, _Q(self.Q), ctypes.byref(p), reg.ctypes.data, rec.ctypes.data if n else None,
+                                       count.ctypes.data, rounds.ctypes.data if n else None,
+                                       lab.ctypes.data if lab is not None else None)
         check(rc)
         return rec, int(count[0]), rounds, lab
 
@@ -479,7 +516,7 @@ class Ruler:
         dev = disparity.device
         s = stream if stream is not None else torch.cuda.current_stream(dev.index)
         with torch.cuda.stream(s):
-            d, conf = self._device_maps(disparity, conf)
+            d, conf, a = self._device_maps(disparity, conf)
             F, H, W = d.shape
             p = self._search_params(max_planes, hypotheses, seed, iterations, inlier_px, min_inliers)
             if _is_cuda(region):
@@ -501,12 +538,71 @@ class Ruler:
             elif labels:
                 lab = torch.empty((H, W), dtype=torch.uint8, device=dev)
             check(lib().sdr_find_planes_device(
-                d.data_ptr(), DISP_F32 if d.dtype == torch.float32 else DISP_S16, d.stride(1),
-                d.stride(1) * H if F == 1 else d.stride(0), W, H, F,
-                conf.data_ptr() if conf is not None else None, _Q(self.Q), ctypes.byref(p), reg.data_ptr(),
-                rec.data_ptr() if n else None, count.data_ptr(), rounds.data_ptr() if n else None,
-                lab.data_ptr() if lab is not None else None, ctypes.c_void_p(s.cuda_stream)))
+                *a, _Q(self.Q), ctypes.byref(p), reg.data_ptr(), rec.data_ptr() if n else None, count.data_ptr(),
+                rounds.data_ptr() if n else None, lab.data_ptr() if lab is not None else None,
+                ctypes.c_void_p(s.cuda_stream)))
         return rec, count, rounds, lab
+
+    # ---- queries against plane records: the point query, the relief, the footprint ----
+    def _plane_queries(self, entry, params, dtype, disparity, planes, rows, kind, conf, labels=_NO_LABELS):
+        """The host-pointer form of an entry that takes maps, plane records and query rows: a `dtype`
+        array of K.  params: makes the parameter struct; kind: the rows' (converter, name, width);
+        labels: the label map or None of an entry that takes one."""
+        p = params()
+        pl = _host_planes(planes)
+        d, c, a = self._host_maps(disparity, conf)
+        lab_arg = ()
+        if labels is not _NO_LABELS:
+            lab = _host_labels(labels, d.shape)
+            lab_arg = (lab.ctypes.data if lab is not None else None,)
+        qs = kind[0](rows)
+        K, P = qs.shape[0], pl.shape[0]
+        out = np.zeros(K, dtype)
+        with _on_device(self.device):
+            rc = entry(*a, *lab_arg, _Q(self.Q), ctypes.byref(p), pl.ctypes.data if P else None, P,
+                       qs.ctypes.data if K else None, K, out.ctypes.data if K else None)
+        check(rc)
+        return out
+
+    def _plane_queries_device(self, name, entry, params, size, disparity, planes, rows, kind, conf, stream,
+                              labels=_NO_LABELS):
+        """The device form of _plane_queries: enqueues on `stream` (default: the current stream) and
+        returns a uint8 tensor (K, size) without synchronising."""
+        if not _is_cuda(disparity):
+            raise SDRError(-5, f"{name} expects a CUDA float32 or int16 tensor")
+        p = params()
+        dev = disparity.device
+        s = stream if stream is not None else torch.cuda.current_stream(dev.index)
+        with torch.cuda.stream(s):
+            d, conf, a = self._device_maps(disparity, conf)
+            pl = _device_planes(planes, dev)
+            P = pl.numel() // 128 if pl is not None else 0
+            lab_arg = ()
+            if labels is not _NO_LABELS:
+                lab = _device_labels(labels, d, dev)
+                lab_arg = (lab.data_ptr() if lab is not None else None,)
+            qs = self._device_rows(rows, kind, dev, s)
+            K = qs.shape[0]
+            out = torch.empty((K, size), dtype=torch.uint8, device=dev)
+            check(entry(*a, *lab_arg, _Q(self.Q), ctypes.byref(p), pl.data_ptr() if P else None, P,
+                        qs.data_ptr() if K else None, K, out.data_ptr() if K else None,
+                        ctypes.c_void_p(s.cuda_stream)))
+        return out
+
+    def _device_rows(self, rows, kind, dev, stream):
+        """Query rows on the device: a CUDA int32 tensor of the kind's width as it is, host rows
+        through the kind's converter and the page-locked staging."""
+        as_rows, what, width = kind
+        if not _is_cuda(rows):
+            return self._upload_segments(as_rows(rows), dev, stream)
+        if rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != width:
+            raise SDRError(-5, f"device {what} must be an int32 tensor (K, {width})")
+        return rows.contiguous()
+
+    def _point_params(self) -> RulerParams:
+        p = self._params(0)
+        p.profile = 0
+        return p
 
     def plane_distance(self, disparity, planes, points, conf=None):
         """Signed distances of sampled points to fitted planes: a PLANE_DISTANCE_DTYPE array of K.
@@ -516,63 +612,16 @@ class Ruler:
         if _is_cuda(disparity):
             out = self.plane_distance_device(disparity, planes, points, conf)
             return out.cpu().numpy().reshape(-1).view(PLANE_DISTANCE_DTYPE)
-        if _is_cuda(planes):
-            planes = planes.cpu().numpy()
-        pl = np.ascontiguousarray(planes).reshape(-1).view(np.uint8).view(PLANE_DTYPE)
-        d, c, rs, fs = self._host_maps(disparity, conf)
-        F, H, W = d.shape
-        qs = as_queries(points)
-        K, P = qs.shape[0], pl.shape[0]
-        out = np.zeros(K, PLANE_DISTANCE_DTYPE)
-        p = self._params(0)
-        p.profile = 0
-        with _on_device(self.device):
-            rc = lib().sdr_plane_distance(
-                d.ctypes.data, DISP_F32 if d.dtype == np.float32 else DISP_S16, rs, fs, W, H, F,
-                c.ctypes.data if c is not None else None, _Q(self.Q), ctypes.byref(p),
-                pl.ctypes.data if P else None, P, qs.ctypes.data if K else None, K,
-                out.ctypes.data if K else None)
-        check(rc)
-        return out
+        return self._plane_queries(lib().sdr_plane_distance, self._point_params, PLANE_DISTANCE_DTYPE, disparity,
+                                   planes, points, _POINTS, conf)
 
     def plane_distance_device(self, disparity, planes, points, conf=None, stream=None):
         """Enqueues the queries on `stream` and returns a uint8 tensor (K, 32) without
         synchronising.  planes: the uint8 tensor (P, 128) of fit_plane_device (a fit and its queries
         then chain on one stream with no host round trip) or host records; points: host (K, 4) /
         (K, 3) or a CUDA int32 (K, 4)."""
-        if not _is_cuda(disparity):
-            raise SDRError(-5, "plane_distance_device expects a CUDA float32 or int16 tensor")
-        dev = disparity.device
-        s = stream if stream is not None else torch.cuda.current_stream(dev.index)
-        with torch.cuda.stream(s):
-            d, conf = self._device_maps(disparity, conf)
-            F, H, W = d.shape
-            if _is_cuda(planes):
-                if planes.dtype != torch.uint8 or planes.numel() % 128:
-                    raise SDRError(-5, "device planes must be a uint8 tensor (P, 128)")
-                pl = planes.contiguous()
-                P = pl.numel() // 128
-            else:
-                host = np.ascontiguousarray(planes).reshape(-1).view(np.uint8).reshape(-1, 128)
-                P = host.shape[0]
-                pl = torch.from_numpy(host.copy()).to(dev) if P else None
-            if _is_cuda(points):
-                if points.dtype != torch.int32 or points.dim() != 2 or points.shape[1] != 4:
-                    raise SDRError(-5, "device points must be an int32 tensor (K, 4)")
-                qs = points.contiguous()
-            else:
-                qs = self._upload_segments(as_queries(points), dev, s)
-            K = qs.shape[0]
-            out = torch.empty((K, 32), dtype=torch.uint8, device=dev)
-            p = self._params(0)
-            p.profile = 0
-            check(lib().sdr_plane_distance_device(
-                d.data_ptr(), DISP_F32 if d.dtype == torch.float32 else DISP_S16, d.stride(1),
-                d.stride(1) * H if F == 1 else d.stride(0), W, H, F,
-                conf.data_ptr() if conf is not None else None, _Q(self.Q), ctypes.byref(p),
-                pl.data_ptr() if P else None, P, qs.data_ptr() if K else None, K,
-                out.data_ptr() if K else None, ctypes.c_void_p(s.cuda_stream)))
-        return out
+        return self._plane_queries_device("plane_distance_device", lib().sdr_plane_distance_device,
+                                          self._point_params, 32, disparity, planes, points, _POINTS, conf, stream)
 
     # ---- the relief of a region (sdr.h, "the relief of a region") ----
     def _relief_params(self, quantiles, band) -> ReliefParams:
@@ -601,33 +650,8 @@ class Ruler:
         if _is_cuda(disparity):
             out = self.relief_device(disparity, planes, regions, labels, conf, quantiles, band)
             return out.cpu().numpy().reshape(-1).view(RELIEF_DTYPE)
-        p = self._relief_params(quantiles, band)
-        if _is_cuda(planes):
-            planes = planes.cpu().numpy()
-        pl = np.ascontiguousarray(planes).reshape(-1).view(np.uint8).view(PLANE_DTYPE)
-        d, c, rs, fs = self._host_maps(disparity, conf)
-        F, H, W = d.shape
-        lab = None
-        if labels is not None:
-            if _is_cuda(labels):
-                labels = labels.cpu().numpy()
-            lab = np.asarray(labels)
-            if lab.dtype != np.uint8:
-                raise SDRError(-5, "labels must be uint8")
-            lab = np.ascontiguousarray(_frames3(lab, "labels"))
-            if lab.shape != d.shape:
-                raise SDRError(-1, "labels must have the disparity's shape")
-        qs = as_relief_queries(regions)
-        K, P = qs.shape[0], pl.shape[0]
-        out = np.zeros(K, RELIEF_DTYPE)
-        with _on_device(self.device):
-            rc = lib().sdr_plane_relief(
-                d.ctypes.data, DISP_F32 if d.dtype == np.float32 else DISP_S16, rs, fs, W, H, F,
-                c.ctypes.data if c is not None else None, lab.ctypes.data if lab is not None else None,
-                _Q(self.Q), ctypes.byref(p), pl.ctypes.data if P else None, P,
-                qs.ctypes.data if K else None, K, out.ctypes.data if K else None)
-        check(rc)
-        return out
+        return self._plane_queries(lib().sdr_plane_relief, lambda: self._relief_params(quantiles, band), RELIEF_DTYPE,
+                                   disparity, planes, regions, _REGIONS, conf, labels)
 
     def relief_device(self, disparity, planes, regions, labels=None, conf=None, quantiles=(50, 500, 950),
                       band: float = 0.0, stream=None):
@@ -635,45 +659,9 @@ class Ruler:
         (K, 128) without synchronising (view its host copy as RELIEF_DTYPE).  planes and labels: as
         find_planes_device returns them (a search and its relief then chain on one stream with no
         host round trip) or host arrays; regions: host rows or a CUDA int32 (K, 8)."""
-        if not _is_cuda(disparity):
-            raise SDRError(-5, "relief_device expects a CUDA float32 or int16 tensor")
-        p = self._relief_params(quantiles, band)
-        dev = disparity.device
-        s = stream if stream is not None else torch.cuda.current_stream(dev.index)
-        with torch.cuda.stream(s):
-            d, conf = self._device_maps(disparity, conf)
-            F, H, W = d.shape
-            if _is_cuda(planes):
-                if planes.dtype != torch.uint8 or planes.numel() % 128:
-                    raise SDRError(-5, "device planes must be a uint8 tensor (P, 128)")
-                pl = planes.contiguous()
-                P = pl.numel() // 128
-            else:
-                host = np.ascontiguousarray(planes).reshape(-1).view(np.uint8).reshape(-1, 128)
-                P = host.shape[0]
-                pl = torch.from_numpy(host.copy()).to(dev) if P else None
-            lab = None
-            if labels is not None:
-                lab = labels if _is_cuda(labels) else torch.from_numpy(np.ascontiguousarray(labels)).to(dev)
-                if lab.dtype != torch.uint8 or lab.numel() != d.numel():
-                    raise SDRError(-5, "labels must be a uint8 map of the disparity's shape")
-                lab = lab.contiguous()
-            if _is_cuda(regions):
-                if regions.dtype != torch.int32 or regions.dim() != 2 or regions.shape[1] != 8:
-                    raise SDRError(-5, "device regions must be an int32 tensor (K, 8)")
-                qs = regions.contiguous()
-            else:
-                qs = self._upload_segments(as_relief_queries(regions), dev, s)
-            K = qs.shape[0]
-            out = torch.empty((K, 128), dtype=torch.uint8, device=dev)
-            check(lib().sdr_plane_relief_device(
-                d.data_ptr(), DISP_F32 if d.dtype == torch.float32 else DISP_S16, d.stride(1),
-                d.stride(1) * H if F == 1 else d.stride(0), W, H, F,
-                conf.data_ptr() if conf is not None else None, lab.data_ptr() if lab is not None else None,
-                _Q(self.Q), ctypes.byref(p), pl.data_ptr() if P else None, P,
-                qs.data_ptr() if K else None, K, out.data_ptr() if K else None,
-                ctypes.c_void_p(s.cuda_stream)))
-        return out
+        return self._plane_queries_device("relief_device", lib().sdr_plane_relief_device,
+                                          lambda: self._relief_params(quantiles, band), 128, disparity, planes,
+                                          regions, _REGIONS, conf, stream, labels)
 
     # ---- the footprint of a region (sdr.h, "the footprint of a region") ----
     def _footprint_params(self, cell, grid, support, h_range) -> FootprintParams:
@@ -699,78 +687,18 @@ class Ruler:
         if _is_cuda(disparity):
             out = self.footprint_device(disparity, planes, regions, labels, conf, cell, grid, support, h_range)
             return out.cpu().numpy().reshape(-1).view(FOOTPRINT_DTYPE)
-        p = self._footprint_params(cell, grid, support, h_range)
-        if _is_cuda(planes):
-            planes = planes.cpu().numpy()
-        pl = np.ascontiguousarray(planes).reshape(-1).view(np.uint8).view(PLANE_DTYPE)
-        d, c, rs, fs = self._host_maps(disparity, conf)
-        F, H, W = d.shape
-        lab = None
-        if labels is not None:
-            if _is_cuda(labels):
-                labels = labels.cpu().numpy()
-            lab = np.asarray(labels)
-            if lab.dtype != np.uint8:
-                raise SDRError(-5, "labels must be uint8")
-            lab = np.ascontiguousarray(_frames3(lab, "labels"))
-            if lab.shape != d.shape:
-                raise SDRError(-1, "labels must have the disparity's shape")
-        qs = as_relief_queries(regions)
-        K, P = qs.shape[0], pl.shape[0]
-        out = np.zeros(K, FOOTPRINT_DTYPE)
-        with _on_device(self.device):
-            rc = lib().sdr_plane_footprint(
-                d.ctypes.data, DISP_F32 if d.dtype == np.float32 else DISP_S16, rs, fs, W, H, F,
-                c.ctypes.data if c is not None else None, lab.ctypes.data if lab is not None else None,
-                _Q(self.Q), ctypes.byref(p), pl.ctypes.data if P else None, P,
-                qs.ctypes.data if K else None, K, out.ctypes.data if K else None)
-        check(rc)
-        return out
+        return self._plane_queries(lib().sdr_plane_footprint,
+                                   lambda: self._footprint_params(cell, grid, support, h_range), FOOTPRINT_DTYPE,
+                                   disparity, planes, regions, _REGIONS, conf, labels)
 
     def footprint_device(self, disparity, planes, regions, labels=None, conf=None, cell: float = 4.0,
                          grid: int = 512, support: int = 4, h_range=None, stream=None):
         """Enqueues the footprints on `stream` (default: the current stream) and returns a uint8
         tensor (K, 256) without synchronising (view its host copy as FOOTPRINT_DTYPE).  The argument
         forms are relief_device's."""
-        if not _is_cuda(disparity):
-            raise SDRError(-5, "footprint_device expects a CUDA float32 or int16 tensor")
-        p = self._footprint_params(cell, grid, support, h_range)
-        dev = disparity.device
-        s = stream if stream is not None else torch.cuda.current_stream(dev.index)
-        with torch.cuda.stream(s):
-            d, conf = self._device_maps(disparity, conf)
-            F, H, W = d.shape
-            if _is_cuda(planes):
-                if planes.dtype != torch.uint8 or planes.numel() % 128:
-                    raise SDRError(-5, "device planes must be a uint8 tensor (P, 128)")
-                pl = planes.contiguous()
-                P = pl.numel() // 128
-            else:
-                host = np.ascontiguousarray(planes).reshape(-1).view(np.uint8).reshape(-1, 128)
-                P = host.shape[0]
-                pl = torch.from_numpy(host.copy()).to(dev) if P else None
-            lab = None
-            if labels is not None:
-                lab = labels if _is_cuda(labels) else torch.from_numpy(np.ascontiguousarray(labels)).to(dev)
-                if lab.dtype != torch.uint8 or lab.numel() != d.numel():
-                    raise SDRError(-5, "labels must be a uint8 map of the disparity's shape")
-                lab = lab.contiguous()
-            if _is_cuda(regions):
-                if regions.dtype != torch.int32 or regions.dim() != 2 or regions.shape[1] != 8:
-                    raise SDRError(-5, "device regions must be an int32 tensor (K, 8)")
-                qs = regions.contiguous()
-            else:
-                qs = self._upload_segments(as_relief_queries(regions), dev, s)
-            K = qs.shape[0]
-            out = torch.empty((K, 256), dtype=torch.uint8, device=dev)
-            check(lib().sdr_plane_footprint_device(
-                d.data_ptr(), DISP_F32 if d.dtype == torch.float32 else DISP_S16, d.stride(1),
-                d.stride(1) * H if F == 1 else d.stride(0), W, H, F,
-                conf.data_ptr() if conf is not None else None, lab.data_ptr() if lab is not None else None,
-                _Q(self.Q), ctypes.byref(p), pl.data_ptr() if P else None, P,
-                qs.data_ptr() if K else None, K, out.data_ptr() if K else None,
-                ctypes.c_void_p(s.cuda_stream)))
-        return out
+        return self._plane_queries_device("footprint_device", lib().sdr_plane_footprint_device,
+                                          lambda: self._footprint_params(cell, grid, support, h_range), 256, disparity,
+                                          planes, regions, _REGIONS, conf, stream, labels)
 
     # ---- XYZ-map mode (the reference's measurement) ----
     def measure_xyz(self, depth_map, segments):

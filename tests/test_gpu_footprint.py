@@ -26,7 +26,7 @@ from stereo_depth_ruler_amd.ruler import FOOTPRINT_DTYPE, PLANE_DTYPE, as_relief
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 Q = S.REFERENCE_Q
 EYE = np.eye(4)
-SLICE = 2048  # pixels a workgroup of the sweeps (csrc/sdr_footprint.hip, kFootSlice)
+SLICE = 2048  # pixels a workgroup of the sweeps (csrc/sdr_region.hpp, kRegionSlice)
 TILE = 16     # cells a side of a workgroup's tile in the cell pass (kFootTile)
 BATCH = 256   # queries a batch at most (kFootBatch); fewer when their grids would pass 64 MiB
 

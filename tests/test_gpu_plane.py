@@ -1,5 +1,5 @@
 """GPU: the plane fit and the point-to-plane distance (sdr_fit_planes*, sdr_plane_distance*,
-csrc/sdr_ruler.hip) through every layer, exact against the numpy restatement (tests/plane_ref.py):
+csrc/sdr_plane.hip) through every layer, exact against the numpy restatement (tests/plane_ref.py):
 doubles and floats as bit patterns, counts and flags exactly."""
 import ctypes
 import os

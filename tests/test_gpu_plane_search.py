@@ -1,4 +1,4 @@
-"""GPU: the plane search (sdr_find_planes*, csrc/sdr_ruler.hip) through every layer, exact against
+"""GPU: the plane search (sdr_find_planes*, csrc/sdr_plane.hip) through every layer, exact against
 the numpy restatement (tests/plane_search_ref.py): records as bit patterns (PR.assert_planes_equal),
 counts, rounds and labels exactly."""
 import os

@@ -26,7 +26,7 @@ from stereo_depth_ruler_amd.ruler import PLANE_DTYPE, RELIEF_DTYPE, as_relief_qu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 Q = S.REFERENCE_Q
 EYE = np.eye(4)
-SLICE = 2048  # pixels a workgroup of the sweeps (csrc/sdr_relief.hip, kReliefSlice)
+SLICE = 2048  # pixels a workgroup of the sweeps (csrc/sdr_region.hpp, kRegionSlice)
 
 
 @pytest.fixture(scope="module", autouse=True)
