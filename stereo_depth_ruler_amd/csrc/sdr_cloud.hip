@@ -16,7 +16,7 @@
 //                    centroids match bit for bit).  Sort and scan are hand-written (k_rs_*, k_scan_*):
 //                    no library on the path.
 #include "../../include/sdr/sdr.h"
-#include "sdr_internal.hpp"
+#include "sdr_host.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -309,13 +309,6 @@ __global__ __launch_bounds__(256) void k_voxel_join(const uint32_t* __restrict__
 
 namespace {
 
-#define CLOUD_HIP(call)                                                                          \
-    do {                                                                                         \
-        hipError_t e_ = (call);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return sdr::set_error(SDR_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 // The voxel grid's scratch: one grow-only device arena a call, leased from a list of idle arenas
 // and bump-allocated.  The call reports a count, so it synchronises its stream before it returns
 // and its arena goes back to the list idle (the lease synchronises again on an early exit).
@@ -384,7 +377,7 @@ int sdr_xyz_to_cloud_device(const float* d_xyz, const uint8_t* d_bgr, size_t bgr
     const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 8192);
     hipLaunchKernelGGL(sdr::k_xyz_to_cloud, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_xyz,
                        d_bgr, width, height, bgr_stride, bgr_frame_stride, n, (float4*)d_points);
-    CLOUD_HIP(hipGetLastError());
+    SDR_HIP(hipGetLastError());
     return SDR_OK;
 }
 
@@ -434,11 +427,11 @@ int sdr_voxel_grid_device(const void* d_points, int n, float lx, float ly, float
     if (!partial) return sdr::set_error(SDR_ERR_NOMEM, "scratch allocation failed");
     const int mmb = std::min(sdr::kMinMaxBlocks, (n + 255) / 256);
     hipLaunchKernelGGL(sdr::k_minmax, dim3(mmb), dim3(256), 0, st, p, n, partial);
-    CLOUD_HIP(hipGetLastError());
+    SDR_HIP(hipGetLastError());
     std::vector<float> hp((size_t)7 * mmb);
-    CLOUD_HIP(hipMemcpyAsync(hp.data(), partial, sizeof(float) * hp.size(), hipMemcpyDeviceToHost, st));
+    SDR_HIP(hipMemcpyAsync(hp.data(), partial, sizeof(float) * hp.size(), hipMemcpyDeviceToHost, st));
     VOXEL_MARK("mm_launch");
-    CLOUD_HIP(hipStreamSynchronize(st));
+    SDR_HIP(hipStreamSynchronize(st));
     VOXEL_MARK("mm_sync");
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     long long nfin = 0;
@@ -460,8 +453,8 @@ int sdr_voxel_grid_device(const void* d_points, int n, float lx, float ly, float
     if (prod > 2147483647LL) {
         // PCL: "Leaf size is too small for the input dataset. Integer indices would overflow." --
         // the output is the input cloud unchanged
-        CLOUD_HIP(hipMemcpyAsync(out, p, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, st));
-        CLOUD_HIP(hipStreamSynchronize(st));
+        SDR_HIP(hipMemcpyAsync(out, p, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, st));
+        SDR_HIP(hipStreamSynchronize(st));
         *out_count = n;
         if (passthrough) *passthrough = 1;
         return SDR_OK;
@@ -515,13 +508,13 @@ int sdr_voxel_grid_device(const void* d_points, int n, float lx, float ly, float
     hipLaunchKernelGGL(sdr::k_voxel_heads, grid, dim3(256), 0, st, sorted, n, head);
     scan(head, n, pos);
     hipLaunchKernelGGL(sdr::k_voxel_centroid, grid, dim3(256), 0, st, p, sorted, n, head, pos, out);
-    CLOUD_HIP(hipGetLastError());
+    SDR_HIP(hipGetLastError());
     VOXEL_MARK("launches");
     int last_pos = 0, last_head = 0;
-    CLOUD_HIP(hipMemcpyAsync(&last_pos, pos + n - 1, 4, hipMemcpyDeviceToHost, st));
-    CLOUD_HIP(hipMemcpyAsync(&last_head, head + n - 1, 4, hipMemcpyDeviceToHost, st));
+    SDR_HIP(hipMemcpyAsync(&last_pos, pos + n - 1, 4, hipMemcpyDeviceToHost, st));
+    SDR_HIP(hipMemcpyAsync(&last_head, head + n - 1, 4, hipMemcpyDeviceToHost, st));
     VOXEL_MARK("copies");
-    CLOUD_HIP(hipStreamSynchronize(st));
+    SDR_HIP(hipStreamSynchronize(st));
     VOXEL_MARK("sync");
     *out_count = last_pos + last_head;
     return SDR_OK;

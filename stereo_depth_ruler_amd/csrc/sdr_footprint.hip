@@ -470,7 +470,7 @@ int sdr_plane_footprint_device(const void* d_disp, int disp_type, size_t stride,
     // scratch of a batch: {grids, states}
     const size_t o_st = (size_t)KB * gbytes;
     char* sc = nullptr;
-    RULER_HIP(sdr::scratch_alloc((void**)&sc, o_st + (size_t)KB * sizeof(sdr::FootState), st));
+    SDR_HIP(sdr::scratch_alloc((void**)&sc, o_st + (size_t)KB * sizeof(sdr::FootState), st));
     unsigned* grids = (unsigned*)sc;
     sdr::FootState* states = (sdr::FootState*)(sc + o_st);
     const unsigned slices = sdr::region_slices(W, H);
@@ -494,9 +494,9 @@ int sdr_plane_footprint_device(const void* d_disp, int disp_type, size_t stride,
     for (int k0 = 0; k0 < K && e == hipSuccess; k0 += KB)
         with_disp(disp_type, d_disp, [&](auto* disp) { batch(disp, k0, std::min(K - k0, KB)); });
     const hipError_t le = hipGetLastError();
-    RULER_HIP(sdr::scratch_free(sc, st));
-    RULER_HIP(e);
-    RULER_HIP(le);
+    SDR_HIP(sdr::scratch_free(sc, st));
+    SDR_HIP(e);
+    SDR_HIP(le);
     return SDR_OK;
 }
 

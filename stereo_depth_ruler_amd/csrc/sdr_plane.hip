@@ -735,8 +735,8 @@ int sdr_fit_planes_device(const void* d_disp, int disp_type, size_t stride, size
     const int sweeps = params->iterations + 2;
     const size_t per = (size_t)sweeps * sdr::kPlaneSlots, bytes = (size_t)K * per * sizeof(long long);
     long long* acc = nullptr;
-    RULER_HIP(sdr::scratch_alloc((void**)&acc, bytes, st));
-    RULER_HIP(hipMemsetAsync(acc, 0, bytes, st));
+    SDR_HIP(sdr::scratch_alloc((void**)&acc, bytes, st));
+    SDR_HIP(hipMemsetAsync(acc, 0, bytes, st));
     const unsigned slices = sdr::region_slices(W, H);
     for (int s = 0; s < sweeps; s++)
         for (int k0 = 0; k0 < K; k0 += 65535) {  // the grid's y extent
@@ -750,8 +750,8 @@ int sdr_fit_planes_device(const void* d_disp, int disp_type, size_t stride, size
     hipLaunchKernelGGL(sdr::k_plane_finish, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, st, d_regions, K, W, H,
                        F, q, *params, (const long long*)acc, d_planes);
     const hipError_t le = hipGetLastError();
-    RULER_HIP(sdr::scratch_free(acc, st));
-    RULER_HIP(le);
+    SDR_HIP(sdr::scratch_free(acc, st));
+    SDR_HIP(le);
     return SDR_OK;
 }
 
@@ -785,7 +785,7 @@ int sdr_find_planes_device(const void* d_disp, int disp_type, size_t stride, siz
     const size_t o_hyp = (o_sc + (size_t)NP * M * sizeof(unsigned) + 63) & ~(size_t)63;
     const size_t o_lab = o_hyp + (size_t)M * sizeof(sdr::SearchHyp);
     char* sc = nullptr;
-    RULER_HIP(sdr::scratch_alloc((void**)&sc, o_lab + (d_labels ? 0 : px), st));
+    SDR_HIP(sdr::scratch_alloc((void**)&sc, o_lab + (d_labels ? 0 : px), st));
     sdr::SearchState* state = (sdr::SearchState*)sc;
     long long* acc = (long long*)(sc + o_acc);
     unsigned* scores = (unsigned*)(sc + o_sc);
@@ -795,7 +795,7 @@ int sdr_find_planes_device(const void* d_disp, int disp_type, size_t stride, siz
     if (e == hipSuccess) e = hipMemsetAsync(labels, 0xff, px, st);
     if (e != hipSuccess) {
         (void)sdr::scratch_free(sc, st);
-        RULER_HIP(e);
+        SDR_HIP(e);
     }
     const unsigned slices = sdr::region_slices(W, H);
     const dim3 sgrid(slices), sblock(sdr::kRegionThreads), dgrid((unsigned)((M + 63) / 64)), one(1), wave(64);
@@ -823,8 +823,8 @@ int sdr_find_planes_device(const void* d_disp, int disp_type, size_t stride, siz
     };
     for (int r = 0; r < NP; r++) with_disp(disp_type, d_disp, [&](auto* disp) { round(disp, r); });
     const hipError_t le = hipGetLastError();
-    RULER_HIP(sdr::scratch_free(sc, st));
-    RULER_HIP(le);
+    SDR_HIP(sdr::scratch_free(sc, st));
+    SDR_HIP(le);
     return SDR_OK;
 }
 
@@ -845,17 +845,17 @@ int sdr_find_planes(const void* disp, int disp_type, size_t stride, size_t frame
         (rc = sdr::ensure(S->segs, sizeof(sdr_segment))) || (rc = sdr::ensure(S->planes, (size_t)NP * sizeof(sdr_plane))) ||
         (rc = sdr::ensure(S->out, 16 + rbytes)) || (rc = sdr::ensure(S->prof, labels ? px : 0)))
         return rc;
-    RULER_HIP(hipMemcpyAsync(S->segs.p, region, sizeof(sdr_segment), hipMemcpyHostToDevice, S->st));
+    SDR_HIP(hipMemcpyAsync(S->segs.p, region, sizeof(sdr_segment), hipMemcpyHostToDevice, S->st));
     rc = sdr_find_planes_device(S->map.p, disp_type, (size_t)W, px, W, H, F, conf ? (const float*)S->conf.p : nullptr, Q,
                                 params, (const sdr_segment*)S->segs.p, (sdr_plane*)S->planes.p, (int32_t*)S->out.p,
                                 (sdr_plane_search_round*)((char*)S->out.p + 16), labels ? (uint8_t*)S->prof.p : nullptr,
                                 S->st);
     if (rc) return rc;
-    RULER_HIP(hipMemcpyAsync(planes, S->planes.p, (size_t)NP * sizeof(sdr_plane), hipMemcpyDeviceToHost, S->st));
-    RULER_HIP(hipMemcpyAsync(count, S->out.p, sizeof(int32_t), hipMemcpyDeviceToHost, S->st));
-    if (rounds) RULER_HIP(hipMemcpyAsync(rounds, (char*)S->out.p + 16, rbytes, hipMemcpyDeviceToHost, S->st));
-    if (labels) RULER_HIP(hipMemcpyAsync(labels, S->prof.p, px, hipMemcpyDeviceToHost, S->st));
-    RULER_HIP(hipStreamSynchronize(S->st));
+    SDR_HIP(hipMemcpyAsync(planes, S->planes.p, (size_t)NP * sizeof(sdr_plane), hipMemcpyDeviceToHost, S->st));
+    SDR_HIP(hipMemcpyAsync(count, S->out.p, sizeof(int32_t), hipMemcpyDeviceToHost, S->st));
+    if (rounds) SDR_HIP(hipMemcpyAsync(rounds, (char*)S->out.p + 16, rbytes, hipMemcpyDeviceToHost, S->st));
+    if (labels) SDR_HIP(hipMemcpyAsync(labels, S->prof.p, px, hipMemcpyDeviceToHost, S->st));
+    SDR_HIP(hipStreamSynchronize(S->st));
     return SDR_OK;
 }
 
@@ -874,7 +874,7 @@ int sdr_plane_distance_device(const void* d_disp, int disp_type, size_t stride, 
         hipLaunchKernelGGL(sdr::k_plane_distance<disp_elem_t<decltype(disp)>>, grid, block, 0, (hipStream_t)stream, disp,
                            stride, frame_stride, W, H, F, d_conf, q, *params, d_planes, P, d_queries, K, d_out);
     });
-    RULER_HIP(hipGetLastError());
+    SDR_HIP(hipGetLastError());
     return SDR_OK;
 }
 
@@ -890,13 +890,13 @@ int sdr_fit_planes(const void* disp, int disp_type, size_t stride, size_t frame_
         (rc = sdr::ensure(S->segs, (size_t)K * sizeof(sdr_segment))) ||
         (rc = sdr::ensure(S->planes, (size_t)K * sizeof(sdr_plane))))
         return rc;
-    RULER_HIP(hipMemcpyAsync(S->segs.p, regions, (size_t)K * sizeof(sdr_segment), hipMemcpyHostToDevice, S->st));
+    SDR_HIP(hipMemcpyAsync(S->segs.p, regions, (size_t)K * sizeof(sdr_segment), hipMemcpyHostToDevice, S->st));
     rc = sdr_fit_planes_device(S->map.p, disp_type, (size_t)W, (size_t)W * H, W, H, F,
                                conf ? (const float*)S->conf.p : nullptr, Q, params, (const sdr_segment*)S->segs.p,
                                K, (sdr_plane*)S->planes.p, S->st);
     if (rc) return rc;
-    RULER_HIP(hipMemcpyAsync(planes, S->planes.p, (size_t)K * sizeof(sdr_plane), hipMemcpyDeviceToHost, S->st));
-    RULER_HIP(hipStreamSynchronize(S->st));
+    SDR_HIP(hipMemcpyAsync(planes, S->planes.p, (size_t)K * sizeof(sdr_plane), hipMemcpyDeviceToHost, S->st));
+    SDR_HIP(hipStreamSynchronize(S->st));
     return SDR_OK;
 }
 
@@ -918,8 +918,8 @@ int sdr_plane_distance(const void* disp, int disp_type, size_t stride, size_t fr
                                    P ? (const sdr_plane*)S->planes.p : nullptr, P,
                                    (const sdr_plane_query*)S->segs.p, K, (struct sdr_plane_distance*)S->out.p, S->st);
     if (rc) return rc;
-    RULER_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(struct sdr_plane_distance), hipMemcpyDeviceToHost, S->st));
-    RULER_HIP(hipStreamSynchronize(S->st));
+    SDR_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(struct sdr_plane_distance), hipMemcpyDeviceToHost, S->st));
+    SDR_HIP(hipStreamSynchronize(S->st));
     return SDR_OK;
 }
 

@@ -16,7 +16,7 @@
 //                    (b) BGR2GRAY + INTER_AREA 0.5x of the rectified eye (the class path's
 //                        stereo_disparity.cpp:19-24 pre-steps), each rounding kept as OpenCV does
 #include "../../include/sdr/sdr.h"
-#include "sdr_internal.hpp"
+#include "sdr_host.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -221,13 +221,6 @@ struct sdr_rectifier {
 
 namespace {
 
-#define RECT_HIP(call)                                                                          \
-    do {                                                                                        \
-        hipError_t e_ = (call);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return sdr::set_error(SDR_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 // iR = inv(P[:, :3] * R): gemm with sums from k = 0, then cv::invert(DECOMP_LU)'s closed form
 // for n = 3 (det3, cofactors times 1/det); host f64, the same expression order as the oracle
 int make_map_params(const double K[9], const double* dist, int ndist, const double R[9],
@@ -278,7 +271,7 @@ int make_map_params(const double K[9], const double* dist, int ndist, const doub
 int enqueue_init_map(const sdr::MapParams& m, int W, int H, int16_t* map1, uint16_t* map2,
                      hipStream_t st) {
     hipLaunchKernelGGL(sdr::k_init_map, dim3((H + 63) / 64), dim3(64), 0, st, m, W, H, map1, map2);
-    RECT_HIP(hipGetLastError());
+    SDR_HIP(hipGetLastError());
     return SDR_OK;
 }
 
@@ -294,11 +287,11 @@ int sdr_init_undistort_rectify_map(const double K[9], const double* dist, int nd
     sdr::MapParams m;
     int rc = make_map_params(K, dist, ndist, R, P, p_cols, &m);
     if (rc) return rc;
-    RECT_HIP(hipSetDevice(device));
+    SDR_HIP(hipSetDevice(device));
     const size_t px = (size_t)W * H;
     int16_t* d1 = nullptr;
     uint16_t* d2 = nullptr;
-    RECT_HIP(hipMalloc((void**)&d1, px * 4));
+    SDR_HIP(hipMalloc((void**)&d1, px * 4));
     if (hipMalloc((void**)&d2, px * 2) != hipSuccess) {
         (void)hipFree(d1);
         return sdr::set_error(SDR_ERR_NOMEM, "hipMalloc failed");
@@ -323,7 +316,7 @@ int sdr_rectifier_create(const double K_left[9], const double* dist_left, int nd
     int rc;
     if ((rc = make_map_params(K_left, dist_left, ndist_left, R1, P1, p_cols, &ml))) return rc;
     if ((rc = make_map_params(K_right, dist_right, ndist_right, R2, P2, p_cols, &mr))) return rc;
-    RECT_HIP(hipSetDevice(device));
+    SDR_HIP(hipSetDevice(device));
     sdr_rectifier* h = new sdr_rectifier();
     h->device = device;
     h->W = W;
@@ -377,11 +370,11 @@ int sdr_rectifier_reset_stream(sdr_rectifier* h) {
 
 int sdr_rectifier_get_maps(const sdr_rectifier* h, int which, int16_t* map1, uint16_t* map2) {
     if (!h || (which != 0 && which != 1)) return sdr::set_error(SDR_ERR_ARG, "bad arguments");
-    RECT_HIP(hipSetDevice(h->device));
-    RECT_HIP(hipStreamSynchronize(h->stream));
+    SDR_HIP(hipSetDevice(h->device));
+    SDR_HIP(hipStreamSynchronize(h->stream));
     const size_t px = (size_t)h->W * h->H;
-    if (map1) RECT_HIP(hipMemcpy(map1, h->map1[which].p, px * 4, hipMemcpyDeviceToHost));
-    if (map2) RECT_HIP(hipMemcpy(map2, h->map2[which].p, px * 2, hipMemcpyDeviceToHost));
+    if (map1) SDR_HIP(hipMemcpy(map1, h->map1[which].p, px * 4, hipMemcpyDeviceToHost));
+    if (map2) SDR_HIP(hipMemcpy(map2, h->map2[which].p, px * 2, hipMemcpyDeviceToHost));
     return SDR_OK;
 }
 
@@ -403,7 +396,7 @@ int sdr_remap_bilinear_device(const uint8_t* src, int sw, int sh, size_t sstride
     else
         hipLaunchKernelGGL(sdr::k_remap<3>, grid, dim3(256), 0, st, src, sw, sh, sstride, sfstride,
                            map1, map2, dw, dh, dst, dstride, dfstride);
-    RECT_HIP(hipGetLastError());
+    SDR_HIP(hipGetLastError());
     return SDR_OK;
 }
 
@@ -412,7 +405,7 @@ int sdr_rectify_device(sdr_rectifier* h, const uint8_t* d_left, const uint8_t* d
                        uint8_t* d_left_out, uint8_t* d_right_out, size_t out_stride,
                        size_t out_frame_stride) {
     if (!h) return sdr::set_error(SDR_ERR_ARG, "null handle");
-    RECT_HIP(hipSetDevice(h->device));
+    SDR_HIP(hipSetDevice(h->device));
     int rc;
     const uint8_t* in[2] = {d_left, d_right};
     uint8_t* outp[2] = {d_left_out, d_right_out};
@@ -437,7 +430,7 @@ int sdr_rectify_sbs_device(sdr_rectifier* h, const uint8_t* d_sbs, size_t sbs_st
     if ((d_small_left || d_small_right) && ((h->W & 1) || (h->H & 1)))
         return sdr::set_error(SDR_ERR_SIZE, "INTER_AREA 0.5x needs even width and height");
     if (h->W < 2) return sdr::set_error(SDR_ERR_SIZE, "the SBS ingest needs eyes at least 2 pixels wide");
-    RECT_HIP(hipSetDevice(h->device));
+    SDR_HIP(hipSetDevice(h->device));
     sdr::SbsArgs a{};
     a.sbs = d_sbs;
     a.sstride = sbs_stride;
@@ -454,7 +447,7 @@ int sdr_rectify_sbs_device(sdr_rectifier* h, const uint8_t* d_sbs, size_t sbs_st
     a.small[1] = d_small_right;
     dim3 grid(((h->W + 1) / 2 + 63) / 64, ((h->H + 1) / 2 + 3) / 4, 2 * nframes);
     hipLaunchKernelGGL(sdr::k_sbs_ingest, grid, dim3(256), 0, h->stream, a);
-    RECT_HIP(hipGetLastError());
+    SDR_HIP(hipGetLastError());
     return SDR_OK;
 }
 

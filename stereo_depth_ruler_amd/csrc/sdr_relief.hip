@@ -377,7 +377,7 @@ int sdr_plane_relief_device(const void* d_disp, int disp_type, size_t stride, si
     const size_t o_h3 = o_h2 + (size_t)KB * nq * sdr::kReliefBins * sizeof(unsigned);
     const size_t bytes = o_h3 + (size_t)KB * nq * sdr::kReliefLastBins * sizeof(unsigned);
     char* sc = nullptr;
-    RULER_HIP(sdr::scratch_alloc((void**)&sc, bytes, st));
+    SDR_HIP(sdr::scratch_alloc((void**)&sc, bytes, st));
     sdr::ReliefState* states = (sdr::ReliefState*)sc;
     unsigned* h1 = (unsigned*)(sc + o_h1);
     unsigned* h2 = (unsigned*)(sc + o_h2);
@@ -409,9 +409,9 @@ int sdr_plane_relief_device(const void* d_disp, int disp_type, size_t stride, si
     for (int k0 = 0; k0 < K && e == hipSuccess; k0 += KB)
         with_disp(disp_type, d_disp, [&](auto* disp) { batch(disp, k0, std::min(K - k0, KB)); });
     const hipError_t le = hipGetLastError();
-    RULER_HIP(sdr::scratch_free(sc, st));
-    RULER_HIP(e);
-    RULER_HIP(le);
+    SDR_HIP(sdr::scratch_free(sc, st));
+    SDR_HIP(e);
+    SDR_HIP(le);
     return SDR_OK;
 }
 

@@ -343,7 +343,7 @@ int sdr_measure_disp_device(const void* d_disp, int disp_type, size_t stride, si
         hipLaunchKernelGGL(sdr::k_ruler<disp_elem_t<decltype(disp)>>, grid, block, 0, (hipStream_t)stream, disp, stride,
                            frame_stride, W, H, F, d_conf, q, *params, d_segs, d_out, d_profile);
     });
-    RULER_HIP(hipGetLastError());
+    SDR_HIP(hipGetLastError());
     return SDR_OK;
 }
 
@@ -355,7 +355,7 @@ int sdr_measure_xyz_device(const float* d_xyz, size_t xyz_stride, size_t xyz_fra
     if (K == 0) return SDR_OK;
     hipLaunchKernelGGL(sdr::k_ruler_xyz, dim3((unsigned)((K + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, d_xyz, xyz_stride, xyz_frame_stride, W, H, F, d_segs, K, d_out);
-    RULER_HIP(hipGetLastError());
+    SDR_HIP(hipGetLastError());
     return SDR_OK;
 }
 
@@ -374,16 +374,16 @@ int sdr_measure_disp(const void* disp, int disp_type, size_t stride, size_t fram
         (rc = sdr::ensure(S->out, (size_t)K * sizeof(sdr_measurement))) || (rc = sdr::ensure(S->prof, prof_bytes)) ||
         (rc = upload_maps(S, disp, disp_type, stride, frame_stride, W, H, F, conf)))
         return rc;
-    RULER_HIP(hipMemcpyAsync(S->segs.p, segs, (size_t)K * sizeof(sdr_segment), hipMemcpyHostToDevice, S->st));
+    SDR_HIP(hipMemcpyAsync(S->segs.p, segs, (size_t)K * sizeof(sdr_segment), hipMemcpyHostToDevice, S->st));
     // rows the kernel leaves untouched keep the caller's values
-    if (prof) RULER_HIP(hipMemcpyAsync(S->prof.p, profile, prof_bytes, hipMemcpyHostToDevice, S->st));
+    if (prof) SDR_HIP(hipMemcpyAsync(S->prof.p, profile, prof_bytes, hipMemcpyHostToDevice, S->st));
     rc = sdr_measure_disp_device(S->map.p, disp_type, (size_t)W, px, W, H, F, conf ? (const float*)S->conf.p : nullptr,
                                  Q, params, (const sdr_segment*)S->segs.p, K, (sdr_measurement*)S->out.p,
                                  prof ? (float*)S->prof.p : nullptr, S->st);
     if (rc) return rc;
-    RULER_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(sdr_measurement), hipMemcpyDeviceToHost, S->st));
-    if (prof) RULER_HIP(hipMemcpyAsync(profile, S->prof.p, prof_bytes, hipMemcpyDeviceToHost, S->st));
-    RULER_HIP(hipStreamSynchronize(S->st));
+    SDR_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(sdr_measurement), hipMemcpyDeviceToHost, S->st));
+    if (prof) SDR_HIP(hipMemcpyAsync(profile, S->prof.p, prof_bytes, hipMemcpyDeviceToHost, S->st));
+    SDR_HIP(hipStreamSynchronize(S->st));
     return SDR_OK;
 }
 
@@ -399,12 +399,12 @@ int sdr_measure_xyz(const float* xyz, size_t xyz_stride, size_t xyz_frame_stride
         (rc = sdr::ensure(S->out, (size_t)K * sizeof(sdr_measurement))))
         return rc;
     if ((rc = upload_rows(S->map.p, xyz, (size_t)W * 12, xyz_stride * 4, xyz_frame_stride * 4, H, F, S->st))) return rc;
-    RULER_HIP(hipMemcpyAsync(S->segs.p, segs, (size_t)K * sizeof(sdr_segment), hipMemcpyHostToDevice, S->st));
+    SDR_HIP(hipMemcpyAsync(S->segs.p, segs, (size_t)K * sizeof(sdr_segment), hipMemcpyHostToDevice, S->st));
     rc = sdr_measure_xyz_device((const float*)S->map.p, (size_t)W * 3, px * 3, W, H, F, (const sdr_segment*)S->segs.p,
                                 K, (sdr_measurement*)S->out.p, S->st);
     if (rc) return rc;
-    RULER_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(sdr_measurement), hipMemcpyDeviceToHost, S->st));
-    RULER_HIP(hipStreamSynchronize(S->st));
+    SDR_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(sdr_measurement), hipMemcpyDeviceToHost, S->st));
+    SDR_HIP(hipStreamSynchronize(S->st));
     return SDR_OK;
 }
 

@@ -9,7 +9,7 @@
 #include <type_traits>
 
 #include "sdr_device.hpp"
-#include "sdr_internal.hpp"
+#include "sdr_host.hpp"
 
 namespace sdr {
 
@@ -137,13 +137,6 @@ __device__ __forceinline__ RulerSample ruler_sample(const T* __restrict__ disp, 
 // ---- host side ----
 namespace ruler_host {
 
-#define RULER_HIP(call)                                                                          \
-    do {                                                                                         \
-        hipError_t e_ = (call);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return sdr::set_error(SDR_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 inline int rfail(int code, const char* msg) { return sdr::set_error(code, msg); }
 
 inline sdr::Q16 make_q16(const double* Q) {
@@ -211,11 +204,11 @@ struct HostState {
 inline int host_state(HostState** out) {
     static thread_local HostState S;
     int dev = 0;
-    RULER_HIP(hipGetDevice(&dev));
+    SDR_HIP(hipGetDevice(&dev));
     if (S.device != dev) {
         S.release();
-        RULER_HIP(hipSetDevice(dev));
-        RULER_HIP(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
+        SDR_HIP(hipSetDevice(dev));
+        SDR_HIP(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
         S.device = dev;
     }
     *out = &S;
@@ -226,7 +219,7 @@ inline int host_state(HostState** out) {
 inline int upload_rows(void* dst, const void* src, size_t row_bytes, size_t src_row, size_t src_frame, int H,
                        int F, hipStream_t st) {
     for (int f = 0; f < F; f++)
-        RULER_HIP(hipMemcpy2DAsync((char*)dst + (size_t)f * row_bytes * H, row_bytes,
+        SDR_HIP(hipMemcpy2DAsync((char*)dst + (size_t)f * row_bytes * H, row_bytes,
                                    (const char*)src + (size_t)f * src_frame, src_row, row_bytes, H,
                                    hipMemcpyHostToDevice, st));
     return SDR_OK;
@@ -240,7 +233,7 @@ inline int upload_maps(HostState* S, const void* disp, int disp_type, size_t str
     if ((rc = sdr::ensure(S->map, (size_t)F * px * es)) || (rc = sdr::ensure(S->conf, conf ? (size_t)F * px * 4 : 0)))
         return rc;
     if ((rc = upload_rows(S->map.p, disp, (size_t)W * es, stride * es, fstride * es, H, F, S->st))) return rc;
-    if (conf) RULER_HIP(hipMemcpyAsync(S->conf.p, conf, (size_t)F * px * 4, hipMemcpyHostToDevice, S->st));
+    if (conf) SDR_HIP(hipMemcpyAsync(S->conf.p, conf, (size_t)F * px * 4, hipMemcpyHostToDevice, S->st));
     return SDR_OK;
 }
 
@@ -252,9 +245,9 @@ inline int upload_queries(HostState* S, const sdr_plane* planes, int P, const vo
     if ((rc = sdr::ensure(S->segs, query_bytes)) || (rc = sdr::ensure(S->planes, (size_t)P * sizeof(sdr_plane))) ||
         (rc = sdr::ensure(S->prof, labels ? label_bytes : 0)) || (rc = sdr::ensure(S->out, out_bytes)))
         return rc;
-    RULER_HIP(hipMemcpyAsync(S->segs.p, queries, query_bytes, hipMemcpyHostToDevice, S->st));
-    if (P) RULER_HIP(hipMemcpyAsync(S->planes.p, planes, (size_t)P * sizeof(sdr_plane), hipMemcpyHostToDevice, S->st));
-    if (labels) RULER_HIP(hipMemcpyAsync(S->prof.p, labels, label_bytes, hipMemcpyHostToDevice, S->st));
+    SDR_HIP(hipMemcpyAsync(S->segs.p, queries, query_bytes, hipMemcpyHostToDevice, S->st));
+    if (P) SDR_HIP(hipMemcpyAsync(S->planes.p, planes, (size_t)P * sizeof(sdr_plane), hipMemcpyHostToDevice, S->st));
+    if (labels) SDR_HIP(hipMemcpyAsync(S->prof.p, labels, label_bytes, hipMemcpyHostToDevice, S->st));
     return SDR_OK;
 }
 
@@ -279,8 +272,8 @@ inline int region_host_call(Check check, Entry entry, const void* disp, int disp
                labels ? (const uint8_t*)S->prof.p : nullptr, Q, params, P ? (const sdr_plane*)S->planes.p : nullptr, P,
                (const sdr_relief_query*)S->segs.p, K, (Rec*)S->out.p, S->st);
     if (rc) return rc;
-    RULER_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(Rec), hipMemcpyDeviceToHost, S->st));
-    RULER_HIP(hipStreamSynchronize(S->st));
+    SDR_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(Rec), hipMemcpyDeviceToHost, S->st));
+    SDR_HIP(hipStreamSynchronize(S->st));
     return SDR_OK;
 }
 

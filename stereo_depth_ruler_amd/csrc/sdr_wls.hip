@@ -25,7 +25,7 @@
 // The FGS line solves are in sdr_fgs_seq.hip (SDR_FGS_THOMAS, the default) and sdr_fgs_pcr.hip
 // (SDR_FGS_PCR); launch_fgs here orchestrates them, and the filter's handle and C ABI follow it.
 #include "sdr_fgs.hpp"
-#include "sdr_internal.hpp"
+#include "sdr_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -483,13 +483,6 @@ struct sdr_wls {
 
 namespace {
 
-#define WLS_HIP(call)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return sdr::set_error(SDR_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 // The sequential solver's exact division needs every pass's pivots in [1, 2^126): each pass's
 // lambda (lambda * attenuation^k, in launch_fgs's float arithmetic) in [0, kFgsThomasMaxLambda]
 // (an attenuation above 1 or below 0 used to pass with only the first checked)
@@ -522,7 +515,7 @@ int upload_lut(sdr_wls* h, double sigma, const float** out) {
     if (h->lut_sigma != sigma) {
         std::vector<float> lut;
         sdr::fgs_lut_host(sigma, &lut);
-        WLS_HIP(hipMemcpy(h->lut.p, lut.data(), sizeof(float) * lut.size(), hipMemcpyHostToDevice));
+        SDR_HIP(hipMemcpy(h->lut.p, lut.data(), sizeof(float) * lut.size(), hipMemcpyHostToDevice));
         h->lut_sigma = sigma;
     }
     *out = (const float*)h->lut.p;
@@ -561,7 +554,7 @@ int sdr_wls_create(const sdr_wls_params* p, int device, sdr_wls** out) {
     if (!p || !out) return sdr::set_error(SDR_ERR_ARG, "null argument");
     int rc = check_wls_params(*p);
     if (rc) return rc;
-    WLS_HIP(hipSetDevice(device));
+    SDR_HIP(hipSetDevice(device));
     sdr_wls* h = new sdr_wls();
     h->p = *p;
     h->device = device;
@@ -637,7 +630,7 @@ int sdr::wls_filter_enqueue(sdr_wls* h, const int16_t* dl, const int16_t* dr, co
     if (W <= 0 || H <= 0 || F <= 0 || gstride < (size_t)W || (F > 1 && gfstride < gstride * H))
         return sdr::set_error(SDR_ERR_ARG, "bad size/stride");
     if (xyz && (!fout || !Q)) return sdr::set_error(SDR_ERR_ARG, "the fused reprojection needs fout and Q");
-    WLS_HIP(hipSetDevice(h->device));
+    SDR_HIP(hipSetDevice(h->device));
     hipStream_t st = h->stream;
     const sdr_wls_params& p = h->p;
     sdr::WlsGeom g{};
@@ -720,7 +713,7 @@ int sdr::wls_filter_enqueue(sdr_wls* h, const int16_t* dl, const int16_t* dr, co
             return sdr::set_error(SDR_ERR_SIZE, "SDR_FGS_PCR solves lines of at most 4096 samples "
                                                 "(use SDR_FGS_THOMAS for larger ROIs)");
         if (fin_fused) {
-            WLS_HIP(hipGetLastError());
+            SDR_HIP(hipGetLastError());
             return SDR_OK;
         }
     }
@@ -728,7 +721,7 @@ int sdr::wls_filter_enqueue(sdr_wls* h, const int16_t* dl, const int16_t* dr, co
         sdr::KScope kt(timer, SDR_KERNEL_WLS_FINAL);
         hipLaunchKernelGGL(sdr::k_wls_final, grid, blk, 0, st, A, B, g, wo);
     }
-    WLS_HIP(hipGetLastError());
+    SDR_HIP(hipGetLastError());
     return SDR_OK;
 }
 
@@ -745,7 +738,7 @@ int sdr_wls_filter(sdr_wls* h, const int16_t* dl, const int16_t* dr, const uint8
                    int H, size_t gstride, int16_t* out, float* conf) {
     if (!h || !dl || !dr || !guide || !out) return sdr::set_error(SDR_ERR_ARG, "null argument");
     if (W <= 0 || H <= 0 || gstride < (size_t)W) return sdr::set_error(SDR_ERR_ARG, "bad size/stride");
-    WLS_HIP(hipSetDevice(h->device));
+    SDR_HIP(hipSetDevice(h->device));
     const size_t px = (size_t)W * H;
     // device staging: dl, dr, guide, out (int16), conf (float)
     int rc;
@@ -757,14 +750,14 @@ int sdr_wls_filter(sdr_wls* h, const int16_t* dl, const int16_t* dr, const uint8
     int16_t* dout = ddr + px;
     uint8_t* dg = (uint8_t*)(dout + px);
     hipStream_t st = h->stream;
-    WLS_HIP(hipMemcpyAsync(ddl, dl, px * 2, hipMemcpyHostToDevice, st));
-    WLS_HIP(hipMemcpyAsync(ddr, dr, px * 2, hipMemcpyHostToDevice, st));
-    WLS_HIP(hipMemcpy2DAsync(dg, W, guide, gstride, W, H, hipMemcpyHostToDevice, st));
+    SDR_HIP(hipMemcpyAsync(ddl, dl, px * 2, hipMemcpyHostToDevice, st));
+    SDR_HIP(hipMemcpyAsync(ddr, dr, px * 2, hipMemcpyHostToDevice, st));
+    SDR_HIP(hipMemcpy2DAsync(dg, W, guide, gstride, W, H, hipMemcpyHostToDevice, st));
     if ((rc = sdr_wls_filter_device(h, ddl, ddr, dg, W, H, W, px, 1, dout, conf ? dconf : nullptr)))
         return rc;
-    WLS_HIP(hipMemcpyAsync(out, dout, px * 2, hipMemcpyDeviceToHost, st));
-    if (conf) WLS_HIP(hipMemcpyAsync(conf, dconf, px * 4, hipMemcpyDeviceToHost, st));
-    WLS_HIP(hipStreamSynchronize(st));
+    SDR_HIP(hipMemcpyAsync(out, dout, px * 2, hipMemcpyDeviceToHost, st));
+    if (conf) SDR_HIP(hipMemcpyAsync(conf, dconf, px * 4, hipMemcpyDeviceToHost, st));
+    SDR_HIP(hipStreamSynchronize(st));
     return SDR_OK;
 }
 
@@ -792,13 +785,13 @@ int sdr_fgs_filter_device(const uint8_t* d_guide, size_t gstride, int w, int h, 
     const size_t px = (size_t)w * h;
     // (frames of the sequential solver's padded layouts: fgs_pad4(w) * fgs_pad4(h) >= px samples)
     const size_t fp = (size_t)sdr::fgs_pad4(w) * sdr::fgs_pad4(h);
-    WLS_HIP(sdr::scratch_alloc((void**)&dlut, sizeof(float) * lut.size(), st));
+    SDR_HIP(sdr::scratch_alloc((void**)&dlut, sizeof(float) * lut.size(), st));
     // (FgsScratch: the sequential solver's two interleaved pass layouts, the weights, and 5 floats
     // a sample for each of its 2 * iters passes' coefficients; its loaders read up to
     // kFgsOverread bytes past an array)
     const size_t ncoef = solver == SDR_FGS_THOMAS ? (size_t)5 * (2 * iters) : 0;
-    WLS_HIP(sdr::scratch_alloc((void**)&scr, sizeof(float) * fp * (6 + ncoef) + sdr::kFgsOverread, st));
-    WLS_HIP(hipMemcpyAsync(dlut, lut.data(), sizeof(float) * lut.size(), hipMemcpyHostToDevice, st));
+    SDR_HIP(sdr::scratch_alloc((void**)&scr, sizeof(float) * fp * (6 + ncoef) + sdr::kFgsOverread, st));
+    SDR_HIP(hipMemcpyAsync(dlut, lut.data(), sizeof(float) * lut.size(), hipMemcpyHostToDevice, st));
     const sdr::FgsScratch fs{scr, scr + 2 * fp, scr + 4 * fp, scr + 5 * fp, scr + 6 * fp};
     // images are filtered in pairs (two right-hand sides of one system per line)
     for (int i = 0; i < nimg; i += 2) {
@@ -806,11 +799,11 @@ int sdr_fgs_filter_device(const uint8_t* d_guide, size_t gstride, int w, int h, 
         (void)sdr::launch_fgs(d_guide, gstride, 0, dlut, d_img + i * px, m == 2 ? d_img + (i + 1) * px : nullptr,
                               w, h, 1, lambda, att, iters, solver, fs, st);
     }
-    WLS_HIP(hipGetLastError());
-    WLS_HIP(sdr::scratch_free(dlut, st));
-    WLS_HIP(sdr::scratch_free(scr, st));
+    SDR_HIP(hipGetLastError());
+    SDR_HIP(sdr::scratch_free(dlut, st));
+    SDR_HIP(sdr::scratch_free(scr, st));
     // the host LUT vector dies here: wait for its upload before returning
-    WLS_HIP(hipStreamSynchronize(st));
+    SDR_HIP(hipStreamSynchronize(st));
     return SDR_OK;
 }
 

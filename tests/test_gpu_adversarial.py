@@ -217,3 +217,25 @@ def test_disparity_range_past_512_is_refused():
     with pytest.raises(sdr.SDRError) as e:
         sdr.StereoSGBM.create(0, 528, 5, 10, 100, 1, 63).compute(L, L)
     assert e.value.code == -8
+
+
+def test_3way_stripe_limit_is_refused_by_every_entry(oracle):
+    """MODE_SGBM_3WAY, 320x100 with nstripes = 30: 25 stripes, more top-to-bottom directions than a
+    path launch holds.  The host-pointer entry (refused before anything is uploaded) and the device
+    entry give the same status and text, and the handle computes again once nstripes fits."""
+    dev = torch.device("cuda", 0)
+    args = (0, 64, 3, 50, 300, 1, 63, 10, 0, 0, 2)
+    L, R = S.make_pair(100, 320, 64, seed=7)[:2]
+    m = sdr.StereoSGBM.create(*args, nstripes=30)
+    texts = []
+    for a, b in ((L, R), (torch.from_numpy(L).to(dev), torch.from_numpy(R).to(dev))):
+        with pytest.raises(sdr.SDRError) as e:
+            m.compute(a, b)
+        assert e.value.code == -1 and "too many 3WAY stripes" in str(e.value)
+        texts.append(str(e.value))
+    assert texts[0] == texts[1]
+    m._set("nstripes", 4)
+    ref = oracle.sgbm_compute(L, R, oracle.make_params(*args, nstripes=4))
+    assert np.array_equal(m.compute(L, R), ref)
+    assert np.array_equal(m.compute(torch.from_numpy(L).to(dev), torch.from_numpy(R).to(dev)).cpu().numpy(), ref)
+    m.close()
