@@ -638,11 +638,8 @@ int class_enqueue(sdr_sgbm* left, sdr_sgbm* right, sdr_wls* wls, const uint8_t* 
     if (wls) {
         // wls_filter->filter(disp_left, left_small, filtered, disp_right) (stereo_disparity.cpp:31)
         // with filtered_disp.convertTo(CV_32F, 1/16) (:34) and computeDepth (:76-80) in its epilogue
-        void* ws = sdr_wls_get_stream(wls);
-        (void)sdr_wls_set_stream(wls, st);
-        rc = sdr::wls_filter_enqueue(wls, dl, dr, sl, w2, h2, w2, px2, F, dw, d_conf, d_out, Q, d_xyz, left);
-        (void)sdr_wls_set_stream(wls, ws);
-        if (rc) return rc;
+        if ((rc = sdr::wls_filter_enqueue(wls, dl, dr, sl, w2, h2, w2, px2, F, dw, d_conf, d_out, Q, d_xyz, st, left)))
+            return rc;
     } else {
         if (d_filtered) SDR_HIP(hipMemcpyAsync(d_filtered, dl, F * px2 * 2, hipMemcpyDeviceToDevice, st));
         sdr::launch_disp16_to_f32(dl, d_out, F * px2, st);

@@ -1,9 +1,11 @@
 // sdr_fgs.hpp -- what the units of the WLS / FGS filter share: the filter's geometry and outputs,
 // the sequential solver's launch arguments, and the host entry points the units call on each other.
 // No kernels: every kernel is launched from the unit that defines it
-//   sdr_wls.hip      the WLS front and back ends, the FGS weights and layouts, launch_fgs, the C ABI
-//   sdr_fgs_seq.hip  the sequential solver (SDR_FGS_THOMAS): k_fgs_th, k_fgs_lr, k_fgs_lrjob
-//   sdr_fgs_pcr.hip  the opt-in solver (SDR_FGS_PCR): k_fgs_pcr
+//   sdr_wls_plan.hip     the plan of a call (sdr_wls_plan.hpp): refusals, path, lambdas, scratch layout
+//   sdr_wls.hip          the WLS front and back ends, the FGS weights and layouts; the stage launchers
+//   sdr_fgs_seq.hip      the sequential solver (SDR_FGS_THOMAS): k_fgs_th, k_fgs_lr, k_fgs_lrjob
+//   sdr_fgs_pcr.hip      the opt-in solver (SDR_FGS_PCR): k_fgs_pcr
+//   sdr_wls_entries.hip  the filter's handle and C ABI: a call's stages over (handle, plan)
 #pragma once
 #include "../../include/sdr/sdr.h"
 #include "sdr_device.hpp"
@@ -134,5 +136,25 @@ inline int pcr_lines(int n, int nlines) { return std::max(1, std::min(nlines, 10
 // fin_o the pass writes the filter's outputs instead.  -1: lines too long (kPcrMaxN, the LDS).
 int launch_pcr(float* U0, float* U1, const float* Cw, int w, int h, int F, int rows, float lam,
                hipStream_t st, const WlsGeom* fin_g = nullptr, const WlsOut* fin_o = nullptr);
+
+// ---- the stages of a planned call (sdr_wls.hip) ----
+struct WlsPlan;  // sdr_wls_plan.hpp
+// What a call's stages read and write; the sizes are the plan's (WlsLayout).
+struct WlsBufs {
+    const int16_t *dl, *dr;      // the two disparity maps (null: FGS alone)
+    const uint8_t* guide;        // the full frame's guide, rows gstride and frames gfstride apart
+    size_t gstride, gfstride;
+    const float* lut;            // the FGS weight table
+    float* conf;                 // the full-size confidence map, nullable
+    WlsOut out;
+    float* rdisc;                // the per-pixel front end's right discontinuity map
+    float *R0, *R1;              // the FGS right-hand sides, row-major over the ROI (R1 null: one)
+    FgsScratch s;
+};
+// timer (nullable): the matcher handle whose per-kernel timing records the launches
+void wls_front(const WlsPlan& pl, const WlsBufs& b, hipStream_t st, sdr_sgbm* timer);
+// the plan's solver on R0 / R1 in place; fused, its last pass writes b.out.  -1: see fgs_pcr
+int launch_fgs(const WlsPlan& pl, const WlsBufs& b, hipStream_t st, sdr_sgbm* timer);
+void wls_back(const WlsPlan& pl, const WlsBufs& b, hipStream_t st, sdr_sgbm* timer);
 
 }  // namespace sdr

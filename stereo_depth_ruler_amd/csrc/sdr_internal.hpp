@@ -318,11 +318,12 @@ struct KScope {
     }
 };
 
-// DisparityWLSFilter::filter on device (sdr_wls.hip) with the class path's fused epilogue:
+// DisparityWLSFilter::filter on device (sdr_wls_entries.hip) with the class path's fused epilogue:
 // fout (nullable) = out / 16, xyz (nullable, needs fout and Q) = reprojectImageTo3D(fout, Q);
-// timer (nullable): the matcher handle whose per-kernel timing records the filter's launches
+// st: the stream of this call (the handle's own binding is neither read nor changed); timer
+// (nullable): the matcher handle whose per-kernel timing records the filter's launches
 int wls_filter_enqueue(sdr_wls* h, const int16_t* dl, const int16_t* dr, const uint8_t* guide, int W,
                        int H, size_t gstride, size_t gfstride, int F, int16_t* out, float* conf,
-                       float* fout, const double* Q, float* xyz, sdr_sgbm* timer = nullptr);
+                       float* fout, const double* Q, float* xyz, hipStream_t st, sdr_sgbm* timer = nullptr);
 
 }  // namespace sdr

@@ -20,23 +20,17 @@
 //                  k_wls_prep has not written them)
 //   k_fgs_pack     row-major images -> the sequential solver's first-pass layout (transposed, both
 //                  right-hand sides interleaved), where k_wls_prep has not written it
-//   k_transpose2   LDS-tiled transpose of two arrays (64x64 tiles); no launch uses it at present
 //   k_wls_final    FGS(conf*d) / FGS(conf) -> saturate_cast<short>, 16*(min_disp-1) outside ROI
 // The FGS line solves are in sdr_fgs_seq.hip (SDR_FGS_THOMAS, the default) and sdr_fgs_pcr.hip
-// (SDR_FGS_PCR); launch_fgs here orchestrates them, and the filter's handle and C ABI follow it.
-#include "sdr_fgs.hpp"
-#include "sdr_host.hpp"
-
-#include <algorithm>
-#include <cmath>
-#include <string>
-#include <vector>
+// (SDR_FGS_PCR).  After the kernels come the stage launchers of a planned call (sdr_wls_plan.hpp):
+// wls_front, launch_fgs, wls_back; the handle and the C ABI that run them are in
+// sdr_wls_entries.hip.
+#include "sdr_internal.hpp"
+#include "sdr_wls_plan.hpp"
 
 #pragma clang fp contract(off)
 
 namespace sdr {
-
-constexpr int kFgsLevels = 65026;  // 255^2 + 1 squared differences of two 8-bit gray levels
 
 __device__ __forceinline__ int reflect101(int p, int len) {
     if (len == 1) return 0;
@@ -169,31 +163,6 @@ __global__ __launch_bounds__(256) void k_fgs_weights(const uint8_t* __restrict__
     }
     ChT[fo + (ch_rowmajor ? (size_t)i * w + j : (size_t)j * hp + i)] = ch;
     Cv[fo + (size_t)i * wp + j] = cv;
-}
-
-// dst[f][c][r] = src[f][r][c] for two arrays (rows x cols per frame), 64x64 LDS tiles
-__global__ __launch_bounds__(256) void k_transpose2(const float* __restrict__ s0,
-                                                    const float* __restrict__ s1, float* __restrict__ d0,
-                                                    float* __restrict__ d1, int rows, int cols) {
-    __shared__ float tile[2][64][65];
-    const int c0 = blockIdx.x * 64, r0 = blockIdx.y * 64;
-    const size_t fo = (size_t)blockIdx.z * rows * cols;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    for (int r = ty; r < 64; r += 4) {
-        const int rr = r0 + r, cc = c0 + tx;
-        if (rr < rows && cc < cols) {
-            tile[0][r][tx] = s0[fo + (size_t)rr * cols + cc];
-            if (s1) tile[1][r][tx] = s1[fo + (size_t)rr * cols + cc];
-        }
-    }
-    __syncthreads();
-    for (int c = ty; c < 64; c += 4) {
-        const int cc = c0 + c, rr = r0 + tx;
-        if (rr < rows && cc < cols) {
-            d0[fo + (size_t)cc * rows + rr] = tile[0][tx][c];
-            if (s1) d1[fo + (size_t)cc * rows + rr] = tile[1][tx][c];
-        }
-    }
 }
 
 // The whole filter front end of one ROI row in one workgroup (grid: rows x frames), replacing
@@ -362,475 +331,125 @@ __global__ __launch_bounds__(256) void k_wls_final(const float* __restrict__ A,
     wls_emit(wo, g, blockIdx.z, x, y, r);
 }
 
-// FastGlobalSmootherFilter::filter on R0 (and R1 when non-null: a second right-hand side of the
-// same systems), row-major w x h per frame, F frames with per-frame guides, in place.
-//   SDR_FGS_THOMAS: weights (ChT column-major = the row pass's k-major, Cv row-major = the column
-//                   pass's), the right-hand sides transposed into s.A (in_transposed: the caller
-//                   already wrote them there), one launch of coefficient jobs (every pass's
-//                   (a, den, 1/den, t)), then the passes alternating between the two layouts (row
-//                   pass: s.A -> s.B, column pass: s.B -> s.A; the last column pass into R0 / R1):
-//                   2 * iters + 1 launches, each on the kernel fgs_plan names (sdr_fgs_seq.hip)
-//   SDR_FGS_PCR:    weights (Ch, Cv row-major), then per iteration k_fgs_pcr over the rows and
-//                   over the columns of the images themselves (2 launches per iteration)
-static int launch_fgs(const uint8_t* guide, size_t gstride, size_t gfstride, const float* lut,
-                      float* R0, float* R1, int w, int h, int F, double lambda, double att,
-                      int iters, int solver, const FgsScratch& s, hipStream_t st,
-                      bool weights_ready = false, sdr_sgbm* timer = nullptr,
-                      const WlsGeom* fin_g = nullptr, const WlsOut* fin_o = nullptr,
-                      bool in_transposed = false) {
-    const size_t fs = (size_t)w * h;
-    const bool pcr = solver == SDR_FGS_PCR;
-    if (!weights_ready)
-        hipLaunchKernelGGL(k_fgs_weights, dim3((w + 63) / 64, (h + 3) / 4, F), dim3(256), 0, st, guide,
-                           gstride, gfstride, lut, w, h, pcr ? 1 : 0, s.ChT, s.Cv);
-    float lam = (float)lambda;
-    const float fa = (float)att;
-    if (!pcr) {
-        if (iters <= 0) return 0;
-        const bool two = R1 != nullptr;
-        if (!in_transposed)
-            hipLaunchKernelGGL(k_fgs_pack, dim3((w + 63) / 64, (h + 63) / 64, F), dim3(256), 0, st, R0, R1, s.A, h, w);
-        const int npass = 2 * iters;
-        // pass p: iteration p / 2, rows (even p: lines = rows, k = column) or columns (odd p);
-        // k-major arrays with sample rows of fgs_pad4(lines)
-        const int wp = fgs_pad4(w), hp = fgs_pad4(h);
-        const size_t fsp = (size_t)wp * hp;
-        std::vector<float> lams(iters);
-        for (int it = 0; it < iters; it++, lam = lam * fa) lams[it] = lam;  // lambda *= attenuation
-        auto pass_args = [&](int p) {
-            FgsThArgs a{};
-            const bool rows = (p & 1) == 0;
-            fgs_pass_shape(p, w, h, &a.nl, &a.n);
-            a.st = rows ? hp : wp;
-            a.onp = rows ? wp : hp;
-            a.fs = fsp;
-            a.ost = (size_t)w;
-            a.ofs = fs;
-            // rows: transposed (s.A) -> row-major (s.B); columns: row-major (s.B) -> transposed (s.A),
-            // the last pass split back into R0 / R1
-            a.U = rows ? s.A : s.B;
-            const bool last = p == npass - 1;
-            a.O = last ? nullptr : rows ? s.B : s.A;
-            a.O0 = last ? R0 : nullptr;
-            a.O1 = last ? R1 : nullptr;
-            // the pass's coefficient block: float4 (a, den, 1/den, t), then t alone
-            float* cb = s.coef + (size_t)p * 5 * F * fsp;
-            a.coef = (const float4*)cb;
-            a.tt = cb + 4 * F * fsp;
-            return a;
-        };
-        // the coefficient jobs of every pass (kFgsMaxJobs a launch), then the passes, each on the
-        // kernel the plan names
-        const FgsPlan plan = fgs_plan(w, h, F, two, iters, device_cus());
-        for (int p0 = 0; p0 < npass; p0 += kFgsMaxJobs) {
-            FgsThArgs c{};
-            c.fs = fsp;
-            for (int p = p0; p < npass && c.njobs < kFgsMaxJobs; p++) {
-                const FgsThArgs q = pass_args(p);
-                const bool rows = (p & 1) == 0;
-                FgsCoefJob& j = c.job[c.njobs++];
-                j.Cw = rows ? s.ChT : s.Cv;
-                j.coef = (float4*)q.coef;
-                j.tt = (float*)q.tt;
-                j.lam = lams[p / 2];
-                j.nl = q.nl;
-                j.n = q.n;
-                j.st = q.st;
-            }
-            KScope kt(timer, SDR_KERNEL_FGS_COEF);
-            launch_fgs_jobs(c, &plan.job[p0], two, F, st);
-        }
-        for (int p = 0; p < npass; p++) {
-            KScope kt(timer, SDR_KERNEL_FGS);
-            launch_fgs_pass(pass_args(p), plan.pass[p], two, F, st);
-        }
-        return 0;
+// ---- the stages of a planned call (sdr_wls_plan.hpp), in launch order ----
+
+// The front end: the confidence map and the FGS right-hand sides.  Fused (k_wls_prep) it also
+// writes the row's FGS weights and, when the outputs are fused too, the pixels outside the ROI.
+void wls_front(const WlsPlan& pl, const WlsBufs& b, hipStream_t st, sdr_sgbm* timer) {
+    const WlsGeom& g = pl.g;
+    const dim3 blk(256);
+    KScope kt(timer, SDR_KERNEL_WLS_PREP);
+    if (pl.fused) {
+        auto* prep = g.radius <= 4 ? k_wls_prep<4> : k_wls_prep<9>;
+        // the sequential solver's first pass (rows) reads the right-hand sides transposed and
+        // interleaved: k_wls_prep writes them into its pass buffer directly
+        float* Ain = pl.rowmajor ? b.R0 : b.s.A;
+        float* Bin = pl.rowmajor ? b.R1 : nullptr;
+        hipLaunchKernelGGL(prep, dim3(g.H, pl.F), blk, (size_t)g.rw * 32, st, b.dl, b.dr, g, b.guide, b.gstride,
+                           b.gfstride, b.lut, pl.rowmajor ? 1 : 0, b.conf, Ain, Bin, b.s.ChT, b.s.Cv,
+                           pl.fin_fused ? 1 : 0, b.out);
+        return;
     }
-    for (int it = 0; it < iters; it++) {
+    if (pl.roi)
+        hipLaunchKernelGGL(k_wls_disc, dim3((g.rw + 63) / 64, (g.rh + 3) / 4, pl.F), blk, 0, st, b.dr, g, b.rdisc);
+    hipLaunchKernelGGL(k_wls_conf, dim3((g.W + 63) / 64, (g.H + 3) / 4, pl.F), blk, 0, st, b.dl, b.dr,
+                       (const float*)b.rdisc, g, b.conf, b.R0, b.R1);
+}
+
+// Pass p of the sequential solver: iteration p / 2, rows (even p: lines = rows, k = column) or
+// columns (odd p); k-major arrays with sample rows of fgs_pad4(lines)
+static FgsThArgs pass_args(const WlsPlan& pl, const WlsBufs& b, int p) {
+    const int w = pl.g.rw, h = pl.g.rh, wp = fgs_pad4(w), hp = fgs_pad4(h);
+    FgsThArgs a{};
+    const bool rows = (p & 1) == 0;
+    fgs_pass_shape(p, w, h, &a.nl, &a.n);
+    a.st = rows ? hp : wp;
+    a.onp = rows ? wp : hp;
+    a.fs = pl.fsp;
+    a.ost = (size_t)w;
+    a.ofs = (size_t)w * h;
+    // rows: transposed (s.A) -> row-major (s.B); columns: row-major (s.B) -> transposed (s.A),
+    // the last pass split back into R0 / R1
+    a.U = rows ? b.s.A : b.s.B;
+    const bool last = p == 2 * pl.iters - 1;
+    a.O = last ? nullptr : rows ? b.s.B : b.s.A;
+    a.O0 = last ? b.R0 : nullptr;
+    a.O1 = last ? b.R1 : nullptr;
+    // the pass's coefficient block: float4 (a, den, 1/den, t), then t alone
+    float* cb = b.s.coef + pl.coef_off(p);
+    a.coef = (const float4*)cb;
+    a.tt = cb + 4 * pl.F * pl.fsp;
+    return a;
+}
+
+// SDR_FGS_THOMAS: the right-hand sides transposed into s.A (fused: k_wls_prep already wrote them
+// there), the coefficient jobs of every pass ((a, den, 1/den, t), kFgsMaxJobs a launch), then the
+// passes alternating between the two layouts (row pass: s.A -> s.B, column pass: s.B -> s.A; the
+// last column pass into R0 / R1): 2 * iters + 1 launches, each on the kernel the plan names
+// (sdr_fgs_seq.hip)
+static void fgs_thomas(const WlsPlan& pl, const WlsBufs& b, hipStream_t st, sdr_sgbm* timer) {
+    const int w = pl.g.rw, h = pl.g.rh, F = pl.F, npass = 2 * pl.iters;
+    if (!pl.fused)
+        hipLaunchKernelGGL(k_fgs_pack, dim3((w + 63) / 64, (h + 63) / 64, F), dim3(256), 0, st, b.R0, b.R1, b.s.A, h, w);
+    for (int p0 = 0; p0 < npass; p0 += kFgsMaxJobs) {
+        FgsThArgs c{};
+        c.fs = pl.fsp;
+        for (int p = p0; p < npass && c.njobs < kFgsMaxJobs; p++) {
+            const FgsThArgs q = pass_args(pl, b, p);
+            FgsCoefJob& j = c.job[c.njobs++];
+            j.Cw = (p & 1) == 0 ? b.s.ChT : b.s.Cv;
+            j.coef = (float4*)q.coef;
+            j.tt = (float*)q.tt;
+            j.lam = pl.lam[p / 2];
+            j.nl = q.nl;
+            j.n = q.n;
+            j.st = q.st;
+        }
+        KScope kt(timer, SDR_KERNEL_FGS_COEF);
+        launch_fgs_jobs(c, &pl.fgs.job[p0], pl.two, F, st);
+    }
+    for (int p = 0; p < npass; p++) {
+        KScope kt(timer, SDR_KERNEL_FGS);
+        launch_fgs_pass(pass_args(pl, b, p), pl.fgs.pass[p], pl.two, F, st);
+    }
+}
+
+// SDR_FGS_PCR: per iteration k_fgs_pcr over the rows and over the columns of the images themselves
+// (2 launches per iteration); fused, the last column pass writes the filter's outputs itself.
+// launch_pcr's -1 is left for its fallback when the device's LDS attribute cannot be read (64 KiB
+// assumed): no size the plan accepts reaches it on gfx950, whose 160 KiB hold kPcrMaxN samples.
+static int fgs_pcr(const WlsPlan& pl, const WlsBufs& b, hipStream_t st, sdr_sgbm* timer) {
+    for (int it = 0; it < pl.iters; it++)
         for (int rows = 1; rows >= 0; rows--) {
             KScope kt(timer, SDR_KERNEL_FGS);
-            // the last column pass writes the filter's outputs itself (fin_g / fin_o)
-            const bool fin = !rows && fin_g && R1 && it == iters - 1;
-            if (launch_pcr(R0, R1, rows ? s.ChT : s.Cv, w, h, F, rows, lam, st, fin ? fin_g : nullptr,
-                           fin ? fin_o : nullptr))
+            const bool fin = !rows && pl.fin_fused && it == pl.iters - 1;
+            if (launch_pcr(b.R0, b.R1, rows ? b.s.ChT : b.s.Cv, pl.g.rw, pl.g.rh, pl.F, rows, pl.lam[it], st,
+                           fin ? &pl.g : nullptr, fin ? &b.out : nullptr))
                 return -1;
         }
-        lam = lam * fa;  // FastGlobalSmootherFilterImpl::filter: lambda *= lambda_attenuation
-    }
     return 0;
 }
 
-// ComputeLUT_ParBody: LUT[i] = -exp(-sqrt((float)i) / sigmaColor), float math on the host
-static void fgs_lut_host(double sigma, std::vector<float>* lut) {
-    lut->resize(kFgsLevels);
-    const float s = (float)sigma;
-    for (int i = 0; i < kFgsLevels; i++) (*lut)[i] = -expf(-sqrtf((float)i) / s);
+// FastGlobalSmootherFilter::filter on R0 (and R1 when the plan has two right-hand sides of the same
+// systems), row-major rw x rh per frame, F frames with per-frame guides, in place: the weights
+// (where k_wls_prep has not written them: ChT column-major = the sequential row pass's k-major, or
+// row-major for k_fgs_pcr; Cv row-major), then the plan's solver.
+int launch_fgs(const WlsPlan& pl, const WlsBufs& b, hipStream_t st, sdr_sgbm* timer) {
+    const WlsGeom& g = pl.g;
+    if (!pl.fused)
+        hipLaunchKernelGGL(k_fgs_weights, dim3((g.rw + 63) / 64, (g.rh + 3) / 4, pl.F), dim3(256), 0, st,
+                           b.guide + (size_t)g.ry * b.gstride + g.rx, b.gstride, b.gfstride, b.lut, g.rw, g.rh,
+                           pl.rowmajor ? 1 : 0, b.s.ChT, b.s.Cv);
+    if (pl.rowmajor) return fgs_pcr(pl, b, st, timer);
+    fgs_thomas(pl, b, st, timer);
+    return 0;
+}
+
+// The back end, where the last FGS pass has not written the outputs itself.
+void wls_back(const WlsPlan& pl, const WlsBufs& b, hipStream_t st, sdr_sgbm* timer) {
+    const WlsGeom& g = pl.g;
+    KScope kt(timer, SDR_KERNEL_WLS_FINAL);
+    hipLaunchKernelGGL(k_wls_final, dim3((g.W + 63) / 64, (g.H + 3) / 4, pl.F), dim3(256), 0, st, b.R0, b.R1, g, b.out);
 }
 
 }  // namespace sdr
-
-// ===========================================================================================
-// C ABI (include/sdr/sdr.h)
-// ===========================================================================================
-struct sdr_wls {
-    sdr_wls_params p{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t own_stream = nullptr;
-    sdr::Buf rdisc, conf, A, B, Ac, Bc, ChT, Cv, lut, out, hbuf, coef;
-    double lut_sigma = -1.0;
-};
-
-namespace {
-
-// The sequential solver's exact division needs every pass's pivots in [1, 2^126): each pass's
-// lambda (lambda * attenuation^k, in launch_fgs's float arithmetic) in [0, kFgsThomasMaxLambda]
-// (an attenuation above 1 or below 0 used to pass with only the first checked)
-bool thomas_lambdas_ok(double lambda, double att, int iters) {
-    float lam = (float)lambda;
-    const float fa = (float)att;
-    for (int it = 0; it < iters; it++, lam = lam * fa)
-        if (!(lam >= 0.0f) || !((double)lam <= sdr::kFgsThomasMaxLambda)) return false;
-    return true;
-}
-constexpr const char* kThomasLambdaMsg =
-    "SDR_FGS_THOMAS needs every pass's lambda * attenuation^k in [0, 2^100] (its pivots stay in [1, 2^126))";
-
-int check_wls_params(const sdr_wls_params& p) {
-    if (!(p.lambda >= 0.0) || !(p.sigma_color >= 0.0) || p.num_iter < 1)
-        return sdr::set_error(SDR_ERR_ARG, "FGS needs lambda >= 0, sigma_color >= 0, num_iter >= 1");
-    if (p.fgs_solver == SDR_FGS_THOMAS && !thomas_lambdas_ok(p.lambda, p.lambda_attenuation, p.num_iter))
-        return sdr::set_error(SDR_ERR_ARG, kThomasLambdaMsg);
-    if (p.fgs_solver != SDR_FGS_PCR && p.fgs_solver != SDR_FGS_THOMAS)
-        return sdr::set_error(SDR_ERR_ARG, "fgs_solver must be SDR_FGS_PCR or SDR_FGS_THOMAS");
-    if (p.depth_discontinuity_radius < 0 || p.left_offset < 0 || p.right_offset < 0 ||
-        p.top_offset < 0 || p.bottom_offset < 0)
-        return sdr::set_error(SDR_ERR_ARG, "negative WLS radius or offset");
-    return SDR_OK;
-}
-
-int upload_lut(sdr_wls* h, double sigma, const float** out) {
-    int rc;
-    if ((rc = sdr::ensure(h->lut, sizeof(float) * sdr::kFgsLevels))) return rc;
-    if (h->lut_sigma != sigma) {
-        std::vector<float> lut;
-        sdr::fgs_lut_host(sigma, &lut);
-        SDR_HIP(hipMemcpy(h->lut.p, lut.data(), sizeof(float) * lut.size(), hipMemcpyHostToDevice));
-        h->lut_sigma = sigma;
-    }
-    *out = (const float*)h->lut.p;
-    return SDR_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-void sdr_wls_params_for_sgbm(sdr_sgbm_params* m, sdr_wls_params* p) {
-    if (!m || !p) return;
-    // createDisparityWLSFilter(Ptr<StereoMatcher>) [ximgproc disparity_filters.cpp]:
-    // setDisp12MaxDiff(1000000), setSpeckleWindowSize(0), and for SGBM setUniquenessRatio(0);
-    // offsets (max(0, minD+numD), max(0, -minD), 0, 0); radius ceil(0.5 * blockSize)
-    m->disp12MaxDiff = 1000000;
-    m->speckleWindowSize = 0;
-    m->uniquenessRatio = 0;
-    const int l = m->minDisparity + m->numDisparities;
-    p->lambda = 8000.0;
-    p->sigma_color = 1.5;
-    p->lrc_thresh = 24;
-    p->depth_discontinuity_radius = (int)std::ceil(0.5 * m->blockSize);
-    p->roll_off = 0.001f;
-    p->lambda_attenuation = 0.25;
-    p->num_iter = 3;
-    p->left_offset = l > 0 ? l : 0;
-    p->right_offset = m->minDisparity < 0 ? -m->minDisparity : 0;
-    p->top_offset = 0;
-    p->bottom_offset = 0;
-    p->min_disp = m->minDisparity;
-    p->fgs_solver = SDR_FGS_THOMAS;  // ximgproc's own elimination order (sdr.h)
-}
-
-int sdr_wls_create(const sdr_wls_params* p, int device, sdr_wls** out) {
-    if (!p || !out) return sdr::set_error(SDR_ERR_ARG, "null argument");
-    int rc = check_wls_params(*p);
-    if (rc) return rc;
-    SDR_HIP(hipSetDevice(device));
-    sdr_wls* h = new sdr_wls();
-    h->p = *p;
-    h->device = device;
-    if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) {
-        delete h;
-        return sdr::set_error(SDR_ERR_DEVICE, "hipStreamCreate failed");
-    }
-    h->stream = h->own_stream;
-    *out = h;
-    return SDR_OK;
-}
-
-int sdr_wls_destroy(sdr_wls* h) {
-    if (!h) return SDR_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (sdr::Buf* b : {&h->rdisc, &h->conf, &h->A, &h->B, &h->Ac, &h->Bc, &h->ChT, &h->Cv,
-                        &h->lut, &h->out, &h->hbuf, &h->coef})
-        if (b->p) (void)hipFree(b->p);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    delete h;
-    return SDR_OK;
-}
-
-int sdr_wls_set_params(sdr_wls* h, const sdr_wls_params* p) {
-    if (!h || !p) return sdr::set_error(SDR_ERR_ARG, "null argument");
-    int rc = check_wls_params(*p);
-    if (rc) return rc;
-    h->p = *p;
-    return SDR_OK;
-}
-
-int sdr_wls_get_params(const sdr_wls* h, sdr_wls_params* p) {
-    if (!h || !p) return sdr::set_error(SDR_ERR_ARG, "null argument");
-    *p = h->p;
-    return SDR_OK;
-}
-
-int sdr_wls_set_stream(sdr_wls* h, void* stream) {
-    if (!h) return sdr::set_error(SDR_ERR_ARG, "null handle");
-    h->stream = (hipStream_t)stream;  // NULL = the HIP null (legacy default) stream
-    return SDR_OK;
-}
-
-int sdr_wls_reset_stream(sdr_wls* h) {
-    if (!h) return sdr::set_error(SDR_ERR_ARG, "null handle");
-    h->stream = h->own_stream;
-    return SDR_OK;
-}
-
-void* sdr_wls_get_stream(const sdr_wls* h) { return h ? (void*)h->stream : nullptr; }
-
-int sdr_wls_get_roi(const sdr_wls* h, int W, int H, int roi[4]) {
-    if (!h || !roi) return sdr::set_error(SDR_ERR_ARG, "null argument");
-    roi[0] = h->p.left_offset;
-    roi[1] = h->p.top_offset;
-    roi[2] = W - h->p.left_offset - h->p.right_offset;
-    roi[3] = H - h->p.top_offset - h->p.bottom_offset;
-    return SDR_OK;
-}
-
-}  // extern "C"
-
-// DisparityWLSFilter::filter on device with the class path's optional fused epilogue (fout =
-// out / 16, xyz = reprojectImageTo3D(fout, Q)); sdr_wls_filter_device is this with neither.
-// ROIs up to kPcrMaxN columns take the fused front end (k_wls_prep: discontinuity maps, LR check,
-// confidence, FGS weights in one launch); wider ones the per-pixel k_wls_disc / k_wls_conf /
-// k_fgs_weights kernels.
-int sdr::wls_filter_enqueue(sdr_wls* h, const int16_t* dl, const int16_t* dr, const uint8_t* guide,
-                            int W, int H, size_t gstride, size_t gfstride, int F, int16_t* out,
-                            float* conf, float* fout, const double* Q, float* xyz, sdr_sgbm* timer) {
-    if (!h || !dl || !dr || !guide || !out) return sdr::set_error(SDR_ERR_ARG, "null argument");
-    if (W <= 0 || H <= 0 || F <= 0 || gstride < (size_t)W || (F > 1 && gfstride < gstride * H))
-        return sdr::set_error(SDR_ERR_ARG, "bad size/stride");
-    if (xyz && (!fout || !Q)) return sdr::set_error(SDR_ERR_ARG, "the fused reprojection needs fout and Q");
-    SDR_HIP(hipSetDevice(h->device));
-    hipStream_t st = h->stream;
-    const sdr_wls_params& p = h->p;
-    sdr::WlsGeom g{};
-    g.W = W;
-    g.H = H;
-    g.rx = p.left_offset;
-    g.ry = p.top_offset;
-    g.rw = W - p.left_offset - p.right_offset;
-    g.rh = H - p.top_offset - p.bottom_offset;
-    g.rrx = W - (g.rx + g.rw);
-    g.radius = p.depth_discontinuity_radius;
-    const int k = 2 * g.radius + 1;
-    g.scale = 1.0 / (double)(k * k);
-    g.roll_off = p.roll_off;
-    g.lrc_thresh = p.lrc_thresh;
-    g.fill = 16 * (p.min_disp - 1);
-    const size_t px = (size_t)W * H;
-    const bool roi = g.rw > 0 && g.rh > 0;
-    if (roi && p.fgs_solver == SDR_FGS_PCR && (g.rw > sdr::kPcrMaxN || g.rh > sdr::kPcrMaxN))
-        return sdr::set_error(SDR_ERR_SIZE, "SDR_FGS_PCR solves lines of at most 4096 samples "
-                                            "(use SDR_FGS_THOMAS for larger ROIs)");
-    const bool fused = roi && g.rw <= sdr::kPcrMaxN && g.radius <= 9;
-    const size_t cpx = roi ? (size_t)g.rw * g.rh : 0;
-    int rc;
-    const float* lut = nullptr;
-    if (!fused && (rc = sdr::ensure(h->rdisc, F * px * 4))) return rc;
-    // the sequential solver's k-major arrays: sample rows padded to 4 lines (fgs_pad4), and room
-    // for its loaders' reads past the last row (kFgsOverread)
-    const size_t cpp = roi ? (size_t)sdr::fgs_pad4(g.rw) * sdr::fgs_pad4(g.rh) : 0;
-    const size_t ov = sdr::kFgsOverread;
-    for (sdr::Buf* b : {&h->A, &h->B})
-        if ((rc = sdr::ensure(*b, F * cpx * 4 + 4))) return rc;
-    for (sdr::Buf* b : {&h->ChT, &h->Cv})
-        if ((rc = sdr::ensure(*b, F * cpp * 4 + ov))) return rc;
-    if (p.fgs_solver == SDR_FGS_THOMAS) {
-        // the two pass layouts (both right-hand sides interleaved) and every pass's elimination
-        // coefficients (float4 (a, den, 1/den, t) and t: 20 bytes a sample and pass)
-        for (sdr::Buf* b : {&h->Ac, &h->Bc})
-            if ((rc = sdr::ensure(*b, F * cpp * 8 + ov))) return rc;
-        if ((rc = sdr::ensure(h->coef, (size_t)std::max(2 * p.num_iter, 0) * F * cpp * 20 + ov))) return rc;
-    }
-    if ((rc = upload_lut(h, p.sigma_color, &lut))) return rc;
-    float* A = (float*)h->A.p;
-    float* B = (float*)h->B.p;
-    const dim3 blk(256);
-    const bool rowmajor = p.fgs_solver == SDR_FGS_PCR;
-    // the sequential solver's first pass (rows) reads the right-hand sides transposed: the fused
-    // front end writes them there directly
-    float* Ain = rowmajor ? A : (float*)h->Ac.p;
-    float* Bin = rowmajor ? B : nullptr;
-    const dim3 grid((W + 63) / 64, (H + 3) / 4, F);
-    sdr::WlsOut wo{out, fout, xyz, {}};
-    if (Q)
-        for (int t = 0; t < 16; t++) wo.Q.q[t] = Q[t];
-    // with the default solver the outputs need no pass of their own: k_wls_prep writes the pixels
-    // outside the ROI and the last FGS column pass the ROI's (k_wls_final otherwise)
-    const bool fin_fused = fused && roi && p.fgs_solver == SDR_FGS_PCR;
-    if (fused) {
-        sdr::KScope kt(timer, SDR_KERNEL_WLS_PREP);
-        // the window radius is ceil(blockSize / 2) <= 9 for every valid SGBM block; wider ones
-        // (setDepthDiscontinuityRadius) take the per-pixel kernels below
-        auto* prep = g.radius <= 4 ? sdr::k_wls_prep<4> : sdr::k_wls_prep<9>;
-        hipLaunchKernelGGL(prep, dim3(H, F), blk, (size_t)g.rw * 32, st, dl, dr, g, guide, gstride, gfstride, lut,
-                           rowmajor ? 1 : 0, conf, Ain, Bin, (float*)h->ChT.p, (float*)h->Cv.p, fin_fused ? 1 : 0, wo);
-    } else {
-        sdr::KScope kt(timer, SDR_KERNEL_WLS_PREP);
-        if (roi)
-            hipLaunchKernelGGL(sdr::k_wls_disc, dim3((g.rw + 63) / 64, (g.rh + 3) / 4, F), blk, 0, st,
-                               dr, g, (float*)h->rdisc.p);
-        hipLaunchKernelGGL(sdr::k_wls_conf, grid, blk, 0, st, dl, dr, (const float*)h->rdisc.p, g,
-                           conf, A, B);
-    }
-    if (roi) {
-        const uint8_t* g0 = guide + (size_t)g.ry * gstride + g.rx;
-        const sdr::FgsScratch fs{(float*)h->Ac.p, (float*)h->Bc.p, (float*)h->ChT.p,
-                                 (float*)h->Cv.p, (float*)h->coef.p};
-        if (sdr::launch_fgs(g0, gstride, gfstride, lut, A, B, g.rw, g.rh, F, p.lambda,
-                            p.lambda_attenuation, p.num_iter, p.fgs_solver, fs, st, fused, timer,
-                            fin_fused ? &g : nullptr, fin_fused ? &wo : nullptr, fused && !rowmajor))
-            return sdr::set_error(SDR_ERR_SIZE, "SDR_FGS_PCR solves lines of at most 4096 samples "
-                                                "(use SDR_FGS_THOMAS for larger ROIs)");
-        if (fin_fused) {
-            SDR_HIP(hipGetLastError());
-            return SDR_OK;
-        }
-    }
-    {
-        sdr::KScope kt(timer, SDR_KERNEL_WLS_FINAL);
-        hipLaunchKernelGGL(sdr::k_wls_final, grid, blk, 0, st, A, B, g, wo);
-    }
-    SDR_HIP(hipGetLastError());
-    return SDR_OK;
-}
-
-extern "C" {
-
-int sdr_wls_filter_device(sdr_wls* h, const int16_t* dl, const int16_t* dr, const uint8_t* guide,
-                          int W, int H, size_t gstride, size_t gfstride, int F, int16_t* out,
-                          float* conf) {
-    return sdr::wls_filter_enqueue(h, dl, dr, guide, W, H, gstride, gfstride, F, out, conf, nullptr,
-                                   nullptr, nullptr);
-}
-
-int sdr_wls_filter(sdr_wls* h, const int16_t* dl, const int16_t* dr, const uint8_t* guide, int W,
-                   int H, size_t gstride, int16_t* out, float* conf) {
-    if (!h || !dl || !dr || !guide || !out) return sdr::set_error(SDR_ERR_ARG, "null argument");
-    if (W <= 0 || H <= 0 || gstride < (size_t)W) return sdr::set_error(SDR_ERR_ARG, "bad size/stride");
-    SDR_HIP(hipSetDevice(h->device));
-    const size_t px = (size_t)W * H;
-    // device staging: dl, dr, guide, out (int16), conf (float)
-    int rc;
-    if ((rc = sdr::ensure(h->hbuf, px * (2 + 2 + 1 + 2 + 4) + 64))) return rc;
-    uint8_t* base = (uint8_t*)h->hbuf.p;
-    float* dconf = (float*)base;
-    int16_t* ddl = (int16_t*)(base + px * 4);
-    int16_t* ddr = ddl + px;
-    int16_t* dout = ddr + px;
-    uint8_t* dg = (uint8_t*)(dout + px);
-    hipStream_t st = h->stream;
-    SDR_HIP(hipMemcpyAsync(ddl, dl, px * 2, hipMemcpyHostToDevice, st));
-    SDR_HIP(hipMemcpyAsync(ddr, dr, px * 2, hipMemcpyHostToDevice, st));
-    SDR_HIP(hipMemcpy2DAsync(dg, W, guide, gstride, W, H, hipMemcpyHostToDevice, st));
-    if ((rc = sdr_wls_filter_device(h, ddl, ddr, dg, W, H, W, px, 1, dout, conf ? dconf : nullptr)))
-        return rc;
-    SDR_HIP(hipMemcpyAsync(out, dout, px * 2, hipMemcpyDeviceToHost, st));
-    if (conf) SDR_HIP(hipMemcpyAsync(conf, dconf, px * 4, hipMemcpyDeviceToHost, st));
-    SDR_HIP(hipStreamSynchronize(st));
-    return SDR_OK;
-}
-
-int sdr_fgs_filter_device(const uint8_t* d_guide, size_t gstride, int w, int h, double lambda,
-                          double sigma, double att, int iters, float* d_img, int nimg,
-                          int solver, void* stream) {
-    if (!d_guide || !d_img) return sdr::set_error(SDR_ERR_ARG, "null argument");
-    if (w <= 0 || h <= 0 || nimg <= 0 || gstride < (size_t)w)
-        return sdr::set_error(SDR_ERR_ARG, "bad size/stride");
-    if (!(lambda >= 0.0) || !(sigma >= 0.0) || iters < 1)
-        return sdr::set_error(SDR_ERR_ARG, "FGS needs lambda >= 0, sigma_color >= 0, num_iter >= 1");
-    if (solver == SDR_FGS_THOMAS && !thomas_lambdas_ok(lambda, att, iters))
-        return sdr::set_error(SDR_ERR_ARG, kThomasLambdaMsg);
-    if (solver != SDR_FGS_PCR && solver != SDR_FGS_THOMAS)
-        return sdr::set_error(SDR_ERR_ARG, "solver must be SDR_FGS_PCR or SDR_FGS_THOMAS");
-    if (solver == SDR_FGS_PCR && (w > sdr::kPcrMaxN || h > sdr::kPcrMaxN))
-        return sdr::set_error(SDR_ERR_SIZE, "SDR_FGS_PCR solves lines of at most 4096 samples "
-                                            "(use SDR_FGS_THOMAS for larger images)");
-    hipStream_t st = (hipStream_t)stream;
-    std::vector<float> lut;
-    sdr::fgs_lut_host(sigma, &lut);
-    // stream-ordered scratch: LUT, column-major copies, coefficients, weights
-    float* dlut = nullptr;
-    float* scr = nullptr;
-    const size_t px = (size_t)w * h;
-    // (frames of the sequential solver's padded layouts: fgs_pad4(w) * fgs_pad4(h) >= px samples)
-    const size_t fp = (size_t)sdr::fgs_pad4(w) * sdr::fgs_pad4(h);
-    SDR_HIP(sdr::scratch_alloc((void**)&dlut, sizeof(float) * lut.size(), st));
-    // (FgsScratch: the sequential solver's two interleaved pass layouts, the weights, and 5 floats
-    // a sample for each of its 2 * iters passes' coefficients; its loaders read up to
-    // kFgsOverread bytes past an array)
-    const size_t ncoef = solver == SDR_FGS_THOMAS ? (size_t)5 * (2 * iters) : 0;
-    SDR_HIP(sdr::scratch_alloc((void**)&scr, sizeof(float) * fp * (6 + ncoef) + sdr::kFgsOverread, st));
-    SDR_HIP(hipMemcpyAsync(dlut, lut.data(), sizeof(float) * lut.size(), hipMemcpyHostToDevice, st));
-    const sdr::FgsScratch fs{scr, scr + 2 * fp, scr + 4 * fp, scr + 5 * fp, scr + 6 * fp};
-    // images are filtered in pairs (two right-hand sides of one system per line)
-    for (int i = 0; i < nimg; i += 2) {
-        const int m = nimg - i >= 2 ? 2 : 1;
-        (void)sdr::launch_fgs(d_guide, gstride, 0, dlut, d_img + i * px, m == 2 ? d_img + (i + 1) * px : nullptr,
-                              w, h, 1, lambda, att, iters, solver, fs, st);
-    }
-    SDR_HIP(hipGetLastError());
-    SDR_HIP(sdr::scratch_free(dlut, st));
-    SDR_HIP(sdr::scratch_free(scr, st));
-    // the host LUT vector dies here: wait for its upload before returning
-    SDR_HIP(hipStreamSynchronize(st));
-    return SDR_OK;
-}
-
-int sdr_fgs_plan_query(int w, int h, int nframes, int nimg, int num_iter, int solver, int cus,
-                       sdr_fgs_plan* out) {
-    if (!out) return sdr::set_error(SDR_ERR_ARG, "null argument");
-    if (w <= 0 || h <= 0 || nframes <= 0 || num_iter < 1 || cus < 0 || (nimg != 1 && nimg != 2))
-        return sdr::set_error(SDR_ERR_ARG, "bad size, nimg other than 1 or 2, num_iter < 1 or cus < 0");
-    if (solver != SDR_FGS_PCR && solver != SDR_FGS_THOMAS)
-        return sdr::set_error(SDR_ERR_ARG, "solver must be SDR_FGS_PCR or SDR_FGS_THOMAS");
-    *out = sdr_fgs_plan{};
-    if (solver == SDR_FGS_PCR) {
-        if (w > sdr::kPcrMaxN || h > sdr::kPcrMaxN)
-            return sdr::set_error(SDR_ERR_SIZE, "SDR_FGS_PCR solves lines of at most 4096 samples");
-        out->row_pass = {SDR_FGS_KERNEL_PCR, sdr::pcr_lines(w, h)};
-        out->col_pass = {SDR_FGS_KERNEL_PCR, sdr::pcr_lines(h, w)};
-        return SDR_OK;
-    }
-    if (!cus) cus = sdr::device_cus();
-    out->cus = cus;
-    // the plan launch_fgs runs: its first row and column pass, and their jobs in the first job launch
-    const sdr::FgsPlan plan = sdr::fgs_plan(w, h, nframes, nimg == 2, num_iter, cus);
-    out->row_pass = plan.pass[0];
-    out->col_pass = plan.pass[1];
-    out->row_job = plan.job[0];
-    out->col_job = plan.job[1];
-    return SDR_OK;
-}
-
-}  // extern "C"
