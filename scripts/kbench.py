@@ -29,6 +29,12 @@ CONFIGS = {  # W, H, D, mode, frames
     "c5b8": (1920, 1080, 256, 1, 8),  # C5 as benched: 8 frames through the row sweeps
     "hh128": (1280, 720, 128, 1, 8),  # the sweeps at two disparities per lane
     "c3b32": (1280, 720, 256, 1, 32),  # C3 as benched: 32 frames per call
+    # kernel variants no benchmark config reaches
+    "d160": (1280, 720, 160, 0, 1),    # 4 disparities a lane, padded
+    "d384": (1280, 720, 384, 0, 1),    # 8 a lane, padded
+    "d512": (1280, 720, 512, 0, 1),    # 8 a lane
+    "w3d128": (640, 360, 128, 2, 1),   # D = 128 with int16 records (3 paths), one chain a wave
+    "c4d128": (640, 360, 128, 2, 2),   # the two-chain and two-column forms without padding
 }
 KINDS = ["prefilter", "k_cost", "k_paths", "k_south_wta", "median", "speckle", "reproject", "k_lr_check",
          "k_sweep", "k_wls_prep", "fgs_pass", "k_wls_final", "k_sweep_down"]  # SDR_KERNEL_* order
@@ -49,13 +55,15 @@ def main():
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--speckle", type=int, default=200, help="speckleWindowSize (0: the plain median kernel runs)")
+    ap.add_argument("--per-round", action="store_true", help="also print every round's value per kernel")
     a = ap.parse_args()
     W, H, D, mode, F = CONFIGS[a.config]
     Ls, Rs = S.make_batch(F, H, W, D, seed0=100)
     dev = torch.device("cuda", 0)
     dl, dr = torch.from_numpy(Ls).to(dev), torch.from_numpy(Rs).to(dev)
     libs = [load(p) for p in a.libs]
-    params = _lib.SgbmParams(0, D, 5, 600, 2400, 1, 63, 12, 200, 2, mode, 4, 0)
+    params = _lib.SgbmParams(0, D, 5, 600, 2400, 1, 63, 12, a.speckle, 2, mode, 4, 0)
     handles, outs = [], []
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     for L in libs:
@@ -93,6 +101,10 @@ def main():
         same = np.array_equal(o.cpu().numpy(), ref)
         vals = [np.median(res[p][c]) if res[p][c] else float("nan") for c in cols]
         print(f"{os.path.basename(p):40s} " + " ".join(f"{v:11.1f}" for v in vals) + f"  {same}")
+    if a.per_round:  # every round's value: the spread between two builds of one source is the noise
+        for c in cols:
+            for p in a.libs:
+                print(f"  {c:13s} {os.path.basename(p):30s} " + " ".join(f"{v:9.2f}" for v in res[p][c]))
 
 
 if __name__ == "__main__":

@@ -256,14 +256,18 @@ __device__ __forceinline__ void unroll_rows_tail(F& f, int k0, int klast, std::i
 }
 
 // trunc(n / d) for d >= 1 and |n / d| < 2^20 without a divide loop: float estimate, then one
-// exact integer correction step (the subpixel quotients are in [-9, 9]).
-__device__ __forceinline__ int div_trunc_small(int n, int d) {
+// exact integer correction step (the subpixel quotients are in [-9, 9]).  The host has a divider.
+__host__ __device__ __forceinline__ int div_trunc_small(int n, int d) {
+#if defined(__HIP_DEVICE_COMPILE__)
     const int an = abs(n);
     int q = (int)((float)an * __builtin_amdgcn_rcpf((float)d));
     const int r = an - q * d;
     q += (r >= d) ? 1 : 0;
     q -= (r < 0) ? 1 : 0;
     return n < 0 ? -q : q;
+#else
+    return n / d;
+#endif
 }
 
 

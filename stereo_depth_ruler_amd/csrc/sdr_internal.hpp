@@ -220,28 +220,22 @@ bool paths_two_chain(const Geometry& g, const PathLaunch& pl, int F);
 bool south_two_col(const Geometry& g, const PathLaunch& pl, int npaths, int F);
 bool path_rec12_supported(const Geometry& g, const PathLaunch& pls, const PathLaunch& plS, int npaths, int F);
 
-// A.9, OpenCV's disp12MaxDiff check, at pixel (x, y) of a frame with geometry g: raw is the frame's
-// WTA map and d2 its right-view keys (both [H][W]).  Every consumer of the LR-checked map
-// computes it on the fly from these two (the median's tiles, the debug stage), so the map itself
-// is never written.
+// The right view's WTA keys (SouthWtaArgs::d2), one word a pixel: kD2None until a left pixel
+// claims it, then d2_key of the claiming pixel with the smallest key.  x: the claiming pixel's
+// matched-range column (image column x + minX1), best: its disparity index (disparity best + minD).
 constexpr uint32_t kD2None = 0xffffffffu;
-__device__ __forceinline__ int lr_at(const Geometry& g, const int16_t* __restrict__ raw,
-                                     const uint32_t* __restrict__ d2, int x, int y, int d12) {
-    const int invalid = (g.minD - 1) * 16;
-    if (x < g.minX1 || x >= g.minX1 + g.W1) return invalid;
-    const size_t ro = (size_t)y * g.W;
-    const int d1 = raw[ro + x];
-    if (d1 == invalid) return d1;
-    const int _d = d1 >> 4, d_ = (d1 + 15) >> 4;
-    const int _x = x - _d, x_ = x - d_;
-    if (_x < 0 || _x >= g.W || x_ < 0 || x_ >= g.W) return d1;
-    const uint32_t ka = d2[ro + _x], kb = d2[ro + x_];
-    const int a2 = ka == kD2None ? invalid : (0xffff - (int)(ka & 0xffff)) + g.minX1 - _x;
-    const int b2 = kb == kD2None ? invalid : (0xffff - (int)(kb & 0xffff)) + g.minX1 - x_;
-    const bool bad = a2 >= g.minD && abs(a2 - _d) > d12 && b2 >= g.minD && abs(b2 - d_) > d12;
-    return bad ? invalid : d1;
+__host__ __device__ __forceinline__ uint32_t d2_key(int minS, int x) {
+    return ((uint32_t)minS << 16) | (uint32_t)(0xffff - x);
 }
-// the LR-checked map of F frames (frames fstride apart), materialised (debug stage only)
+// the right-view image column the pixel claims (the caller drops columns outside [0, W))
+__host__ __device__ __forceinline__ int d2_column(const Geometry& g, int x, int best) {
+    return x + g.minX1 - g.minD - best;
+}
+// the disparity the key at right-view column x2 stands for; INVALID when nothing claimed it
+__host__ __device__ __forceinline__ int d2_disparity(uint32_t key, int x2, const Geometry& g) {
+    return key == kD2None ? (g.minD - 1) * 16 : (0xffff - (int)(key & 0xffff)) + g.minX1 - x2;
+}
+// the LR-checked map (A.9: lr_at, sdr_sgbm_rules.hpp) of F frames (frames fstride apart), materialised (debug stage only)
 void launch_lr_apply(const Geometry& g, const int16_t* raw, const uint32_t* d2, int16_t* out,
                      size_t fstride, int disp12MaxDiff, int F, hipStream_t st);
 // the median's source: A.9 of (raw, d2) per frame (frames fstride apart)

@@ -16,6 +16,7 @@
 // left-right check (lr_at) is then computed by the median's tiles from those two maps.
 #include "sdr_device.hpp"
 #include "sdr_internal.hpp"
+#include "sdr_sgbm_rules.hpp"
 
 #include <algorithm>
 
@@ -24,7 +25,6 @@ namespace sdr {
 struct Chain {
     int x0, y0, dx, dy, len, kwrite;
 };
-
 
 __device__ __forceinline__ Chain make_chain(const Geometry& g, const PathDir& d, int c) {
     Chain ch;
@@ -58,32 +58,6 @@ __device__ __forceinline__ Chain make_chain(const Geometry& g, const PathDir& d,
     return ch;
 }
 
-// The per-word recurrence of one step: L = C + min(Lp, min(Lp[d-1], Lp[d+1]) + P1, delta2) -
-// delta2 for the lane's K words, and m = the minimum of L's pairs.  (Issuing two words' packed ops
-// alternately -- 4 x int16 vector ops, no packed op right after the one it reads, so none of
-// gfx950's wait states -- removed ~40 % of the path kernels' s_nops and measured no faster: at
-// 3-4 waves per SIMD the other waves fill those slots; profiles/r4_ab_variants.txt.)
-// WE: also E = C - L = delta2 - t, the 12-bit record's value (0 <= E <= P2: minLp <= t <= delta2),
-// one packed op beside the recurrence's dependency chain.
-template <int K, bool PAD, bool WE = false>
-__device__ __forceinline__ void step_words(const Regs<K>& c, const Regs<K>& Lp, uint32_t delta2, uint32_t P1x2,
-                                           bool active, uint32_t up, uint32_t dn, Regs<K>& L, uint32_t& m,
-                                           Regs<K>* E = nullptr) {
-    m = kMaxPair;
-#pragma unroll
-    for (int i = 0; i < K; i++) {
-        const uint32_t dm1 = funnel16(Lp.r[i], i == 0 ? up : Lp.r[i == 0 ? 0 : i - 1]);
-        const uint32_t dp1 = funnel16(i == K - 1 ? dn : Lp.r[i == K - 1 ? 0 : i + 1], Lp.r[i]);
-        uint32_t t = pk_add_sat(pk_min(dm1, dp1), P1x2);
-        t = pk_min(pk_min(t, Lp.r[i]), delta2);
-        uint32_t l = pk_sub(pk_add(c.r[i], t), delta2);
-        if constexpr (PAD) l = active ? l : kMaxPair;
-        if constexpr (WE) E->r[i] = pk_sub(delta2, t);
-        L.r[i] = l;
-        m = pk_min(m, l);
-    }
-}
-
 // One step of the path recurrence on a wave's packed int16 pairs (lane l: disparities
 // [l*2K, l*2K + 2K)); returns L of this pixel.  State: Lp := L, delta2 := minL + P2 (both
 // halves).  upr/dnr: the lane-shifted neighbour words of the previous step -- a wave shift leaves
@@ -102,8 +76,7 @@ __device__ __forceinline__ Regs<K> path_step(Regs<K> c, Regs<K>& Lp, uint32_t& d
     const uint32_t up = upr = lane_from_prev(Lp.r[K - 1], upr);
     const uint32_t dn = dnr = lane_from_next(Lp.r[0], dnr);
     Regs<K> L;
-    uint32_t m;
-    step_words<K, PAD, WE>(c, Lp, delta2, P1x2, active, up, dn, L, m, E);
+    const uint32_t m = step_words<K, PAD, WE>(c.r, Lp.r, delta2, P1x2, active, up, dn, L.r, WE ? E->r : nullptr);
     // min of the pair into the low half (one SDWA op; L >= 0, so u16 order is int16 order), the
     // wave minimum as a wave-uniform value, splatted and offset by P2 in scalar registers
     const uint32_t m16 = (uint32_t)__builtin_elementwise_min((unsigned short)(m & 0xffffu),
@@ -127,6 +100,59 @@ constexpr int paths_la() { return DPL == 8 ? 8 : 16; }
 // 219 -> 183 us (MI355X, scripts/kbench.py A/B, bit-exact).
 constexpr int kLoadNT = 2;
 
+// The chain walk of a k_paths wave: cp / op = the chain's first pixel in C / in its record buffer,
+// rowb / rowl = their byte steps along the chain, vld = the lane's byte offset into a C pixel;
+// step(c, rO, soffl) runs the recurrence on the pixel's costs c and stores its record at the lane's
+// offset into (rO, soffl); it takes them by value (by reference the kernels' code size moved).
+// C is loaded LA steps ahead into a ring of 2*LA slots: the slot a load fills was consumed LA steps
+// earlier, so every slot keeps one register across the loop's back edge (a ring of LA slots makes
+// the compiler copy the in-flight loads at the back edge, which waits for all of them).
+// C: one resource for the whole chain, based at the lowest address the chain's loads touch (row
+// `low`); the SGPR offset of row j is (j - low) * rowb >= 0 (below 2^31: the engine refuses frames
+// whose chain span passes it).  L: the record stride is P-1 times larger, so the store resource is
+// re-based at every ring period (R steps) instead.
+template <int K, int LA, typename Step>
+__device__ __forceinline__ void walk_chain(const char* cp, char* op, ptrdiff_t rowb, ptrdiff_t rowl, int len,
+                                           uint32_t vld, Step& step) {
+    constexpr int R = 2 * LA;
+    const int last = len - 1;
+    const int low = rowb >= 0 ? 0 : last + LA;
+    const Rsrc rC = rsrc_at(cp + (ptrdiff_t)low * rowb);
+    uint32_t soff = (uint32_t)((ptrdiff_t)(0 - low) * rowb);
+    Rsrc rO;
+    uint32_t soffl = 0;
+    auto rebase = [&](int k0) __attribute__((always_inline)) {
+        const int lo = rowl >= 0 ? k0 : k0 + R - 1;
+        rO = rsrc_at(op + (ptrdiff_t)lo * rowl);
+        soffl = (uint32_t)((ptrdiff_t)(k0 - lo) * rowl);
+    };
+    Regs<K> cring[R];
+#pragma unroll
+    for (int j = 0; j < LA; j++) {
+        cring[j] = load_buf<K>(rC, vld, soff);
+        soff += (uint32_t)rowb;
+    }
+    auto row = [&](const int, auto jc) __attribute__((always_inline)) {
+        constexpr int j = decltype(jc)::value;
+        const Regs<K> c = cring[j];
+        cring[(j + LA) % R] = load_buf<K>(rC, vld, soff);
+        soff += (uint32_t)rowb;
+        step(c, rO, soffl);
+        soffl += (uint32_t)rowl;
+        // one scheduling region per step (as the branch used to make it): scheduled across the
+        // whole unrolled ring, the steps' loads and stores were reordered and the ring registers
+        // copied, with vmcnt(0) waits inside the loop
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    int k0 = 0;
+    for (; k0 + R <= len; k0 += R) {
+        rebase(k0);
+        unroll_rows(row, k0, std::make_integer_sequence<int, R>{});
+    }
+    rebase(k0);
+    unroll_rows_tail(row, k0, last, std::make_integer_sequence<int, R - 1>{});
+}
+
 // R12: the records are 12-bit e = C - L (rec12_pack): a quad of lanes' 8 disparities in 12 bytes,
 // lanes 0-2 of the quad storing a dword each, a pixel's record of one direction D * 3/2 contiguous
 // bytes (three whole 64-byte segments at D = 128).
@@ -134,12 +160,6 @@ template <int DPL, bool PAD, bool R12 = false>
 __global__ __launch_bounds__(256) void k_paths(Geometry g, PathLaunch pl) {
     static_assert(!R12 || (DPL == 2 && !PAD), "12-bit records: D = 128");
     constexpr int K = DPL / 2;
-    // C is loaded LA steps ahead into a ring of 2*LA slots: the slot a load fills was consumed
-    // LA steps earlier, so every slot keeps one register across the loop's back edge (a ring
-    // of LA slots makes the compiler copy the in-flight loads at the back edge, which waits for
-    // all of them)
-    constexpr int LA = paths_la<DPL>();
-    constexpr int R = 2 * LA;
     const int lane = threadIdx.x & 63;
     // wave-uniform chain index in an SGPR: all chain control flow stays scalar
     const int cg = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
@@ -169,28 +189,6 @@ __global__ __launch_bounds__(256) void k_paths(Geometry g, PathLaunch pl) {
                                    ((size_t)(ch.y0 - pl.redir[i].s0) * W1 + ch.x0) * D);
     }
     char* op = (char*)(pd.out + (size_t)f * pl.l_fstride + ((size_t)ch.y0 * W1 + ch.x0) * pl.l_pix);
-    const int last = ch.len - 1;
-    // C: one resource for the whole chain, based at the lowest address the chain's loads touch
-    // (row `low`); the SGPR offset of row j is (j - low) * rowb >= 0 (below 2^31: the engine
-    // refuses frames whose chain span passes it).  L: the record stride is P-1 times larger, so
-    // the store resource is re-based at every ring period (R steps) instead.
-    const int low = rowb >= 0 ? 0 : last + LA;
-    const Rsrc rC = rsrc_at(cp + (ptrdiff_t)low * rowb);
-    uint32_t soff = (uint32_t)((ptrdiff_t)(0 - low) * rowb);
-    Rsrc rO;
-    uint32_t soffl = 0;
-    auto rebase = [&](int k0) __attribute__((always_inline)) {
-        const int lo = rowl >= 0 ? k0 : k0 + R - 1;
-        rO = rsrc_at(op + (ptrdiff_t)lo * rowl);
-        soffl = (uint32_t)((ptrdiff_t)(k0 - lo) * rowl);
-    };
-
-    Regs<K> cring[R];
-#pragma unroll
-    for (int j = 0; j < LA; j++) {
-        cring[j] = load_buf<K>(rC, lofs, soff);
-        soff += (uint32_t)rowb;
-    }
 
     Regs<K> Lp;
 #pragma unroll
@@ -210,11 +208,7 @@ __global__ __launch_bounds__(256) void k_paths(Geometry g, PathLaunch pl) {
     // (12-bit records: the quad's fourth lane has no dword of its own and is dropped the same way)
     const uint32_t sofs_st = R12 ? ((lane & 3) == 3 ? 0x80000000u : (uint32_t)((lane >> 2) * 12 + (lane & 3) * 4))
                                  : active ? lofs : 0x80000000u;
-    auto step = [&](const int, auto jc) __attribute__((always_inline)) {
-        constexpr int j = decltype(jc)::value;
-        const Regs<K> c = cring[j];
-        cring[(j + LA) % R] = load_buf<K>(rC, lofs, soff);
-        soff += (uint32_t)rowb;
+    auto step = [&](const Regs<K> c, const Rsrc rO, const uint32_t soffl) __attribute__((always_inline)) {
         if constexpr (R12) {
             Regs<K> E;
             (void)path_step<K, PAD, true>(c, Lp, delta2, P1x2, P2x2, active, upr, dnr, &E);
@@ -224,19 +218,8 @@ __global__ __launch_bounds__(256) void k_paths(Geometry g, PathLaunch pl) {
             const Regs<K> L = path_step<K, PAD>(c, Lp, delta2, P1x2, P2x2, active, upr, dnr);
             store_buf_nt<K>(rO, sofs_st, soffl, L);
         }
-        soffl += (uint32_t)rowl;
-        // one scheduling region per step (as the branch used to make it): scheduled across the
-        // whole unrolled ring, the steps' loads and stores were reordered and the ring registers
-        // copied, with vmcnt(0) waits inside the loop
-        __builtin_amdgcn_sched_barrier(0);
     };
-    int k0 = 0;
-    for (; k0 + R <= ch.len; k0 += R) {
-        rebase(k0);
-        unroll_rows(step, k0, std::make_integer_sequence<int, R>{});
-    }
-    rebase(k0);
-    unroll_rows_tail(step, k0, last, std::make_integer_sequence<int, R - 1>{});
+    walk_chain<K, paths_la<DPL>()>(cp, op, rowb, rowl, ch.len, lofs, step);
 }
 
 // k_paths with TWO chains per wave (lanes 0-31: chain 2w, lanes 32-63: chain 2w+1 of the same
@@ -269,18 +252,7 @@ __device__ __forceinline__ Regs<2> path_step_tc(Regs<2> c, Regs<2>& Lp, uint32_t
     const uint32_t up = lane == 32 ? kMaxPair : upr;  // chain B's first lane: its own boundary
     const uint32_t dn = lane == 31 ? kMaxPair : dnr;
     Regs<K> L;
-    uint32_t m = kMaxPair;
-#pragma unroll
-    for (int i = 0; i < K; i++) {
-        const uint32_t dm1 = funnel16(Lp.r[i], i == 0 ? up : Lp.r[i == 0 ? 0 : i - 1]);
-        const uint32_t dp1 = funnel16(i == K - 1 ? dn : Lp.r[i == K - 1 ? 0 : i + 1], Lp.r[i]);
-        uint32_t t = pk_add_sat(pk_min(dm1, dp1), P1x2);
-        t = pk_min(pk_min(t, Lp.r[i]), delta2);
-        uint32_t l = pk_sub(pk_add(c.r[i], t), delta2);
-        if constexpr (PAD) l = active ? l : kMaxPair;
-        L.r[i] = l;
-        m = pk_min(m, l);
-    }
+    const uint32_t m = step_words<K, PAD>(c.r, Lp.r, delta2, P1x2, active, up, dn, L.r);
     // the two chains' minima, in every lane of each half: 16-lane row minima (DPP), then rows 0+1
     // and 2+3 by one v_permlane16_swap (rows 0 <-> 1, 2 <-> 3); no readlane / scalar round trip
     uint32_t m16 = (uint32_t)__builtin_elementwise_min((unsigned short)(m & 0xffffu), (unsigned short)(m >> 16));
@@ -295,15 +267,13 @@ __device__ __forceinline__ Regs<2> path_step_tc(Regs<2> c, Regs<2>& Lp, uint32_t
 template <bool PAD>
 __global__ __launch_bounds__(256) void k_paths_tc(Geometry g, PathLaunch pl) {
     constexpr int DPL = 4, K = 2;
-    constexpr int LA = paths_la<DPL>();
-    constexpr int R = 2 * LA;
     const int lane = threadIdx.x & 63;
     const int half = lane >> 5, hl = lane & 31;
     const int wg = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
     const int f = blockIdx.y;
     int di = 0, w0 = 0;
     for (; di < pl.ndirs; di++) {
-        const int nw = (pl.d[di].nchains + 1) / 2;
+        const int nw = pair_count(pl.d[di].nchains);
         if (wg < w0 + nw) break;
         w0 += nw;
     }
@@ -325,46 +295,17 @@ __global__ __launch_bounds__(256) void k_paths_tc(Geometry g, PathLaunch pl) {
     const uint32_t vst = active ? lofs + (half ? (uint32_t)(pixB * pl.l_pix * 2) : 0u) : 0x80000000u;
     const char* cp = (const char*)(pl.C + (size_t)f * pl.cs_fstride + ((size_t)ch.y0 * W1 + ch.x0) * D);
     char* op = (char*)(pd.out + (size_t)f * pl.l_fstride + ((size_t)ch.y0 * W1 + ch.x0) * pl.l_pix);
-    const int last = ch.len - 1;
-    const int low = rowb >= 0 ? 0 : last + LA;
-    const Rsrc rC = rsrc_at(cp + (ptrdiff_t)low * rowb);
-    uint32_t soff = (uint32_t)((ptrdiff_t)(0 - low) * rowb);
-    Rsrc rO;
-    uint32_t soffl = 0;
-    auto rebase = [&](int k0) __attribute__((always_inline)) {
-        const int lo = rowl >= 0 ? k0 : k0 + R - 1;
-        rO = rsrc_at(op + (ptrdiff_t)lo * rowl);
-        soffl = (uint32_t)((ptrdiff_t)(k0 - lo) * rowl);
-    };
-    Regs<K> cring[R];
-#pragma unroll
-    for (int j = 0; j < LA; j++) {
-        cring[j] = load_buf<K>(rC, vld, soff);
-        soff += (uint32_t)rowb;
-    }
     Regs<K> Lp;
 #pragma unroll
     for (int i = 0; i < K; i++) Lp.r[i] = active ? 0u : kMaxPair;
     const uint32_t P1x2 = splat16(g.P1), P2x2 = splat16(g.P2);
     uint32_t delta2 = P2x2;
     uint32_t upr = kMaxPair, dnr = kMaxPair;
-    auto step = [&](const int, auto jc) __attribute__((always_inline)) {
-        constexpr int j = decltype(jc)::value;
-        const Regs<K> c = cring[j];
-        cring[(j + LA) % R] = load_buf<K>(rC, vld, soff);
-        soff += (uint32_t)rowb;
+    auto step = [&](const Regs<K> c, const Rsrc rO, const uint32_t soffl) __attribute__((always_inline)) {
         const Regs<K> L = path_step_tc<PAD>(c, Lp, delta2, P1x2, P2x2, active, upr, dnr, lane);
         store_buf_nt<K>(rO, vst, soffl, L);
-        soffl += (uint32_t)rowl;
-        __builtin_amdgcn_sched_barrier(0);
     };
-    int k0 = 0;
-    for (; k0 + R <= ch.len; k0 += R) {
-        rebase(k0);
-        unroll_rows(step, k0, std::make_integer_sequence<int, R>{});
-    }
-    rebase(k0);
-    unroll_rows_tail(step, k0, last, std::make_integer_sequence<int, R - 1>{});
+    walk_chain<K, paths_la<DPL>()>(cp, op, rowb, rowl, ch.len, vld, step);
 }
 
 // the two-chain kernel for this launch?  D <= 128, no redirected 3WAY rows, every direction with
@@ -381,9 +322,7 @@ void launch_paths(const Geometry& g, const PathLaunch& pl, int F, hipStream_t st
     const int total = pl.prefix[pl.ndirs];
     if (total <= 0) return;
     if (paths_two_chain(g, pl, F)) {
-        int waves = 0;
-        for (int i = 0; i < pl.ndirs; i++) waves += (pl.d[i].nchains + 1) / 2;
-        const dim3 grid2((waves + 3) / 4, F);
+        const dim3 grid2((pair_workgroups(pl) + 3) / 4, F);
         if (g.D < 128) hipLaunchKernelGGL((k_paths_tc<true>), grid2, dim3(256), 0, st, g, pl);
         else hipLaunchKernelGGL((k_paths_tc<false>), grid2, dim3(256), 0, st, g, pl);
         return;
@@ -496,10 +435,9 @@ __global__ __launch_bounds__(64 * (1 + kSouthConsumers)) void k_south_wta(Geomet
     int di = 0, c0i = 0;
     bool hasB = false;
     if constexpr (TC) {
-        // workgroups per direction entry: ceil(chains / 2)
         int w0 = 0;
         for (; di < pl.ndirs; di++) {
-            const int nw = (pl.d[di].nchains + 1) / 2;
+            const int nw = pair_count(pl.d[di].nchains);
             if (cg < w0 + nw) break;
             w0 += nw;
         }
@@ -610,14 +548,12 @@ __global__ __launch_bounds__(64 * (1 + kSouthConsumers)) void k_south_wta(Geomet
     // rows before kw belong to the previous 3WAY stripe: recurred through, never output
     const int kw = ch.kwrite;
     const int invalid = (g.minD - 1) * 16;
-    const bool check_uniq = a.uniq > 0 || !a.uniq_simd;
-    const bool uniq_simd = a.uniq_simd != 0;
-    const int lhs_scale = 100 - a.uniq;
-    const double inv100u = 1.0 / (double)(100 - a.uniq) * (1.0 + 0x1p-40);
+    const UniqRule uniq = make_uniq_rule(a.uniq, a.uniq_simd);
     const int x = ch.x0;  // matched-range column of this chain
     int16_t* raw = a.disp_raw + (size_t)f * a.disp_fstride + x + g.minX1;
     uint32_t* d2 = a.d2 ? a.d2 + (size_t)f * a.disp_fstride : nullptr;
-    const int x2base = x + g.minX1 - g.minD;  // the right-view column of disparity index 0
+    // column of disparity index 0, hoisted (d2_column a pixel costs every variant one more SGPR)
+    const int x2base = d2_column(g, x, 0);
 
     // window w of staged outputs (rows [w*kStageRows, ...)) to HBM, by the consumer lanes
     auto flush = [&](int w) __attribute__((always_inline)) {
@@ -634,8 +570,7 @@ __global__ __launch_bounds__(64 * (1 + kSouthConsumers)) void k_south_wta(Geomet
                 if (d2 && key < kNoWrite) {
                     // A.8's disp2 candidate of this pixel (no return value: a fire-and-forget atomic)
                     const int x2 = x2base + col - (int)(key & 0xffff);
-                    if (x2 >= 0 && x2 < g.W)
-                        atomicMin(&d2[y * g.W + x2], (key & 0xffff0000u) | (uint32_t)(0xffff - (x + col)));
+                    if (x2 >= 0 && x2 < g.W) atomicMin(&d2[y * g.W + x2], d2_key((int)(key >> 16), x + col));
                 }
             }
         }
@@ -689,40 +624,16 @@ __global__ __launch_bounds__(64 * (1 + kSouthConsumers)) void k_south_wta(Geomet
         key = row16_min_u32(wactive ? key : 0xffffffffu);
         const int minS = (int)(key >> 16) - 32768;
         const int best = (int)(key & 0xffff);
-        const int dm = max(best - 1, 0), dp = min(best + 1, D - 1);
-        // uniqueness: min of S[d] over |d - best| > 1 (0 <= S <= 32767: 0x7fff masks a half);
-        // the halfword accesses alias the row's 32-bit words: may_alias keeps their order
-        typedef int16_t __attribute__((may_alias)) s16a;
-        typedef uint32_t __attribute__((may_alias)) u32a;
-        s16a* s16 = (s16a*)srow;
-        const int Sm = s16[dm];
-        const int Sp = s16[dp];
-        s16[dm] = 0x7fff;
-        s16[best] = 0x7fff;
-        s16[dp] = 0x7fff;
-        uint32_t m2 = kMaxPair;
-#pragma unroll
-        for (int i = 0; i < WK; i++) m2 = pk_min(m2, ((u32a*)srow)[gl * WK + i]);
-        m2 = wactive ? m2 : kMaxPair;
-        m2 = pk_min(m2, funnel16(m2, m2));
-        m2 = row16_min_u32(m2);
-        const int min2 = (int)(m2 & 0x7fff);
-        // SIMD rule: S[d] < (short)(thresh + 1), thresh = (100*minS)/(100-u); scalar: S*(100-u) < 100*minS
-        const int thr16 = (int)(short)((int)((double)(100 * minS) * inv100u) + 1);
-        const bool reject = check_uniq && (uniq_simd ? (min2 < thr16) : (min2 * lhs_scale < minS * 100));
+        int Sm, Sp;
+        const int min2 = wta_second_min<WK>(srow, gl, wactive, best, D, Sm, Sp);
+        const bool reject = uniq_rejects(uniq, minS, min2);
         if (gl == 0 && k <= last) {
             int out = invalid;
             uint32_t okey = kNoWrite;
             if (rowok) {
                 okey = kRejected;
-                // every S saturated: OpenCV's first-minimum scan (strict '<' from MAX_COST) keeps
-                // bestDisp = -1, whose value (-1 + minD) * 16 is INVALID and whose disp2
-                // candidate (cost MAX_COST) never replaces the initial one
-                if (!reject && minS < kMaxCost) {
-                    // subpixel: d*16 + ((S[d-1]-S[d+1])*16 + den) / (2*den), C truncating division
-                    const int den = max(Sm + Sp - 2 * minS, 1);
-                    const int qq = div_trunc_small((Sm - Sp) * 16 + den, 2 * den);
-                    out = best * 16 + (((0 < best) & (best < D - 1)) ? qq : 0) + g.minD * 16;
+                if (!reject && minS < kMaxCost) {  // every S saturated: no disparity (wta_subpixel)
+                    out = wta_subpixel(best, minS, Sm, Sp, D, g.minD);
                     okey = ((uint32_t)minS << 16) | (uint32_t)best;
                 }
             }
@@ -802,9 +713,7 @@ static void launch_south_np(const Geometry& g, const PathLaunch& pl, const South
     }
     if constexpr (DPL == 2) {
         if (south_two_col(g, pl, a.npaths, F)) {
-            int wgs = 0;
-            for (int i = 0; i < pl.ndirs; i++) wgs += (pl.d[i].nchains + 1) / 2;
-            const dim3 grid2(wgs, F);
+            const dim3 grid2(pair_workgroups(pl), F);
             switch (a.npaths) {
             case 3: hipLaunchKernelGGL((k_south_wta<2, PAD, 2, true>), grid2, block, 0, st, g, pl, a); return;
             case 4: hipLaunchKernelGGL((k_south_wta<2, PAD, 3, true>), grid2, block, 0, st, g, pl, a); return;

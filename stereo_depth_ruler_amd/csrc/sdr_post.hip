@@ -3,6 +3,7 @@
 // (BGR2GRAY, INTER_AREA 0.5x) and a device self-test of the cross-lane primitives.
 #include "sdr_device.hpp"
 #include "sdr_internal.hpp"
+#include "sdr_sgbm_rules.hpp"
 
 #include <float.h>
 
@@ -27,13 +28,7 @@ __device__ __forceinline__ int median3_at(const int16_t* __restrict__ src, int W
             if (MASK && (xs[j] < c0 || xs[j] >= c1)) p[i * 3 + j] = fill;
             else p[i * 3 + j] = src[(size_t)ys[i] * W + xs[j]];
         }
-#define SDR_S(a, b) { int t_ = min(p[a], p[b]); p[b] = max(p[a], p[b]); p[a] = t_; }
-    SDR_S(1, 2) SDR_S(4, 5) SDR_S(7, 8) SDR_S(0, 1) SDR_S(3, 4) SDR_S(6, 7)
-    SDR_S(1, 2) SDR_S(4, 5) SDR_S(7, 8) SDR_S(0, 3) SDR_S(5, 8) SDR_S(4, 7)
-    SDR_S(3, 6) SDR_S(1, 4) SDR_S(2, 5) SDR_S(4, 7) SDR_S(4, 2) SDR_S(6, 4)
-    SDR_S(4, 2)
-#undef SDR_S
-    return p[4];
+    return median9(p);
 }
 
 __global__ __launch_bounds__(256) void k_median3(const int16_t* __restrict__ src,
@@ -52,8 +47,8 @@ void launch_median3(const int16_t* src, int16_t* dst, int W, int H, int F, hipSt
 
 // the (TW + 2) x (TH + 2) neighbourhood of a TW x TH tile of the LR-checked map (A.9 from the WTA
 // map and the right-view keys), rows and columns clamped (medianBlur's BORDER_REPLICATE), in LDS
-// (lr_at unrolled over a thread's NPT pixels: all WTA loads, then all key loads, so the block
-// pays two dependent memory round trips, not two per pixel)
+// (sdr_sgbm_rules.hpp's lr_at unrolled over a thread's NPT pixels: all WTA loads, then all key
+// loads, so the block pays two dependent memory round trips, not two per pixel)
 template <int TW, int TH, int NT>
 __device__ __forceinline__ void stage_lr_halo(const LrSrc& lr, int tx0, int ty0, int f, int16_t* hal) {
     const Geometry g = frame_geom(lr.g, f);
@@ -80,8 +75,8 @@ __device__ __forceinline__ void stage_lr_halo(const LrSrc& lr, int tx0, int ty0,
     for (int k = 0; k < NPT; k++) {
         if (!m[k]) d1[k] = invalid;
         const int x = xa[k];
-        xa[k] = x - (d1[k] >> 4);
-        xb[k] = x - ((d1[k] + 15) >> 4);
+        xa[k] = x - lr_lo(d1[k]);
+        xb[k] = x - lr_hi(d1[k]);
         ka[k] = d2[ro[k] + min(max(xa[k], 0), g.W - 1)];
         kb[k] = d2[ro[k] + min(max(xb[k], 0), g.W - 1)];
     }
@@ -90,12 +85,8 @@ __device__ __forceinline__ void stage_lr_halo(const LrSrc& lr, int tx0, int ty0,
         const int i = threadIdx.x + k * NT;
         if (i >= N) break;
         int v = d1[k];
-        const int _d = v >> 4, d_ = (v + 15) >> 4;
-        if (v != invalid && xa[k] >= 0 && xa[k] < g.W && xb[k] >= 0 && xb[k] < g.W) {
-            const int a2 = ka[k] == kD2None ? invalid : (0xffff - (int)(ka[k] & 0xffff)) + g.minX1 - xa[k];
-            const int b2 = kb[k] == kD2None ? invalid : (0xffff - (int)(kb[k] & 0xffff)) + g.minX1 - xb[k];
-            if (a2 >= g.minD && abs(a2 - _d) > lr.d12 && b2 >= g.minD && abs(b2 - d_) > lr.d12) v = invalid;
-        }
+        if (v != invalid && xa[k] >= 0 && xa[k] < g.W && xb[k] >= 0 && xb[k] < g.W)
+            v = lr_verdict(v, d2_disparity(ka[k], xa[k], g), d2_disparity(kb[k], xb[k], g), g.minD, lr.d12);
         hal[i] = (int16_t)v;
     }
 }
@@ -108,13 +99,7 @@ __device__ __forceinline__ int median3_lds(const int16_t* hal, int lx, int ly) {
     for (int i = 0; i < 3; i++)
 #pragma unroll
         for (int j = 0; j < 3; j++) p[i * 3 + j] = hal[(ly + i) * HW + lx + j];
-#define SDR_S(a, b) { int t_ = min(p[a], p[b]); p[b] = max(p[a], p[b]); p[a] = t_; }
-    SDR_S(1, 2) SDR_S(4, 5) SDR_S(7, 8) SDR_S(0, 1) SDR_S(3, 4) SDR_S(6, 7)
-    SDR_S(1, 2) SDR_S(4, 5) SDR_S(7, 8) SDR_S(0, 3) SDR_S(5, 8) SDR_S(4, 7)
-    SDR_S(3, 6) SDR_S(1, 4) SDR_S(2, 5) SDR_S(4, 7) SDR_S(4, 2) SDR_S(6, 4)
-    SDR_S(4, 2)
-#undef SDR_S
-    return p[4];
+    return median9(p);
 }
 
 // A.9 + A.10 without the speckle filter: 64 x 4 tiles, the LR check computed once per staged pixel

@@ -36,6 +36,7 @@
 // post-filter (launch_sweep_verdict) and the handle's status reports SDR_ERR_DEVICE.
 #include "sdr_device.hpp"
 #include "sdr_internal.hpp"
+#include "sdr_sgbm_rules.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -70,30 +71,18 @@ struct SwShape {
     static constexpr int MH = UP ? SDR_SW_UP_MH : SDR_SW_DN_MH;
 };
 
-// the path recurrence of one pixel step on a 16-lane row: L = C + min(Lp, min(Lp[d-1], Lp[d+1]) +
-// P1, dp) - dp with dp = min(Lp) + P2, for the lane's DW words; m16 = min of L over the lane's
-// disparities (low half).  The row's first lane has no d-1 for its first word: it takes its own
-// first word there (whose high half, d+1, repeats the d+1 term of the minimum, so the minimum is
-// the one +inf would give); the last lane likewise takes its own last word as d+1 (low half d-2,
-// the d-1 term again).  A padded D's inactive lanes hold +inf (kMaxPair), so the last active
-// lane's d+1 is +inf through the shift itself.
+// the path recurrence (step_words) of one pixel step on a 16-lane row, dp = min(Lp) + P2, for the
+// lane's DW words; m16 = min of L over the lane's disparities (low half).  The row's first lane
+// has no d-1 for its first word: it takes its own first word there (whose high half, d+1, repeats
+// the d+1 term of the minimum, so the minimum is the one +inf would give); the last lane likewise
+// takes its own last word as d+1 (low half d-2, the d-1 term again).  A padded D's inactive lanes
+// hold +inf (kMaxPair), so the last active lane's d+1 is +inf through the shift itself.
 template <int DW, bool PAD>
 __device__ __forceinline__ void step16(const uint32_t (&c)[DW], const uint32_t (&Lp)[DW], uint32_t dp,
                                        uint32_t P1x2, bool active, uint32_t (&L)[DW], uint32_t& m16) {
     const uint32_t up = (uint32_t)__builtin_amdgcn_update_dpp((int)Lp[0], (int)Lp[DW - 1], kDppRowShr1, 0xf, 0xf, false);
     const uint32_t dn = (uint32_t)__builtin_amdgcn_update_dpp((int)Lp[DW - 1], (int)Lp[0], kDppRowShl1, 0xf, 0xf, false);
-    uint32_t m = kMaxPair;
-#pragma unroll
-    for (int i = 0; i < DW; i++) {
-        const uint32_t dm1 = funnel16(Lp[i], i == 0 ? up : Lp[i == 0 ? 0 : i - 1]);
-        const uint32_t dp1 = funnel16(i == DW - 1 ? dn : Lp[i == DW - 1 ? 0 : i + 1], Lp[i]);
-        uint32_t t = pk_add_sat(pk_min(dm1, dp1), P1x2);
-        t = pk_min(pk_min(t, Lp[i]), dp);
-        uint32_t l = pk_sub(pk_add(c[i], t), dp);
-        if constexpr (PAD) l = active ? l : kMaxPair;
-        L[i] = l;
-        m = pk_min(m, l);
-    }
+    const uint32_t m = step_words<DW, PAD>(c, Lp, dp, P1x2, active, up, dn, L);
     m16 = (uint32_t)__builtin_elementwise_min((unsigned short)(m & 0xffffu), (unsigned short)(m >> 16));
 }
 
@@ -194,6 +183,7 @@ __device__ __forceinline__ void sweep_wave(const Geometry& g, const SweepArgs& a
     // publishing waves: the first NPUB own waves (side 0), the last NPUB (side 1)
     const int pub0 = OWN && wv - 1 < NPUB ? wv - 1 : -1;
     const int pub1 = OWN && wv >= NO - NPUB + 1 ? wv - (NO - NPUB + 1) : -1;
+    const UniqRule uniq = make_uniq_rule(w.uniq, w.uniq_simd);
     bool gave_up = false;
     auto wait = [&](const int* fl, int target) __attribute__((always_inline)) {
         int n = 0;
@@ -355,9 +345,6 @@ __device__ __forceinline__ void sweep_wave(const Geometry& g, const SweepArgs& a
             if constexpr (WTA) {
                 const int kb = k & ~15, nrow = k - kb + 1;
                 const int invalid = (g.minD - 1) * 16;
-                const bool check_uniq = w.uniq > 0 || !w.uniq_simd;
-                // SIMD rule: S[d] < (short)(thresh + 1), thresh = (100*minS)/(100-u); scalar: S*(100-u) < 100*minS
-                const double inv100u = 1.0 / (double)(100 - w.uniq) * (1.0 + 0x1p-40);
 #pragma unroll
                 for (int q = 0; q < MO; q++) {
                     const int e = q * 64 + lane;
@@ -369,20 +356,13 @@ __device__ __forceinline__ void sweep_wave(const Geometry& g, const SweepArgs& a
                         const int Sm = (int)(int16_t)(v.y >> 16), Sp = (int)(int16_t)(v.y & 0xffffu);
                         const int min2 = (int)v.z;
                         const int y = yof(kb + kk);
-                        const int thr16 = (int)(short)((int)((double)(100 * minS) * inv100u) + 1);
-                        const bool reject =
-                            check_uniq && (w.uniq_simd ? (min2 < thr16) : (min2 * (100 - w.uniq) < minS * 100));
                         int out = invalid;
-                        // every S saturated: OpenCV's first-minimum scan keeps bestDisp = -1 (INVALID)
-                        if (!reject && minS < kMaxCost) {
-                            const int den = max(Sm + Sp - 2 * minS, 1);
-                            const int qq = div_trunc_small((Sm - Sp) * 16 + den, 2 * den);
-                            out = best * 16 + (((0 < best) & (best < D - 1)) ? qq : 0) + g.minD * 16;
+                        if (!uniq_rejects(uniq, minS, min2) && minS < kMaxCost) {  // every S saturated: no disparity
+                            out = wta_subpixel(best, minS, Sm, Sp, D, g.minD);
                             if (w.d2) {
-                                const int x2 = x + g.minX1 - g.minD - best;
+                                const int x2 = d2_column(g, x, best);
                                 if (x2 >= 0 && x2 < g.W)
-                                    atomicMin(&w.d2[(size_t)f * w.disp_fstride + (size_t)y * g.W + x2],
-                                              ((uint32_t)minS << 16) | (uint32_t)(0xffff - x));
+                                    atomicMin(&w.d2[(size_t)f * w.disp_fstride + (size_t)y * g.W + x2], d2_key(minS, x));
                             }
                         }
                         w.disp_raw[(size_t)f * w.disp_fstride + (size_t)y * g.W + x + g.minX1] = (int16_t)out;
@@ -562,26 +542,12 @@ __device__ __forceinline__ void sweep_wave(const Geometry& g, const SweepArgs& a
                         key = row16_min_u32(active ? key : 0xffffffffu);
                         const int minS = (int)(key >> 16);
                         const int best = (int)(key & 0xffff);
-                        const int dm = max(best - 1, 0), dp = min(best + 1, D - 1);
-                        typedef int16_t __attribute__((may_alias)) s16a;
                         typedef uint32_t __attribute__((may_alias)) u32a;
                         u32a* srow = (u32a*)&sh.sS[UP ? 0 : wv - 1][r][0];
 #pragma unroll
                         for (int i = 0; i < DW; i++) srow[gl * DW + i] = St[i];
-                        s16a* s16 = (s16a*)srow;
-                        const int Sm = s16[dm];
-                        const int Sp = s16[dp];
-                        s16[dm] = 0x7fff;
-                        s16[best] = 0x7fff;
-                        s16[dp] = 0x7fff;
-                        // uniqueness: min of S[d] over |d - best| > 1 (0 <= S <= 32767: 0x7fff masks a half)
-                        uint32_t m2 = kMaxPair;
-#pragma unroll
-                        for (int i = 0; i < DW; i++) m2 = pk_min(m2, srow[gl * DW + i]);
-                        m2 = active ? m2 : kMaxPair;
-                        m2 = pk_min(m2, funnel16(m2, m2));
-                        m2 = row16_min_u32(m2);
-                        const int min2 = (int)(m2 & 0x7fff);
+                        int Sm, Sp;
+                        const int min2 = wta_second_min<DW>(srow, gl, active, best, D, Sm, Sp);
                         // the pixel's epilogue waits in the queue (wta_flush)
                         if (gl == 0)
                             sh.wq[wv - 1][((k & 15) * 4 + r) * MO + m] =

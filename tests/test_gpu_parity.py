@@ -101,6 +101,35 @@ def test_uniqueness_rule_switch(oracle, rule, mode):
     assert np.array_equal(got, ref)
 
 
+@pytest.mark.parametrize("rule", [1, 2])
+def test_uniqueness_rule_switch_rec12(oracle, rule):
+    """Both rules through k_south_wta's 12-bit-record consumer (mode 0, D = 128, one frame)."""
+    L, R, _ = S.make_pair(48, 200, 128, seed=27)
+    args = (0, 128, 5, 600, 2400, 1, 63, 15, 0, 0, 0)
+    got, ref, _ = run_both(oracle, L, R, args, uniq_rule=rule)
+    assert np.array_equal(got, ref)
+
+
+@pytest.mark.parametrize("rule", [1, 2])
+def test_uniqueness_rule_switch_two_columns(oracle, rule):
+    """Both rules through k_south_wta's two-column form: test_two_chain_paths' batched 3WAY shape
+    (4 frames x 4 stripes x 372 column chains, more than 8 a CU; D = 48, 3 paths)."""
+    mode, D, H, W, batch = 2, 48, 300, 420, 4
+    args = (0, D, 5, 600, 2400, 1, 63, 15, 0, 0, mode)
+    Ls = np.empty((batch, H, W), np.uint8)
+    Rs = np.empty((batch, H, W), np.uint8)
+    for i in range(batch):
+        Ls[i], Rs[i], _ = S.make_pair(H, W, D, seed=34 + i)
+    dev = torch.device("cuda", 0)
+    m = sdr.StereoSGBM.create(*args, uniq_rule=rule)
+    out = m.compute(torch.from_numpy(Ls).to(dev), torch.from_numpy(Rs).to(dev)).cpu().numpy()
+    p = oracle.make_params(*args, uniq_rule=rule)
+    for i in range(batch):
+        ref = oracle.sgbm_compute(Ls[i], Rs[i], p)
+        assert np.array_equal(out[i], ref), f"frame {i}: {(out[i] != ref).sum()} px differ"
+    m.close()
+
+
 def test_cost_volume_bit_exact(oracle):
     L, R, _ = S.make_pair(40, 150, 48, seed=23)
     for mode in (0, 1, 3):

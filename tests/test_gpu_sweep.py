@@ -59,6 +59,28 @@ def test_hh_sweep_batch_bit_exact(oracle, kind, F, H, W, D, speckle, seed):
     m.close()
 
 
+@pytest.mark.parametrize("rule", [1, 2])
+@pytest.mark.parametrize("H,W,D,seed", [
+    (18, 90, 48, 12),     # 2 disparities a lane, padded; W1 = 42: one partial tile
+    (16, 200, 160, 13),   # 4 a lane, padded
+])
+def test_hh_sweep_uniqueness_rules(oracle, rule, H, W, D, seed):
+    """The down pass's A.8 under both explicit uniqueness rules (uniq_rule 1: scalar, 2: SIMD; the
+    default of MODE_HH is the scalar one) at uniquenessRatio 15, each frame against the oracle."""
+    F = 8
+    args = (0, D, 5, 600, 2400, 1, 63, 15, 0, 2, sdr.MODE_HH)
+    Ls, Rs = _batch("textured", F, H, W, D, seed)
+    dev = torch.device("cuda", 0)
+    m = sdr.StereoSGBM.create(*args, uniq_rule=rule)
+    out = m.compute(torch.from_numpy(Ls).to(dev), torch.from_numpy(Rs).to(dev)).cpu().numpy()
+    m.check_status()
+    p = oracle.make_params(*args, uniq_rule=rule)
+    for i in range(F):
+        ref = oracle.sgbm_compute(Ls[i], Rs[i], p)
+        assert np.array_equal(out[i], ref), f"frame {i}: {(out[i] != ref).sum()} px differ"
+    m.close()
+
+
 def test_hh_sweep_frames_per_slot_and_negative_min_disparity(oracle):
     """Wide frames (W1 = 1652: 21 tiles of 80 columns, so about 12 frames fit the resident grid)
     in a batch of 16: the slots take a second frame each (the edge counters run on across frames,
