@@ -15,8 +15,11 @@
 //                    thread per voxel sums its run in point order: the oracle's order, so
 //                    centroids match bit for bit).  Sort and scan are hand-written (k_rs_*, k_scan_*):
 //                    no library on the path.
+// The host side of a voxel-grid call: the arena's layout and the grid derivation are
+// sdr_voxel_plan.hpp's (no HIP call there); VoxelCall below runs the stages over them.
 #include "../../include/sdr/sdr.h"
 #include "sdr_host.hpp"
+#include "sdr_voxel_plan.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -61,8 +64,6 @@ __global__ __launch_bounds__(256) void k_xyz_to_cloud(const float* __restrict__ 
     }
 }
 
-constexpr int kMinMaxBlocks = 512;
-
 // partial[b] = {min x, y, z, max x, y, z, finite count (as float bits)}
 __global__ __launch_bounds__(256) void k_minmax(const float4* __restrict__ p, int n,
                                                 float* __restrict__ partial) {
@@ -92,12 +93,6 @@ __global__ __launch_bounds__(256) void k_minmax(const float4* __restrict__ p, in
     }
     if (threadIdx.x < 7) partial[blockIdx.x * 7 + threadIdx.x] = s[threadIdx.x][0];
 }
-
-struct VoxelParams {
-    float inv[3];
-    int minb[3];
-    uint32_t mul1, mul2;
-};
 
 __global__ __launch_bounds__(256) void k_voxel_keys(const float4* __restrict__ p, int n, VoxelParams v,
                                                     uint64_t* __restrict__ keys) {
@@ -156,8 +151,7 @@ __global__ __launch_bounds__(256) void k_voxel_centroid(const float4* __restrict
     out[pos[i]] = o;
 }
 
-// ---- exclusive scan of int32 (reduce, scan the block totals, apply) ----------------------------
-constexpr int kScanItems = 8, kScanSeg = 256 * kScanItems;
+// ---- exclusive scan of int32 (reduce, scan the block totals, apply), kScanSeg a workgroup -------
 
 // the block's exclusive prefix of one int per thread (256 threads), and the block total
 __device__ __forceinline__ int block_excl_scan(int v, int* total, int* lds /* [4] */) {
@@ -226,8 +220,7 @@ __global__ __launch_bounds__(256) void k_scan_apply(const int* __restrict__ in, 
     }
 }
 
-// ---- stable LSD radix sort of (32-bit key, 32-bit value) pairs, 8-bit digits ------------------
-constexpr int kRsRounds = 16, kRsTile = 256 * kRsRounds;
+// ---- stable LSD radix sort of (32-bit key, 32-bit value) pairs, 8-bit digits, kRsTile a tile ---
 
 // hist[d * nb + b] = keys of tile b with digit d (digit-major: the scan of this array in order is
 // every key's bucket start for the stable scatter)
@@ -310,8 +303,9 @@ __global__ __launch_bounds__(256) void k_voxel_join(const uint32_t* __restrict__
 namespace {
 
 // The voxel grid's scratch: one grow-only device arena a call, leased from a list of idle arenas
-// and bump-allocated.  The call reports a count, so it synchronises its stream before it returns
-// and its arena goes back to the list idle (the lease synchronises again on an early exit).
+// and laid out once (sdr_voxel_plan.hpp VoxelArena).  The call reports a count, so it synchronises
+// its stream before it returns and its arena goes back to the list idle (the lease synchronises
+// again on an early exit).
 // Stream-ordered allocations freed at the end of every call measured 0.75-1.45 ms of host time
 // a call on MI355X (the hipFreeAsync calls), more than the grid's kernels take.
 struct Arena {
@@ -324,7 +318,6 @@ std::vector<Arena*> g_idle_arenas;
 struct ArenaLease {
     hipStream_t st;
     Arena* a = nullptr;
-    size_t used = 0;
     explicit ArenaLease(hipStream_t s) : st(s) {}
     // an idle arena of the stream's device with room for `bytes`: SDR_OK or an SDR_* status
     int open(size_t bytes) {
@@ -347,17 +340,136 @@ struct ArenaLease {
         }
         return sdr::ensure(a->buf, bytes);  // grows (hipFree + hipMalloc) only past its size
     }
-    void* get(size_t bytes) {
-        const size_t at = (used + 255) & ~(size_t)255;
-        if (!a || at + bytes > a->buf.n) return nullptr;
-        used = at + bytes;
-        return (char*)a->buf.p + at;
-    }
     ~ArenaLease() {
         if (!a) return;
         (void)hipStreamSynchronize(st);  // idle before another call may take it
         std::lock_guard<std::mutex> lk(g_arena_mu);
         g_idle_arenas.push_back(a);
+    }
+};
+
+// SDR_VOXEL_TIMING (a build-time diagnostic): host-side phase times of one call on stderr
+struct VoxelPhases {
+#ifdef SDR_VOXEL_TIMING
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), last = t0;
+    char buf[256];
+    int len = 0;
+    void mark(const char* what) {
+        const auto now = std::chrono::steady_clock::now();
+        len += std::snprintf(buf + len, sizeof(buf) - len, " %s %.1f", what,
+                             std::chrono::duration<double, std::micro>(now - last).count());
+        last = now;
+    }
+    ~VoxelPhases() {
+        mark("end");
+        std::fprintf(stderr, "voxel_grid us:%s\n", buf);
+    }
+#else
+    void mark(const char*) {}
+#endif
+};
+
+// One call's stages, in order, over the cloud, the stream and the leased arena's slices.
+struct VoxelCall {
+    const float4* p;
+    int n;
+    hipStream_t st;
+    sdr::VoxelArena a;
+    VoxelPhases ph;
+    void* base = nullptr;  // the leased arena
+
+    template <typename T>
+    T* at(const sdr::VoxelArena::Slice& s) const {
+        return (T*)((char*)base + s.off);
+    }
+    dim3 grid() const { return dim3((n + 255) / 256); }
+
+    // the bounds and the count of the finite points (k_minmax's partials, reduced here); synchronises
+    int bounds(float mn[3], float mx[3], long long* nfin) {
+        float* partial = at<float>(a.partial);
+        const int mmb = std::min(sdr::kMinMaxBlocks, (n + 255) / 256);
+        hipLaunchKernelGGL(sdr::k_minmax, dim3(mmb), dim3(256), 0, st, p, n, partial);
+        SDR_HIP(hipGetLastError());
+        std::vector<float> hp((size_t)7 * mmb);
+        SDR_HIP(hipMemcpyAsync(hp.data(), partial, sizeof(float) * hp.size(), hipMemcpyDeviceToHost, st));
+        ph.mark("mm_launch");
+        SDR_HIP(hipStreamSynchronize(st));
+        ph.mark("mm_sync");
+        *nfin = 0;
+        for (int c = 0; c < 3; c++) {
+            mn[c] = INFINITY;
+            mx[c] = -INFINITY;
+        }
+        for (int b = 0; b < mmb; b++) {
+            for (int c = 0; c < 3; c++) {
+                mn[c] = std::fmin(mn[c], hp[b * 7 + c]);
+                mx[c] = std::fmax(mx[c], hp[b * 7 + 3 + c]);
+            }
+            int cnt;
+            std::memcpy(&cnt, &hp[b * 7 + 6], 4);
+            *nfin += cnt;
+        }
+        return SDR_OK;
+    }
+
+    // PCL's overflow refusal: the output is the input cloud unchanged
+    int pass_through(float4* out, int* out_count, int* passthrough) {
+        SDR_HIP(hipMemcpyAsync(out, p, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, st));
+        SDR_HIP(hipStreamSynchronize(st));
+        *out_count = n;
+        if (passthrough) *passthrough = 1;
+        return SDR_OK;
+    }
+
+    void scan(const int* in, int m, int* o) {
+        int* spart = at<int>(a.spart);
+        const int nb = (m + sdr::kScanSeg - 1) / sdr::kScanSeg;
+        hipLaunchKernelGGL(sdr::k_scan_reduce, dim3(nb), dim3(256), 0, st, in, m, spart);
+        hipLaunchKernelGGL(sdr::k_scan_partials, dim3(1), dim3(256), 0, st, spart, nb);
+        hipLaunchKernelGGL(sdr::k_scan_apply, dim3(nb), dim3(256), 0, st, in, m, spart, o);
+    }
+
+    // the 64-bit keys (voxel << 32 | point) in (voxel, point) order: keyed, split into the sort's
+    // 32-bit pairs, sorted by as many 8-bit digits as g.bits needs, joined again
+    void sort(const sdr::VoxelGrid& g) {
+        uint64_t* keys = at<uint64_t>(a.keys);
+        uint32_t* kv[4];
+        for (int q = 0; q < 4; q++) kv[q] = at<uint32_t>(a.kv[q]);
+        int* hist = at<int>(a.hist);
+        hipLaunchKernelGGL(sdr::k_voxel_keys, grid(), dim3(256), 0, st, p, n, g.v, keys);
+        hipLaunchKernelGGL(sdr::k_voxel_split, grid(), dim3(256), 0, st, keys, n, g.past, kv[0], kv[1]);
+        int cur = 0;
+        for (int shift = 0; shift < g.bits; shift += 8) {
+            hipLaunchKernelGGL(sdr::k_rs_hist, dim3(a.nb_rs), dim3(256), 0, st, kv[cur], n, shift, hist, a.nb_rs);
+            scan(hist, a.nh, hist);
+            hipLaunchKernelGGL(sdr::k_rs_scatter, dim3(a.nb_rs), dim3(256), 0, st, kv[cur], kv[cur + 1], n, shift,
+                               hist, a.nb_rs, kv[2 - cur], kv[3 - cur]);
+            cur = 2 - cur;
+        }
+        hipLaunchKernelGGL(sdr::k_voxel_join, grid(), dim3(256), 0, st, kv[cur], kv[cur + 1], n, g.past,
+                           at<uint64_t>(a.sorted));
+    }
+
+    // one centroid a voxel, at the voxel's rank: the heads of the sorted runs, scanned
+    void centroids(float4* out) {
+        const uint64_t* sorted = at<uint64_t>(a.sorted);
+        int* head = at<int>(a.head);
+        int* pos = at<int>(a.pos);
+        hipLaunchKernelGGL(sdr::k_voxel_heads, grid(), dim3(256), 0, st, sorted, n, head);
+        scan(head, n, pos);
+        hipLaunchKernelGGL(sdr::k_voxel_centroid, grid(), dim3(256), 0, st, p, sorted, n, head, pos, out);
+    }
+
+    // the number of voxels: the last point's position, plus one when it heads a run; synchronises
+    int count(int* out_count) {
+        int last_pos = 0, last_head = 0;
+        SDR_HIP(hipMemcpyAsync(&last_pos, at<int>(a.pos) + n - 1, 4, hipMemcpyDeviceToHost, st));
+        SDR_HIP(hipMemcpyAsync(&last_head, at<int>(a.head) + n - 1, 4, hipMemcpyDeviceToHost, st));
+        ph.mark("copies");
+        SDR_HIP(hipStreamSynchronize(st));
+        ph.mark("sync");
+        *out_count = last_pos + last_head;
+        return SDR_OK;
     }
 };
 
@@ -386,138 +498,25 @@ int sdr_voxel_grid_device(const void* d_points, int n, float lx, float ly, float
     if (!d_points || !d_out || !out_count) return sdr::set_error(SDR_ERR_ARG, "null argument");
     if (n < 0) return sdr::set_error(SDR_ERR_ARG, "negative point count");
     if (!(lx > 0.0f) || !(ly > 0.0f) || !(lz > 0.0f)) return sdr::set_error(SDR_ERR_ARG, "leaf size must be > 0");
-    hipStream_t st = (hipStream_t)stream;
-#ifdef SDR_VOXEL_TIMING  // diagnostic: host-side phase times of one call on stderr
-    struct Phases {
-        std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), last = t0;
-        char buf[256];
-        int len = 0;
-        void mark(const char* what) {
-            const auto now = std::chrono::steady_clock::now();
-            len += std::snprintf(buf + len, sizeof(buf) - len, " %s %.1f", what,
-                                 std::chrono::duration<double, std::micro>(now - last).count());
-            last = now;
-        }
-        ~Phases() {
-            mark("end");
-            std::fprintf(stderr, "voxel_grid us:%s\n", buf);
-        }
-    } ph;
-#define VOXEL_MARK(w) ph.mark(w)
-#else
-#define VOXEL_MARK(w) (void)0
-#endif
-    const float4* p = (const float4*)d_points;
-    float4* out = (float4*)d_out;
     *out_count = 0;
     if (passthrough) *passthrough = 0;
     if (n == 0) return SDR_OK;
-    // the arena holds everything below: the min/max partials, then the keys, the sort's ping-pong
-    // (voxel, point) arrays, the heads and positions, the sort's histograms and the scan's totals
-    const size_t un = (size_t)n;
-    const int nb_rs = (n + sdr::kRsTile - 1) / sdr::kRsTile;
-    const int nh = 256 * nb_rs;
-    const int nb_scan = (std::max(n, nh) + sdr::kScanSeg - 1) / sdr::kScanSeg;
-    const size_t need = sizeof(float) * 7 * sdr::kMinMaxBlocks + un * (8 + 8 + 4 + 4 + 4 * 4) +
-                        sizeof(int) * ((size_t)nh + nb_scan) + 11 * 256;
-    ArenaLease scratch(st);
-    int rc = scratch.open(need);
+    VoxelCall c{(const float4*)d_points, n, (hipStream_t)stream, sdr::voxel_arena(n)};
+    ArenaLease scratch(c.st);
+    int rc = scratch.open(c.a.total);
     if (rc) return rc;
-    float* partial = (float*)scratch.get(sizeof(float) * 7 * sdr::kMinMaxBlocks);
-    if (!partial) return sdr::set_error(SDR_ERR_NOMEM, "scratch allocation failed");
-    const int mmb = std::min(sdr::kMinMaxBlocks, (n + 255) / 256);
-    hipLaunchKernelGGL(sdr::k_minmax, dim3(mmb), dim3(256), 0, st, p, n, partial);
+    c.base = scratch.a->buf.p;
+    float mn[3], mx[3];
+    long long nfin;
+    if ((rc = c.bounds(mn, mx, &nfin))) return rc;
+    const sdr::VoxelGrid g = sdr::voxel_grid(mn, mx, nfin, lx, ly, lz);
+    if (g.kind == sdr::VOXEL_EMPTY) return SDR_OK;
+    if (g.kind == sdr::VOXEL_PASSTHROUGH) return c.pass_through((float4*)d_out, out_count, passthrough);
+    c.sort(g);
+    c.centroids((float4*)d_out);
     SDR_HIP(hipGetLastError());
-    std::vector<float> hp((size_t)7 * mmb);
-    SDR_HIP(hipMemcpyAsync(hp.data(), partial, sizeof(float) * hp.size(), hipMemcpyDeviceToHost, st));
-    VOXEL_MARK("mm_launch");
-    SDR_HIP(hipStreamSynchronize(st));
-    VOXEL_MARK("mm_sync");
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    long long nfin = 0;
-    for (int b = 0; b < mmb; b++) {
-        for (int c = 0; c < 3; c++) {
-            mn[c] = std::fmin(mn[c], hp[b * 7 + c]);
-            mx[c] = std::fmax(mx[c], hp[b * 7 + 3 + c]);
-        }
-        int cnt;
-        std::memcpy(&cnt, &hp[b * 7 + 6], 4);
-        nfin += cnt;
-    }
-    if (!nfin) return SDR_OK;  // nothing finite: empty output
-    const float inv[3] = {1.0f / lx, 1.0f / ly, 1.0f / lz};
-    long long d[3];
-    for (int c = 0; c < 3; c++) d[c] = (long long)((mx[c] - mn[c]) * inv[c]) + 1;
-    const long long prod = (long long)((unsigned long long)d[0] * (unsigned long long)d[1] *
-                                       (unsigned long long)d[2]);
-    if (prod > 2147483647LL) {
-        // PCL: "Leaf size is too small for the input dataset. Integer indices would overflow." --
-        // the output is the input cloud unchanged
-        SDR_HIP(hipMemcpyAsync(out, p, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, st));
-        SDR_HIP(hipStreamSynchronize(st));
-        *out_count = n;
-        if (passthrough) *passthrough = 1;
-        return SDR_OK;
-    }
-    sdr::VoxelParams v;
-    int div[3];
-    for (int c = 0; c < 3; c++) {
-        v.inv[c] = inv[c];
-        v.minb[c] = (int)std::floor(mn[c] * inv[c]);
-        const int maxb = (int)std::floor(mx[c] * inv[c]);
-        div[c] = maxb - v.minb[c] + 1;
-    }
-    v.mul1 = (uint32_t)div[0];
-    v.mul2 = (uint32_t)div[0] * (uint32_t)div[1];
-    uint64_t* keys = (uint64_t*)scratch.get(sizeof(uint64_t) * n);
-    uint64_t* sorted = (uint64_t*)scratch.get(sizeof(uint64_t) * n);
-    int* head = (int*)scratch.get(sizeof(int) * n);
-    int* pos = (int*)scratch.get(sizeof(int) * n);
-    // the sort's ping-pong (voxel, point) arrays and its histograms; the scan's block totals
-    uint32_t* kv[4];
-    for (auto& q : kv) q = (uint32_t*)scratch.get(sizeof(uint32_t) * n);
-    int* hist = (int*)scratch.get(sizeof(int) * nh);
-    int* spart = (int*)scratch.get(sizeof(int) * nb_scan);
-    if (!keys || !sorted || !head || !pos || !kv[0] || !kv[1] || !kv[2] || !kv[3] || !hist || !spart)
-        return sdr::set_error(SDR_ERR_NOMEM, "scratch allocation failed");
-    VOXEL_MARK("alloc");
-    const dim3 grid((n + 255) / 256);
-    auto scan = [&](const int* in, int m, int* o) {
-        const int nb = (m + sdr::kScanSeg - 1) / sdr::kScanSeg;
-        hipLaunchKernelGGL(sdr::k_scan_reduce, dim3(nb), dim3(256), 0, st, in, m, spart);
-        hipLaunchKernelGGL(sdr::k_scan_partials, dim3(1), dim3(256), 0, st, spart, nb);
-        hipLaunchKernelGGL(sdr::k_scan_apply, dim3(nb), dim3(256), 0, st, in, m, spart, o);
-    };
-    hipLaunchKernelGGL(sdr::k_voxel_keys, grid, dim3(256), 0, st, p, n, v, keys);
-    // voxel indices are below div0 * div1 * div2 (each div at most one above PCL's d, whose product
-    // passed the overflow check); `past` = that bound marks the non-finite points, which sort last
-    const unsigned long long divprod = (unsigned long long)div[0] * (unsigned long long)div[1] * (unsigned long long)div[2];
-    const uint32_t past = divprod < 0xFFFFFFFFull ? (uint32_t)divprod : 0xFFFFFFFFu;
-    int bits = 1;
-    while (bits < 32 && (past >> bits) != 0) bits++;
-    hipLaunchKernelGGL(sdr::k_voxel_split, grid, dim3(256), 0, st, keys, n, past, kv[0], kv[1]);
-    int cur = 0;
-    for (int shift = 0; shift < bits; shift += 8) {
-        hipLaunchKernelGGL(sdr::k_rs_hist, dim3(nb_rs), dim3(256), 0, st, kv[cur], n, shift, hist, nb_rs);
-        scan(hist, nh, hist);
-        hipLaunchKernelGGL(sdr::k_rs_scatter, dim3(nb_rs), dim3(256), 0, st, kv[cur], kv[cur + 1], n, shift, hist,
-                           nb_rs, kv[2 - cur], kv[3 - cur]);
-        cur = 2 - cur;
-    }
-    hipLaunchKernelGGL(sdr::k_voxel_join, grid, dim3(256), 0, st, kv[cur], kv[cur + 1], n, past, sorted);
-    hipLaunchKernelGGL(sdr::k_voxel_heads, grid, dim3(256), 0, st, sorted, n, head);
-    scan(head, n, pos);
-    hipLaunchKernelGGL(sdr::k_voxel_centroid, grid, dim3(256), 0, st, p, sorted, n, head, pos, out);
-    SDR_HIP(hipGetLastError());
-    VOXEL_MARK("launches");
-    int last_pos = 0, last_head = 0;
-    SDR_HIP(hipMemcpyAsync(&last_pos, pos + n - 1, 4, hipMemcpyDeviceToHost, st));
-    SDR_HIP(hipMemcpyAsync(&last_head, head + n - 1, 4, hipMemcpyDeviceToHost, st));
-    VOXEL_MARK("copies");
-    SDR_HIP(hipStreamSynchronize(st));
-    VOXEL_MARK("sync");
-    *out_count = last_pos + last_head;
-    return SDR_OK;
+    c.ph.mark("launches");
+    return c.count(out_count);
 }
 
 int sdr_pcd_header(int width, int height, char* buf, size_t cap) {

@@ -17,9 +17,10 @@
 // single-lane kernel that keeps the smoothing state on the device so the sequence stays
 // asynchronous.  Batches of F frames are handled in frame order: the EMA state of pixel i is
 // carried through the frames by the thread that owns pixel i.  The rounding rules follow
-// oracle/display_oracle.c (recorded OpenCV assumptions there).
+// oracle/display_oracle.c (recorded OpenCV assumptions there).  The sdr_display handle's device,
+// stream binding and release are sdr_host.hpp's Bound.
 #include "../../include/sdr/sdr.h"
-#include "sdr_internal.hpp"
+#include "sdr_host.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -236,28 +237,23 @@ static int colormap_lut(int cmap, uint8_t* lut) {
 
 }  // namespace sdr
 
-struct sdr_display {
-    int device = 0;
-    hipStream_t stream = nullptr, own_stream = nullptr;
+struct sdr_display : sdr::Bound {
     sdr::Buf prev_vis, prev_depth, zrange, stats, ab, stage_in, stage_out, stage_left, stage_vis, stage_zr;
     int vis_w = 0, vis_h = 0;      // prev_vis size (0 = empty)
     int depth_w = 0, depth_h = 0;  // prev_depth_vis size
     sdr::Lut turbo{}, jet{};
     double zinit[2] = {1000.0, 2000.0};
+    sdr_display()
+        : Bound{&prev_vis, &prev_depth, &zrange, &stats, &ab, &stage_in, &stage_out, &stage_left, &stage_vis, &stage_zr} {}
 };
 
 namespace {
-int dfail(int code, const char* msg) { return sdr::set_error(code, msg); }
-#define SDR_DHIP(call)                                                              \
-    do {                                                                            \
-        hipError_t e_ = (call);                                                     \
-        if (e_ != hipSuccess) return dfail(SDR_ERR_DEVICE, hipGetErrorString(e_)); \
-    } while (0)
+using sdr::set_error;
 
 // static double zmin_smooth = 1000.0, zmax_smooth = 2000.0: the copy is ordered on the handle's
 // current stream, from memory the handle owns (a pageable source may be read after the call)
 int reset_zrange(sdr_display* h) {
-    SDR_DHIP(hipMemcpyAsync(h->zrange.p, h->zinit, sizeof(h->zinit), hipMemcpyHostToDevice, h->stream));
+    SDR_HIP(hipMemcpyAsync(h->zrange.p, h->zinit, sizeof(h->zinit), hipMemcpyHostToDevice, h->stream));
     return SDR_OK;
 }
 
@@ -266,6 +262,14 @@ sdr::Lut lut_or(const uint8_t* user, const sdr::Lut& dflt) {
     sdr::Lut l;
     std::memcpy(l.v, user, 768);
     return l;
+}
+
+// the per-frame statistics of F frames of Z into h->stats (reserved by the caller)
+void launch_zstats(sdr_display* h, const float* d_xyz, int W, int H, int channels, int F, int col0) {
+    sdr::ZStats* st = (sdr::ZStats*)h->stats.p;
+    hipLaunchKernelGGL(sdr::k_zstats_init, dim3((F + 63) / 64), dim3(64), 0, h->stream, st, F);
+    hipLaunchKernelGGL(sdr::k_zstats, dim3((W + 255) / 256, H, F), dim3(256), 0, h->stream, d_xyz, channels,
+                       W, H, col0, st);
 }
 
 // the shared part of show_depthMap: stats -> range recurrence -> TURBO + EMA
@@ -279,11 +283,8 @@ int depth_map(sdr_display* h, const float* d_xyz, int W, int H, int channels, in
     if (!same) {
         if ((rc = sdr::ensure(h->prev_depth, px * 3))) return rc;
     }
-    sdr::ZStats* st = (sdr::ZStats*)h->stats.p;
-    hipLaunchKernelGGL(sdr::k_zstats_init, dim3((F + 63) / 64), dim3(64), 0, h->stream, st, F);
-    hipLaunchKernelGGL(sdr::k_zstats, dim3((W + 255) / 256, H, F), dim3(256), 0, h->stream, d_xyz, channels,
-                       W, H, col0, st);
-    hipLaunchKernelGGL(sdr::k_zrange, dim3(1), dim3(64), 0, h->stream, st, F,
+    launch_zstats(h, d_xyz, W, H, channels, F, col0);
+    hipLaunchKernelGGL(sdr::k_zrange, dim3(1), dim3(64), 0, h->stream, (const sdr::ZStats*)h->stats.p, F,
                        d_zr ? d_zr : (double*)h->zrange.p, (float2*)h->ab.p);
     if (d_out) {
         hipLaunchKernelGGL(sdr::k_depth_vis, dim3((W + 255) / 256, H), dim3(256), 0, h->stream, d_xyz,
@@ -292,7 +293,7 @@ int depth_map(sdr_display* h, const float* d_xyz, int W, int H, int channels, in
         h->depth_w = W;
         h->depth_h = H;
     }
-    SDR_DHIP(hipGetLastError());
+    SDR_HIP(hipGetLastError());
     return SDR_OK;
 }
 
@@ -301,42 +302,55 @@ int read_coverage(sdr_display* h, int W, int H, int F, double* pct) {
     sdr::ZStats tmp[64];
     for (int f0 = 0; f0 < F; f0 += 64) {
         const int n = F - f0 < 64 ? F - f0 : 64;
-        SDR_DHIP(hipMemcpyAsync(tmp, (sdr::ZStats*)h->stats.p + f0, n * sizeof(sdr::ZStats),
+        SDR_HIP(hipMemcpyAsync(tmp, (sdr::ZStats*)h->stats.p + f0, n * sizeof(sdr::ZStats),
                                 hipMemcpyDeviceToHost, h->stream));
-        SDR_DHIP(hipStreamSynchronize(h->stream));
+        SDR_HIP(hipStreamSynchronize(h->stream));
         for (int k = 0; k < n; k++) pct[f0 + k] = ((double)tmp[k].count / ((double)W * H)) * 100;
     }
     return SDR_OK;
 }
+
+// ---- the host-pointer entries' steps: reserve the staging buffers (sdr::ensure), stage in, the
+// device form, stage out, finish; pageable copies on the handle's stream, in call order ----
+using sdr::ensure;
+int copy(sdr_display* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    SDR_HIP(hipMemcpyAsync(dst, src, bytes, kind, h->stream));
+    return SDR_OK;
+}
+int copy_rows(sdr_display* h, void* dst, size_t dpitch, const void* src, size_t spitch, size_t row_bytes,
+              size_t rows, hipMemcpyKind kind) {
+    SDR_HIP(hipMemcpy2DAsync(dst, dpitch, src, spitch, row_bytes, rows, kind, h->stream));
+    return SDR_OK;
+}
+int finish(sdr_display* h) {
+    SDR_HIP(hipStreamSynchronize(h->stream));
+    return SDR_OK;
+}
+constexpr hipMemcpyKind kIn = hipMemcpyHostToDevice, kOut = hipMemcpyDeviceToHost;
 }  // namespace
 
 extern "C" {
 
 int sdr_colormap_lut(int colormap, uint8_t* lut_bgr) {
-    if (!lut_bgr) return dfail(SDR_ERR_ARG, "null argument");
-    return sdr::colormap_lut(colormap, lut_bgr) ? dfail(SDR_ERR_ARG, "unknown colormap") : SDR_OK;
+    if (!lut_bgr) return set_error(SDR_ERR_ARG, "null argument");
+    return sdr::colormap_lut(colormap, lut_bgr) ? set_error(SDR_ERR_ARG, "unknown colormap") : SDR_OK;
 }
 
 int sdr_display_create(int device, sdr_display** out) {
-    if (!out) return dfail(SDR_ERR_ARG, "null argument");
+    if (!out) return set_error(SDR_ERR_ARG, "null argument");
     *out = nullptr;
-    int ndev = 0;
-    SDR_DHIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return dfail(SDR_ERR_DEVICE, "invalid device index");
-    SDR_DHIP(hipSetDevice(device));
     sdr_display* h = new sdr_display();
-    h->device = device;
-    if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) {
+    int rc = h->open(device);
+    if (rc) {
         delete h;
-        return dfail(SDR_ERR_DEVICE, "hipStreamCreate failed");
+        return rc;
     }
-    h->stream = h->own_stream;
     sdr::colormap_lut(SDR_COLORMAP_TURBO, h->turbo.v);
     sdr::colormap_lut(SDR_COLORMAP_JET, h->jet.v);
-    int rc = sdr::ensure(h->zrange, 2 * sizeof(double));
+    rc = sdr::ensure(h->zrange, 2 * sizeof(double));
     // blocking copy: later work may run on any stream the caller sets
     if (!rc && hipMemcpy(h->zrange.p, h->zinit, sizeof(h->zinit), hipMemcpyHostToDevice) != hipSuccess)
-        rc = dfail(SDR_ERR_DEVICE, "hipMemcpy failed");
+        rc = set_error(SDR_ERR_DEVICE, "hipMemcpy failed");
     if (rc) {
         sdr_display_destroy(h);
         return rc;
@@ -347,30 +361,25 @@ int sdr_display_create(int device, sdr_display** out) {
 
 int sdr_display_destroy(sdr_display* h) {
     if (!h) return SDR_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (sdr::Buf* b : {&h->prev_vis, &h->prev_depth, &h->zrange, &h->stats, &h->ab, &h->stage_in,
-                        &h->stage_out, &h->stage_left, &h->stage_vis, &h->stage_zr})
-        if (b->p) (void)hipFree(b->p);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    h->close();
     delete h;
     return SDR_OK;
 }
 
 int sdr_display_set_stream(sdr_display* h, void* stream) {
-    if (!h) return dfail(SDR_ERR_ARG, "null handle");
-    h->stream = (hipStream_t)stream;  // NULL = the HIP null stream (torch's default stream)
+    if (!h) return set_error(SDR_ERR_ARG, "null handle");
+    h->bind(stream);  // NULL: torch's default stream
     return SDR_OK;
 }
 
 int sdr_display_reset_stream(sdr_display* h) {
-    if (!h) return dfail(SDR_ERR_ARG, "null handle");
-    h->stream = h->own_stream;
+    if (!h) return set_error(SDR_ERR_ARG, "null handle");
+    h->unbind();
     return SDR_OK;
 }
 
 int sdr_display_reset(sdr_display* h) {
-    if (!h) return dfail(SDR_ERR_ARG, "null handle");
+    if (!h) return set_error(SDR_ERR_ARG, "null handle");
     (void)hipSetDevice(h->device);
     h->vis_w = h->vis_h = h->depth_w = h->depth_h = 0;
     return reset_zrange(h);
@@ -378,9 +387,9 @@ int sdr_display_reset(sdr_display* h) {
 
 int sdr_show_disparity_map_device(sdr_display* h, const float* d_disp, int W, int H, size_t stride,
                                   size_t frame_stride, int F, int num_disparities, uint8_t* d_vis) {
-    if (!h || !d_disp || !d_vis) return dfail(SDR_ERR_ARG, "null argument");
-    if (W <= 0 || H <= 0 || F <= 0 || stride < (size_t)W) return dfail(SDR_ERR_ARG, "bad size");
-    SDR_DHIP(hipSetDevice(h->device));
+    if (!h || !d_disp || !d_vis) return set_error(SDR_ERR_ARG, "null argument");
+    if (W <= 0 || H <= 0 || F <= 0 || stride < (size_t)W) return set_error(SDR_ERR_ARG, "bad size");
+    SDR_HIP(hipSetDevice(h->device));
     const bool same = h->vis_w == W && h->vis_h == H;
     int rc;
     if (!same && (rc = sdr::ensure(h->prev_vis, (size_t)W * H))) return rc;
@@ -390,17 +399,17 @@ int sdr_show_disparity_map_device(sdr_display* h, const float* d_disp, int W, in
                        F > 1 ? frame_stride : 0, W, H, F, scale, (uint8_t*)h->prev_vis.p, same ? 1 : 0, d_vis);
     h->vis_w = W;
     h->vis_h = H;
-    SDR_DHIP(hipGetLastError());
+    SDR_HIP(hipGetLastError());
     return SDR_OK;
 }
 
 int sdr_show_depth_map_device(sdr_display* h, const float* d_xyz, int W, int H, int channels, int F,
                               double* d_zrange, const uint8_t* lut_bgr, uint8_t* d_bgr,
                               double* coverage_pct) {
-    if (!h || !d_xyz || !d_bgr) return dfail(SDR_ERR_ARG, "null argument");
-    if (W <= 0 || H <= 0 || F <= 0) return dfail(SDR_ERR_ARG, "bad size");
-    if (channels != 1 && channels != 3) return dfail(SDR_ERR_TYPE, "depth must have 1 or 3 channels");
-    SDR_DHIP(hipSetDevice(h->device));
+    if (!h || !d_xyz || !d_bgr) return set_error(SDR_ERR_ARG, "null argument");
+    if (W <= 0 || H <= 0 || F <= 0) return set_error(SDR_ERR_ARG, "bad size");
+    if (channels != 1 && channels != 3) return set_error(SDR_ERR_TYPE, "depth must have 1 or 3 channels");
+    SDR_HIP(hipSetDevice(h->device));
     int rc = depth_map(h, d_xyz, W, H, channels, F, d_zrange, lut_bgr, d_bgr, 80);
     if (rc) return rc;
     return read_coverage(h, W, H, F, coverage_pct);
@@ -408,16 +417,13 @@ int sdr_show_depth_map_device(sdr_display* h, const float* d_xyz, int W, int H, 
 
 int sdr_depth_coverage_device(sdr_display* h, const float* d_xyz, int W, int H, int F, int col0,
                               double* pct) {
-    if (!h || !d_xyz || !pct) return dfail(SDR_ERR_ARG, "null argument");
-    if (W <= 0 || H <= 0 || F <= 0) return dfail(SDR_ERR_ARG, "bad size");
-    SDR_DHIP(hipSetDevice(h->device));
+    if (!h || !d_xyz || !pct) return set_error(SDR_ERR_ARG, "null argument");
+    if (W <= 0 || H <= 0 || F <= 0) return set_error(SDR_ERR_ARG, "bad size");
+    SDR_HIP(hipSetDevice(h->device));
     int rc;
     if ((rc = sdr::ensure(h->stats, (size_t)F * sizeof(sdr::ZStats)))) return rc;
-    sdr::ZStats* st = (sdr::ZStats*)h->stats.p;
-    hipLaunchKernelGGL(sdr::k_zstats_init, dim3((F + 63) / 64), dim3(64), 0, h->stream, st, F);
-    hipLaunchKernelGGL(sdr::k_zstats, dim3((W + 255) / 256, H, F), dim3(256), 0, h->stream, d_xyz, 3, W, H,
-                       col0, st);
-    SDR_DHIP(hipGetLastError());
+    launch_zstats(h, d_xyz, W, H, 3, F, col0);
+    SDR_HIP(hipGetLastError());
     return read_coverage(h, W, H, F, pct);
 }
 
@@ -425,14 +431,14 @@ int sdr_disparity_overlay_device(sdr_display* h, const uint8_t* d_vis, const uin
                                  size_t left_stride, size_t left_frame_stride, int W, int H, int F,
                                  const uint8_t* lut_bgr, uint8_t* d_heat, uint8_t* d_overlay) {
     if (!h || !d_vis || (!d_heat && !d_overlay) || (d_overlay && !d_left_bgr))
-        return dfail(SDR_ERR_ARG, "null argument");
-    if (W <= 0 || H <= 0 || F <= 0) return dfail(SDR_ERR_ARG, "bad size");
-    if (d_left_bgr && left_stride < (size_t)W * 6) return dfail(SDR_ERR_ARG, "left_stride < 3 * (2 * width)");
-    SDR_DHIP(hipSetDevice(h->device));
+        return set_error(SDR_ERR_ARG, "null argument");
+    if (W <= 0 || H <= 0 || F <= 0) return set_error(SDR_ERR_ARG, "bad size");
+    if (d_left_bgr && left_stride < (size_t)W * 6) return set_error(SDR_ERR_ARG, "left_stride < 3 * (2 * width)");
+    SDR_HIP(hipSetDevice(h->device));
     hipLaunchKernelGGL(sdr::k_overlay, dim3((W + 255) / 256, H, F), dim3(256), 0, h->stream, d_vis,
                        d_left_bgr, left_stride, left_frame_stride ? left_frame_stride : left_stride * 2 * H,
                        W, H, lut_or(lut_bgr, h->jet), d_heat, d_overlay);
-    SDR_DHIP(hipGetLastError());
+    SDR_HIP(hipGetLastError());
     return SDR_OK;
 }
 
@@ -440,80 +446,72 @@ int sdr_disparity_overlay_device(sdr_display* h, const uint8_t* d_vis, const uin
 
 int sdr_show_disparity_map(sdr_display* h, const float* disp, int W, int H, size_t stride,
                            int num_disparities, uint8_t* out, size_t out_stride) {
-    if (!h || !disp || !out) return dfail(SDR_ERR_ARG, "null argument");
-    if (W <= 0 || H <= 0 || stride < (size_t)W || out_stride < (size_t)W) return dfail(SDR_ERR_ARG, "bad size");
-    SDR_DHIP(hipSetDevice(h->device));
-    const size_t px = (size_t)W * H;
+    if (!h || !disp || !out) return set_error(SDR_ERR_ARG, "null argument");
+    if (W <= 0 || H <= 0 || stride < (size_t)W || out_stride < (size_t)W) return set_error(SDR_ERR_ARG, "bad size");
+    SDR_HIP(hipSetDevice(h->device));
+    const size_t px = (size_t)W * H, row = (size_t)W * 4;
     int rc;
-    if ((rc = sdr::ensure(h->stage_in, px * 4)) || (rc = sdr::ensure(h->stage_vis, px))) return rc;
-    SDR_DHIP(hipMemcpy2DAsync(h->stage_in.p, W * 4, disp, stride * 4, W * 4, H, hipMemcpyHostToDevice, h->stream));
-    if ((rc = sdr_show_disparity_map_device(h, (const float*)h->stage_in.p, W, H, W, px, 1, num_disparities,
-                                            (uint8_t*)h->stage_vis.p)))
+    if ((rc = ensure(h->stage_in, px * 4)) || (rc = ensure(h->stage_vis, px)) ||
+        (rc = copy_rows(h, h->stage_in.p, row, disp, stride * 4, row, H, kIn)) ||
+        (rc = sdr_show_disparity_map_device(h, (const float*)h->stage_in.p, W, H, W, px, 1, num_disparities,
+                                            (uint8_t*)h->stage_vis.p)) ||
+        (rc = copy_rows(h, out, out_stride, h->stage_vis.p, W, W, H, kOut)))
         return rc;
-    SDR_DHIP(hipMemcpy2DAsync(out, out_stride, h->stage_vis.p, W, W, H, hipMemcpyDeviceToHost, h->stream));
-    SDR_DHIP(hipStreamSynchronize(h->stream));
-    return SDR_OK;
+    return finish(h);
 }
 
 int sdr_show_depth_map(sdr_display* h, const float* xyz, int W, int H, int channels, double* zrange,
                        uint8_t* out_bgr, double* coverage_pct) {
-    if (!h || !xyz || !out_bgr) return dfail(SDR_ERR_ARG, "null argument");
-    if (W <= 0 || H <= 0) return dfail(SDR_ERR_ARG, "bad size");
-    if (channels != 1 && channels != 3) return dfail(SDR_ERR_TYPE, "depth must have 1 or 3 channels");
-    SDR_DHIP(hipSetDevice(h->device));
+    if (!h || !xyz || !out_bgr) return set_error(SDR_ERR_ARG, "null argument");
+    if (W <= 0 || H <= 0) return set_error(SDR_ERR_ARG, "bad size");
+    if (channels != 1 && channels != 3) return set_error(SDR_ERR_TYPE, "depth must have 1 or 3 channels");
+    SDR_HIP(hipSetDevice(h->device));
     const size_t px = (size_t)W * H;
     int rc;
-    if ((rc = sdr::ensure(h->stage_in, px * 4 * channels)) || (rc = sdr::ensure(h->stage_out, px * 3)) ||
-        (rc = sdr::ensure(h->stage_zr, 2 * sizeof(double))))
+    constexpr size_t kZr = 2 * sizeof(double);
+    if ((rc = ensure(h->stage_in, px * 4 * channels)) || (rc = ensure(h->stage_out, px * 3)) ||
+        (rc = ensure(h->stage_zr, kZr)))
         return rc;
-    double* dzr = nullptr;
-    SDR_DHIP(hipMemcpyAsync(h->stage_in.p, xyz, px * 4 * channels, hipMemcpyHostToDevice, h->stream));
-    if (zrange) {  // caller-owned range state (the reference's function-static doubles)
-        dzr = (double*)h->stage_zr.p;
-        SDR_DHIP(hipMemcpyAsync(dzr, zrange, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    }
-    if ((rc = sdr_show_depth_map_device(h, (const float*)h->stage_in.p, W, H, channels, 1, dzr, nullptr,
-                                        (uint8_t*)h->stage_out.p, coverage_pct)))
+    // caller-owned range state (the reference's function-static doubles), staged there and back
+    double* dzr = zrange ? (double*)h->stage_zr.p : nullptr;
+    if ((rc = copy(h, h->stage_in.p, xyz, px * 4 * channels, kIn)) || (zrange && (rc = copy(h, dzr, zrange, kZr, kIn))) ||
+        (rc = sdr_show_depth_map_device(h, (const float*)h->stage_in.p, W, H, channels, 1, dzr, nullptr,
+                                        (uint8_t*)h->stage_out.p, coverage_pct)) ||
+        (rc = copy(h, out_bgr, h->stage_out.p, px * 3, kOut)) || (zrange && (rc = copy(h, zrange, dzr, kZr, kOut))))
         return rc;
-    SDR_DHIP(hipMemcpyAsync(out_bgr, h->stage_out.p, px * 3, hipMemcpyDeviceToHost, h->stream));
-    if (zrange) SDR_DHIP(hipMemcpyAsync(zrange, dzr, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    SDR_DHIP(hipStreamSynchronize(h->stream));
-    return SDR_OK;
+    return finish(h);
 }
 
 int sdr_depth_coverage(sdr_display* h, const float* xyz, int W, int H, int col0, double* pct) {
-    if (!h || !xyz || !pct) return dfail(SDR_ERR_ARG, "null argument");
-    if (W <= 0 || H <= 0) return dfail(SDR_ERR_ARG, "bad size");
-    SDR_DHIP(hipSetDevice(h->device));
+    if (!h || !xyz || !pct) return set_error(SDR_ERR_ARG, "null argument");
+    if (W <= 0 || H <= 0) return set_error(SDR_ERR_ARG, "bad size");
+    SDR_HIP(hipSetDevice(h->device));
+    const size_t bytes = (size_t)W * H * 12;
     int rc;
-    if ((rc = sdr::ensure(h->stage_in, (size_t)W * H * 12))) return rc;
-    SDR_DHIP(hipMemcpyAsync(h->stage_in.p, xyz, (size_t)W * H * 12, hipMemcpyHostToDevice, h->stream));
-    // statistics only: the handle's EMA history and range state are not touched
+    if ((rc = ensure(h->stage_in, bytes)) || (rc = copy(h, h->stage_in.p, xyz, bytes, kIn))) return rc;
+    // statistics only: the handle's EMA history and range state are not touched; the device form
+    // synchronises when it reads the counts back
     return sdr_depth_coverage_device(h, (const float*)h->stage_in.p, W, H, 1, col0, pct);
 }
 
 int sdr_disparity_overlay(sdr_display* h, const uint8_t* vis, const uint8_t* left_bgr, size_t left_stride,
                           int W, int H, uint8_t* heat, uint8_t* overlay) {
-    if (!h || !vis || !left_bgr || (!heat && !overlay)) return dfail(SDR_ERR_ARG, "null argument");
-    if (W <= 0 || H <= 0 || left_stride < (size_t)W * 6) return dfail(SDR_ERR_ARG, "bad size");
-    SDR_DHIP(hipSetDevice(h->device));
-    const size_t px = (size_t)W * H;
+    if (!h || !vis || !left_bgr || (!heat && !overlay)) return set_error(SDR_ERR_ARG, "null argument");
+    if (W <= 0 || H <= 0 || left_stride < (size_t)W * 6) return set_error(SDR_ERR_ARG, "bad size");
+    SDR_HIP(hipSetDevice(h->device));
+    const size_t px = (size_t)W * H, row = (size_t)W * 6;
     int rc;
-    if ((rc = sdr::ensure(h->stage_vis, px)) || (rc = sdr::ensure(h->stage_left, px * 12)) ||
-        (rc = sdr::ensure(h->stage_out, px * 6)))
+    if ((rc = ensure(h->stage_vis, px)) || (rc = ensure(h->stage_left, px * 12)) || (rc = ensure(h->stage_out, px * 6)))
         return rc;
     uint8_t* dh = (uint8_t*)h->stage_out.p;
     uint8_t* dov = dh + px * 3;
-    SDR_DHIP(hipMemcpyAsync(h->stage_vis.p, vis, px, hipMemcpyHostToDevice, h->stream));
-    SDR_DHIP(hipMemcpy2DAsync(h->stage_left.p, (size_t)W * 6, left_bgr, left_stride, (size_t)W * 6, 2 * H,
-                              hipMemcpyHostToDevice, h->stream));
-    if ((rc = sdr_disparity_overlay_device(h, (const uint8_t*)h->stage_vis.p, (const uint8_t*)h->stage_left.p,
-                                           (size_t)W * 6, 0, W, H, 1, nullptr, dh, dov)))
+    if ((rc = copy(h, h->stage_vis.p, vis, px, kIn)) ||
+        (rc = copy_rows(h, h->stage_left.p, row, left_bgr, left_stride, row, 2 * (size_t)H, kIn)) ||
+        (rc = sdr_disparity_overlay_device(h, (const uint8_t*)h->stage_vis.p, (const uint8_t*)h->stage_left.p, row, 0,
+                                           W, H, 1, nullptr, dh, dov)) ||
+        (heat && (rc = copy(h, heat, dh, px * 3, kOut))) || (overlay && (rc = copy(h, overlay, dov, px * 3, kOut))))
         return rc;
-    if (heat) SDR_DHIP(hipMemcpyAsync(heat, dh, px * 3, hipMemcpyDeviceToHost, h->stream));
-    if (overlay) SDR_DHIP(hipMemcpyAsync(overlay, dov, px * 3, hipMemcpyDeviceToHost, h->stream));
-    SDR_DHIP(hipStreamSynchronize(h->stream));
-    return SDR_OK;
+    return finish(h);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // sdr_entries.hip -- the C entries that take no matcher handle: the error text, parameter
 // defaults, reprojection, the post filters and conversions on a caller's stream, the probes and
-// the self-test (their kernels: sdr_post.hip).
+// the self-test (their kernels: sdr_post.hip).  sdr_reproject, the one host-pointer entry here,
+// keeps its stream, buffers and staging a thread (sdr_host.hpp ThreadState).
 #include "sdr_host.hpp"
 #include "sdr_staging.hpp"
 
@@ -9,7 +10,17 @@
 
 namespace {
 thread_local std::string g_last_error;
-}
+
+// what sdr_reproject keeps a thread (sdr_host.hpp ThreadState): device buffers and staging
+struct ReprojectRes {
+    sdr::Buf dd, dx, mins;
+    sdr::HostXfer hx;
+    void release() {
+        sdr::free_bufs({&dd, &dx, &mins});
+        hx.release();
+    }
+};
+}  // namespace
 
 int sdr::set_error(int code, const std::string& msg) {
     g_last_error = msg;
@@ -117,35 +128,8 @@ int sdr_reproject(const float* disp, int W, int H, size_t disp_stride, const dou
     int rc = check_dims(W, H, disp_stride, 1);
     if (rc) return rc;
     if (xyz_stride < (size_t)W * 3) return set_error(SDR_ERR_ARG, "xyz_stride < 3*width");
-    // per-thread persistent device buffers, staging and stream (per current device)
-    struct State {
-        int device = -1;
-        hipStream_t st = nullptr;
-        Buf dd, dx, mins;
-        sdr::HostXfer hx;
-        ~State() {
-            if (device < 0) return;
-            (void)hipSetDevice(device);
-            if (st) (void)hipStreamSynchronize(st);
-            for (Buf* b : {&dd, &dx, &mins})
-                if (b->p) (void)hipFree(b->p);
-            hx.release();
-            if (st) (void)hipStreamDestroy(st);
-        }
-    };
-    static thread_local State S;
-    int dev = 0;
-    SDR_HIP(hipGetDevice(&dev));
-    if (S.device != dev) {
-        if (S.device >= 0) {
-            (void)hipSetDevice(S.device);
-            S.~State();
-            new (&S) State();
-            SDR_HIP(hipSetDevice(dev));
-        }
-        SDR_HIP(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
-        S.device = dev;
-    }
+    static thread_local sdr::ThreadState<ReprojectRes> S;
+    if ((rc = S.acquire())) return rc;
     const size_t px = (size_t)W * H;
     if ((rc = ensure(S.dd, px * 4)) || (rc = ensure(S.dx, px * 12)) || (rc = ensure(S.mins, 4))) return rc;
     if ((rc = S.hx.begin(stage_bytes(px * 4) + stage_bytes(px * 12)))) return rc;

@@ -15,6 +15,8 @@
 //                    (a) rectified BGR (optional, display/colour) and/or
 //                    (b) BGR2GRAY + INTER_AREA 0.5x of the rectified eye (the class path's
 //                        stereo_disparity.cpp:19-24 pre-steps), each rounding kept as OpenCV does
+// The sdr_rectifier handle holds both eyes' maps; its device, stream binding and release are
+// sdr_host.hpp's Bound.
 #include "../../include/sdr/sdr.h"
 #include "sdr_host.hpp"
 
@@ -213,13 +215,18 @@ __global__ __launch_bounds__(256) void k_sbs_ingest(SbsArgs a) {
 // ===========================================================================================
 // C ABI (include/sdr/sdr.h)
 // ===========================================================================================
-struct sdr_rectifier {
-    int device = 0, W = 0, H = 0;
-    hipStream_t stream = nullptr, own_stream = nullptr;
+struct sdr_rectifier : sdr::Bound {
+    int W = 0, H = 0;
     sdr::Buf map1[2], map2[2];
+    sdr_rectifier() : Bound{&map1[0], &map1[1], &map2[0], &map2[1]} {}
 };
 
 namespace {
+
+int check_map_size(int W, int H) {
+    if (W > 32767 || H > 32767) return sdr::set_error(SDR_ERR_SIZE, "CV_16SC2 maps need size < 32768");
+    return SDR_OK;
+}
 
 // iR = inv(P[:, :3] * R): gemm with sums from k = 0, then cv::invert(DECOMP_LU)'s closed form
 // for n = 3 (det3, cofactors times 1/det); host f64, the same expression order as the oracle
@@ -283,24 +290,17 @@ int sdr_init_undistort_rectify_map(const double K[9], const double* dist, int nd
                                    const double* P, int p_cols, int W, int H, int device,
                                    int16_t* map1, uint16_t* map2) {
     if (!map1 || !map2 || W <= 0 || H <= 0) return sdr::set_error(SDR_ERR_ARG, "bad map arguments");
-    if (W > 32767 || H > 32767) return sdr::set_error(SDR_ERR_SIZE, "CV_16SC2 maps need size < 32768");
     sdr::MapParams m;
-    int rc = make_map_params(K, dist, ndist, R, P, p_cols, &m);
-    if (rc) return rc;
+    int rc;
+    if ((rc = check_map_size(W, H)) || (rc = make_map_params(K, dist, ndist, R, P, p_cols, &m))) return rc;
     SDR_HIP(hipSetDevice(device));
     const size_t px = (size_t)W * H;
-    int16_t* d1 = nullptr;
-    uint16_t* d2 = nullptr;
-    SDR_HIP(hipMalloc((void**)&d1, px * 4));
-    if (hipMalloc((void**)&d2, px * 2) != hipSuccess) {
-        (void)hipFree(d1);
-        return sdr::set_error(SDR_ERR_NOMEM, "hipMalloc failed");
-    }
-    rc = enqueue_init_map(m, W, H, d1, d2, nullptr);
-    if (!rc && hipMemcpy(map1, d1, px * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = SDR_ERR_DEVICE;
-    if (!rc && hipMemcpy(map2, d2, px * 2, hipMemcpyDeviceToHost) != hipSuccess) rc = SDR_ERR_DEVICE;
-    (void)hipFree(d1);
-    (void)hipFree(d2);
+    sdr::Buf d1, d2;
+    if (!(rc = sdr::ensure(d1, px * 4)) && !(rc = sdr::ensure(d2, px * 2)))
+        rc = enqueue_init_map(m, W, H, (int16_t*)d1.p, (uint16_t*)d2.p, nullptr);
+    if (!rc && hipMemcpy(map1, d1.p, px * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = SDR_ERR_DEVICE;
+    if (!rc && hipMemcpy(map2, d2.p, px * 2, hipMemcpyDeviceToHost) != hipSuccess) rc = SDR_ERR_DEVICE;
+    sdr::free_bufs({&d1, &d2});
     if (rc == SDR_ERR_DEVICE) return sdr::set_error(rc, "map copy failed");
     return rc;
 }
@@ -311,22 +311,19 @@ int sdr_rectifier_create(const double K_left[9], const double* dist_left, int nd
                          const double* P2, int p_cols, int W, int H, int device,
                          sdr_rectifier** out) {
     if (!out || W <= 0 || H <= 0) return sdr::set_error(SDR_ERR_ARG, "bad rectifier arguments");
-    if (W > 32767 || H > 32767) return sdr::set_error(SDR_ERR_SIZE, "CV_16SC2 maps need size < 32768");
     sdr::MapParams ml, mr;
     int rc;
+    if ((rc = check_map_size(W, H))) return rc;
     if ((rc = make_map_params(K_left, dist_left, ndist_left, R1, P1, p_cols, &ml))) return rc;
     if ((rc = make_map_params(K_right, dist_right, ndist_right, R2, P2, p_cols, &mr))) return rc;
-    SDR_HIP(hipSetDevice(device));
     sdr_rectifier* h = new sdr_rectifier();
-    h->device = device;
     h->W = W;
     h->H = H;
     const size_t px = (size_t)W * H;
-    if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) {
+    if ((rc = h->open(device))) {
         delete h;
-        return sdr::set_error(SDR_ERR_DEVICE, "hipStreamCreate failed");
+        return rc;
     }
-    h->stream = h->own_stream;
     for (int e = 0; e < 2 && !rc; e++) {
         if ((rc = sdr::ensure(h->map1[e], px * 4))) break;
         if ((rc = sdr::ensure(h->map2[e], px * 2))) break;
@@ -345,26 +342,20 @@ int sdr_rectifier_create(const double K_left[9], const double* dist_left, int nd
 
 int sdr_rectifier_destroy(sdr_rectifier* h) {
     if (!h) return SDR_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (int e = 0; e < 2; e++) {
-        if (h->map1[e].p) (void)hipFree(h->map1[e].p);
-        if (h->map2[e].p) (void)hipFree(h->map2[e].p);
-    }
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    h->close();
     delete h;
     return SDR_OK;
 }
 
 int sdr_rectifier_set_stream(sdr_rectifier* h, void* stream) {
     if (!h) return sdr::set_error(SDR_ERR_ARG, "null handle");
-    h->stream = (hipStream_t)stream;  // NULL = the HIP null (legacy default) stream
+    h->bind(stream);
     return SDR_OK;
 }
 
 int sdr_rectifier_reset_stream(sdr_rectifier* h) {
     if (!h) return sdr::set_error(SDR_ERR_ARG, "null handle");
-    h->stream = h->own_stream;
+    h->unbind();
     return SDR_OK;
 }
 

@@ -1,8 +1,8 @@
 // sdr_ruler_shared.hpp -- what the ruler's units (sdr_ruler.hip, sdr_plane.hip, sdr_relief.hip,
 // sdr_footprint.hip) share: on the device the disparity loads, the canonical NaN, the wave
 // reductions, a rectangle's range test and the ruler's sample; on the host (ruler_host) the argument
-// guards, the Q and disparity-type plumbing of a launch, the per-thread persistent buffers and the
-// host-pointer path of the calls that take plane records and queries.  The region rule of the
+// guards, the Q and disparity-type plumbing of a launch, the per-thread persistent buffers (held in
+// sdr_host.hpp's ThreadState) and the host-pointer path of the calls that take plane records and queries.  The region rule of the
 // relief and the footprint is in sdr_region.hpp.
 #pragma once
 #include <string>
@@ -180,39 +180,18 @@ inline int check_plane_maps(const void* disp, int disp_type, size_t stride, size
     return SDR_OK;
 }
 
-// per-thread persistent device buffers and stream of the host-pointer calls (per current device)
-struct HostState {
-    int device = -1;
-    hipStream_t st = nullptr;
+// the device buffers of the host-pointer calls, kept by the thread (sdr_host.hpp ThreadState)
+struct HostBufs {
     sdr::Buf map, conf, segs, out, prof, planes;
-    void release() {
-        if (device < 0) return;
-        (void)hipSetDevice(device);
-        if (st) (void)hipStreamSynchronize(st);
-        for (sdr::Buf* b : {&map, &conf, &segs, &out, &prof, &planes}) {
-            if (b->p) (void)hipFree(b->p);
-            *b = sdr::Buf();
-        }
-        if (st) (void)hipStreamDestroy(st);
-        st = nullptr;
-        device = -1;
-    }
-    ~HostState() { release(); }
+    void release() { sdr::free_bufs({&map, &conf, &segs, &out, &prof, &planes}); }
 };
+using HostState = sdr::ThreadState<HostBufs>;
 
 // one state a thread, whichever unit asks (an inline function's local is one object)
 inline int host_state(HostState** out) {
     static thread_local HostState S;
-    int dev = 0;
-    SDR_HIP(hipGetDevice(&dev));
-    if (S.device != dev) {
-        S.release();
-        SDR_HIP(hipSetDevice(dev));
-        SDR_HIP(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
-        S.device = dev;
-    }
     *out = &S;
-    return SDR_OK;
+    return S.acquire();
 }
 
 // rows of `row_bytes` of F frames of H rows into a dense device buffer

@@ -1,20 +1,18 @@
 // sdr_wls_entries.hip -- the WLS / FGS filter's handle and C ABI (include/sdr/sdr.h).  Every call
 // is planned once (sdr_wls_plan.hpp: the one refusal rule, the path, the scratch layout) and then
-// runs its stages (sdr_wls.hip) over (handle, plan): reserve, front end, solver, back end.
-// No kernels.
+// runs its stages (sdr_wls.hip) over (handle, plan): reserve, front end, solver, back end.  The
+// handle's device, stream binding and buffer release are sdr_host.hpp's Bound.  No kernels.
 #include "sdr_host.hpp"
 #include "sdr_wls_plan.hpp"
 
 #include <cmath>
 #include <vector>
 
-struct sdr_wls {
+struct sdr_wls : sdr::Bound {
     sdr_wls_params p{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t own_stream = nullptr;
-    sdr::Buf rdisc, conf, A, B, Ac, Bc, ChT, Cv, lut, out, hbuf, coef;
+    sdr::Buf rdisc, A, B, Ac, Bc, ChT, Cv, lut, hbuf, coef;
     double lut_sigma = -1.0;
+    sdr_wls() : Bound{&rdisc, &A, &B, &Ac, &Bc, &ChT, &Cv, &lut, &hbuf, &coef} {}
 };
 
 namespace {
@@ -130,27 +128,19 @@ void sdr_wls_params_for_sgbm(sdr_sgbm_params* m, sdr_wls_params* p) {
 int sdr_wls_create(const sdr_wls_params* p, int device, sdr_wls** out) {
     if (!p || !out) return sdr::set_error(SDR_ERR_ARG, "null argument");
     if (const sdr::WlsRefusal no = sdr::wls_refusal(*p); no.rc) return refuse(no);
-    SDR_HIP(hipSetDevice(device));
     sdr_wls* h = new sdr_wls();
     h->p = *p;
-    h->device = device;
-    if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) {
+    if (const int rc = h->open(device)) {
         delete h;
-        return sdr::set_error(SDR_ERR_DEVICE, "hipStreamCreate failed");
+        return rc;
     }
-    h->stream = h->own_stream;
     *out = h;
     return SDR_OK;
 }
 
 int sdr_wls_destroy(sdr_wls* h) {
     if (!h) return SDR_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (sdr::Buf* b : {&h->rdisc, &h->conf, &h->A, &h->B, &h->Ac, &h->Bc, &h->ChT, &h->Cv,
-                        &h->lut, &h->out, &h->hbuf, &h->coef})
-        if (b->p) (void)hipFree(b->p);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    h->close();
     delete h;
     return SDR_OK;
 }
@@ -170,13 +160,13 @@ int sdr_wls_get_params(const sdr_wls* h, sdr_wls_params* p) {
 
 int sdr_wls_set_stream(sdr_wls* h, void* stream) {
     if (!h) return sdr::set_error(SDR_ERR_ARG, "null handle");
-    h->stream = (hipStream_t)stream;  // NULL = the HIP null (legacy default) stream
+    h->bind(stream);
     return SDR_OK;
 }
 
 int sdr_wls_reset_stream(sdr_wls* h) {
     if (!h) return sdr::set_error(SDR_ERR_ARG, "null handle");
-    h->stream = h->own_stream;
+    h->unbind();
     return SDR_OK;
 }
 
