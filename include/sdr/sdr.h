@@ -974,6 +974,109 @@ int sdr_plane_footprint(const void* disp, int disp_type, size_t stride, size_t f
                         const sdr_plane* planes, int P, const sdr_relief_query* queries, int K,
                         sdr_footprint* out);
 
+/* ---- the objects of a region: connected sets of pixels in a band of heights above a plane ----
+ * sdr_find_objects* labels the connected sets of a rectangle's pixels that stand in a band of
+ * heights above a plane record and whose disparities change by at most max_diff from pixel to
+ * pixel, and reports the largest of them, largest first, as records and as a label map in the form
+ * sdr_plane_relief* and sdr_plane_footprint* take: a floor from sdr_find_planes*, one label a thing
+ * standing on it from here, each thing's height, length and width from those two.  Every output is
+ * a count, an integer sum, an extreme or a set membership: none depends on the grid shape or on the
+ * order the workgroups finish in, and every one is defined to the bit.
+ *   - Query: one sdr_relief_query under the relief's rules (rectangle xs, xe, ys, ye, rw, rh, area;
+ *     the label mask against the INPUT label map).  SDR_OBJECTS_OUT_OF_RANGE (a frame or corner
+ *     outside, a label outside -1..255, a label >= 0 without an input label map): nothing read,
+ *     every count (area too) 0.  Otherwise SDR_OBJECTS_NO_PLANE (`plane` outside [0, P) or a record
+ *     without SDR_PLANE_OK): the maps are not read, area is the region's, the other counts 0.
+ *     label = 255 with sdr_find_planes*' map selects the pixels no plane claimed.
+ *   - Member: a pixel that passes the relief's steps 1 to 5 (n_masked and n_valid count as there),
+ *     then h_lo <= hf && hf <= h_hi (float comparisons, the footprint's band).  n counts the members.
+ *   - Adjacent: with connectivity 4 two pixels of the rectangle that share an edge, with 8 two that
+ *     share an edge or a corner.  Joined: two adjacent members p, q with fabsf(d_p - d_q) <= max_diff,
+ *     d the float disparity as step 2 reads it (int16: (float)v * 0.0625f): one float subtraction,
+ *     one comparison.
+ *   - Component: a class of the transitive closure of "joined"; its root is the smallest index
+ *     v * rw + u (u = x - xs, v = y - ys) of its pixels.  n_components counts the components.
+ *   - Kept: the components of at least min_pixels pixels, n_kept of them, ordered by size
+ *     descending, ties to the lower root.  count = min(n_kept, max_objects); n_kept > max_objects
+ *     sets SDR_OBJECTS_TRUNCATED beside the other flag; n_kept == 0 gives SDR_OBJECTS_EMPTY (the
+ *     counts as found), else SDR_OBJECTS_VALID.  largest_dropped is the size of the largest
+ *     component that is not kept (smaller than min_pixels), 0 with none.
+ *   - Object k < count: n and root; x0, y0, x1, y1 the bounding box in image coordinates, inclusive;
+ *     sum_x, sum_y the sums of the image x and y; sum256 the sum of the relief's
+ *     e = llrint((double)hf * 256.0); h_min, h_max the extreme hf; flags SDR_OBJECT_VALID, and
+ *     SDR_OBJECT_CUT iff the box touches the rectangle's border (x0 == xs || x1 == xe || y0 == ys ||
+ *     y1 == ye).  Records k >= count (all max_objects are written): n 0, root and the box -1, the
+ *     sums 0, the floats the canonical NaN, flags 0.
+ *   - Scan record: flags, the counts, and the query's frame, plane and label in every case.
+ *   - Labels: uint8 [height][width] of the query's frame, 255 everywhere but on the pixels of object
+ *     k < count, which hold k: the count of label k is objects[k].n.  A refused query writes 255
+ *     everywhere. */
+typedef struct sdr_object_params { /* 64 bytes */
+    float min_disp, conf_min;      /* the ruler's validity rule */
+    float h_lo, h_hi;              /* members have h_lo <= hf <= h_hi; not NaN, h_lo <= h_hi */
+    float max_diff;                /* joined: |d_p - d_q| <= max_diff (px); finite, >= 0 */
+    int32_t connectivity;          /* 4 or 8 */
+    int32_t min_pixels;            /* a kept component's least size, 1..2^24 */
+    int32_t max_objects;           /* records (and labels) written, 1..64 */
+    int32_t reserved[8];           /* 0 */
+} sdr_object_params;
+
+enum {
+    SDR_OBJECTS_VALID = 1, SDR_OBJECTS_OUT_OF_RANGE = 2, SDR_OBJECTS_NO_PLANE = 4,
+    SDR_OBJECTS_EMPTY = 8, SDR_OBJECTS_TRUNCATED = 16
+};
+enum { SDR_OBJECT_VALID = 1, SDR_OBJECT_CUT = 2 };
+
+typedef struct sdr_object { /* 64 bytes */
+    int32_t n;                     /* pixels */
+    int32_t root;                  /* the smallest v * rw + u of its pixels; -1: no object */
+    int32_t x0, y0, x1, y1;        /* the bounding box, image coordinates, inclusive */
+    int64_t sum_x, sum_y;          /* sums of the image x and y: the centroid is sum / n */
+    int64_t sum256;                /* the sum of llrint(hf * 256): the mean height is sum256 / n / 256 */
+    float h_min, h_max;
+    uint32_t flags;                /* SDR_OBJECT_* */
+    int32_t reserved;              /* 0 */
+} sdr_object;
+
+typedef struct sdr_object_scan { /* 64 bytes */
+    uint32_t flags;                /* SDR_OBJECTS_* */
+    int32_t area, n_masked, n_valid, n;
+    int32_t n_components, n_kept, count, largest_dropped;
+    int32_t frame, plane, label;   /* the query's */
+    int32_t reserved[4];           /* 0 */
+} sdr_object_scan;
+
+/* {-1.0f, 0.0f, 10.0f, 1048576.0f, 1.0f, 8, 64, 16, {0, ...}} */
+void sdr_object_params_default(sdr_object_params* p);
+/* One query (d_query: one sdr_relief_query on the device) on device maps against the P records of
+ * d_planes (arguments as sdr_plane_relief_device; d_labels_in, nullable, is its dense uint8
+ * [F][H][W] label map), asynchronous on `stream`: a fixed sequence of launches with no host
+ * synchronisation and no workgroup that waits on another (32 x 32 tiles labelled in LDS, tile
+ * borders merged by a lock-free min-root union-find, sizes, a ranking of the kept roots, one sweep
+ * for the records and the labels).  Writes the max_objects records of d_objects, *d_scan and, when
+ * it is not NULL, the width * height labels of d_labels_out, which must not be d_labels_in.  The
+ * query is device memory, so the stream-ordered scratch is sized for the frame: 8 bytes a pixel of
+ * width * height (a parent and a size), 8 * max_objects + 16 bytes for every 2048 pixels (candidate
+ * keys, counts), 16 bytes a 32 x 32 tile (counts) and 3616 bytes of state: 1.87 MB for 640 x 360
+ * at max_objects 16.  The host refuses, before any device call and with SDR_ERR_ARG: what
+ * sdr_plane_relief_device refuses of the maps and planes, a null d_query, d_objects or d_scan,
+ * d_labels_out == d_labels_in (not NULL), h_lo or h_hi NaN or h_lo > h_hi, a max_diff that is not
+ * finite or negative, a connectivity other than 4 or 8, min_pixels outside 1..2^24, max_objects
+ * outside 1..64, a non-zero reserved field of the parameters. */
+int sdr_find_objects_device(const void* d_disp, int disp_type, size_t stride, size_t frame_stride,
+                            int width, int height, int nframes, const float* d_conf,
+                            const uint8_t* d_labels_in, const double Q[16],
+                            const sdr_object_params* params, const sdr_plane* d_planes, int P,
+                            const sdr_relief_query* d_query, sdr_object* d_objects,
+                            sdr_object_scan* d_scan, uint8_t* d_labels_out, void* stream);
+/* Host-pointer version (synchronous; per-thread persistent device buffers as sdr_fit_planes);
+ * labels_out (nullable): width * height bytes. */
+int sdr_find_objects(const void* disp, int disp_type, size_t stride, size_t frame_stride, int width,
+                     int height, int nframes, const float* conf, const uint8_t* labels_in,
+                     const double Q[16], const sdr_object_params* params, const sdr_plane* planes,
+                     int P, const sdr_relief_query* query, sdr_object* objects,
+                     sdr_object_scan* scan, uint8_t* labels_out);
+
 /* Bytes of device scratch the handle holds for the given frame shape (for capacity planning);
  * 0 when compute would refuse the shape or parameters.  sdr_sgbm_scratch_bytes is the CV_8UC1
  * figure, sdr_sgbm_scratch_bytes_cn takes the channel count (1 or 3: colour input holds three

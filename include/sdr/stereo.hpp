@@ -448,6 +448,8 @@ using Plane = sdr_plane;
 using PlaneDistance = struct sdr_plane_distance;  // the C record shares its name with a function
 using Relief = sdr_relief;
 using Footprint = sdr_footprint;
+using Object = sdr_object;
+using ObjectScan = sdr_object_scan;
 struct Point {
     int x = 0, y = 0;
 };
@@ -666,6 +668,52 @@ public:
                         int label = -1, const Mat* conf = nullptr) const {
         return footprint(disparity, std::vector<Plane>{plane},
                          {sdr_relief_query{0, a.x, a.y, b.x, b.y, 0, label, 0}}, labels, conf)[0];
+    }
+    // The objects of the rectangle a..b standing on `plane` (sdr.h, "the objects of a region"): the
+    // connected sets of pixels whose height above the plane lies in h_lo..h_hi and whose disparities
+    // step by at most max_diff between neighbours (connectivity 4 or 8), those of at least min_pixels
+    // pixels, the largest first, at most max_objects.  objects: the objects found; scan: the counts and
+    // flags; labels (with_labels): CV_8UC1 of the map's size, k on object k's pixels and 255 elsewhere,
+    // which relief and footprint take with label k.  labels_in / label: the mask of relief
+    struct Objects {
+        std::vector<Object> objects;
+        ObjectScan scan;
+        Mat labels;
+    };
+    Objects find_objects(const Mat& disparity, const std::vector<Plane>& planes, const sdr_relief_query& region,
+                         const Mat* labels_in = nullptr, const Mat* conf = nullptr, float h_lo = 10.0f,
+                         float h_hi = 1048576.0f, float max_diff = 1.0f, int connectivity = 8, int min_pixels = 64,
+                         int max_objects = 16, bool with_labels = true) const {
+        check_maps(disparity, conf, "find_objects");
+        check_labels(disparity, labels_in);
+        const size_t es = elem_size(disparity.type);
+        sdr_object_params op;
+        sdr_object_params_default(&op);
+        op.min_disp = p_.min_disp;
+        op.conf_min = p_.conf_min;
+        op.h_lo = h_lo;
+        op.h_hi = h_hi;
+        op.max_diff = max_diff;
+        op.connectivity = connectivity;
+        op.min_pixels = min_pixels;
+        op.max_objects = max_objects;
+        Objects out;
+        out.objects.resize(max_objects > 0 && max_objects <= 64 ? (size_t)max_objects : 1);
+        std::memset(&out.scan, 0, sizeof out.scan);
+        if (with_labels) out.labels = Mat::pageable(disparity.rows, disparity.cols, CV_8UC1);
+        check(sdr_find_objects(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16,
+                               disparity.step / es, disparity.step / es * disparity.rows, disparity.cols,
+                               disparity.rows, 1, conf ? conf->ptr<float>(0) : nullptr,
+                               labels_in ? labels_in->data : nullptr, q_, &op, planes.empty() ? nullptr : planes.data(),
+                               (int)planes.size(), &region, out.objects.data(), &out.scan,
+                               with_labels ? out.labels.data : nullptr));
+        out.objects.resize((size_t)out.scan.count);
+        return out;
+    }
+    Objects find_objects(const Mat& disparity, const Plane& plane, Point a, Point b, const Mat* labels_in = nullptr,
+                         int label = -1, const Mat* conf = nullptr) const {
+        return find_objects(disparity, std::vector<Plane>{plane}, sdr_relief_query{0, a.x, a.y, b.x, b.y, 0, label, 0},
+                            labels_in, conf);
     }
 
 private:

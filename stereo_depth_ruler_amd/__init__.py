@@ -21,6 +21,8 @@ from .ruler import (  # noqa: F401
     RELIEF_DTYPE, RELIEF_EMPTY, RELIEF_NO_PLANE, RELIEF_OUT_OF_RANGE, RELIEF_VALID, as_relief_queries,
     FOOTPRINT_CLIPPED, FOOTPRINT_DTYPE, FOOTPRINT_EMPTY, FOOTPRINT_NO_PLANE, FOOTPRINT_OUT_OF_RANGE, FOOTPRINT_VALID,
     footprint_length_width,
+    OBJECT_CUT, OBJECT_DTYPE, OBJECT_SCAN_DTYPE, OBJECT_VALID, OBJECTS_EMPTY, OBJECTS_NO_PLANE, OBJECTS_OUT_OF_RANGE,
+    OBJECTS_TRUNCATED, OBJECTS_VALID,
 )
 from .stereo_disparity import StereoDisparity  # noqa: F401
 
@@ -37,4 +39,6 @@ __all__ = [
     "RELIEF_DTYPE", "RELIEF_VALID", "RELIEF_OUT_OF_RANGE", "RELIEF_NO_PLANE", "RELIEF_EMPTY", "as_relief_queries",
     "FOOTPRINT_DTYPE", "FOOTPRINT_VALID", "FOOTPRINT_OUT_OF_RANGE", "FOOTPRINT_NO_PLANE", "FOOTPRINT_EMPTY",
     "FOOTPRINT_CLIPPED", "footprint_length_width",
+    "OBJECT_DTYPE", "OBJECT_SCAN_DTYPE", "OBJECT_VALID", "OBJECT_CUT", "OBJECTS_VALID", "OBJECTS_OUT_OF_RANGE",
+    "OBJECTS_NO_PLANE", "OBJECTS_EMPTY", "OBJECTS_TRUNCATED",
 ]

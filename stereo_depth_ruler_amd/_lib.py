@@ -180,6 +180,29 @@ class Footprint(ctypes.Structure):
                [("flags", ctypes.c_uint32), ("reserved", ctypes.c_int32 * 4)]
 
 
+class ObjectParams(ctypes.Structure):
+    """sdr_object_params (64 bytes)."""
+    _fields_ = [(n, ctypes.c_float) for n in ("min_disp", "conf_min", "h_lo", "h_hi", "max_diff")] + \
+               [(n, ctypes.c_int32) for n in ("connectivity", "min_pixels", "max_objects")] + \
+               [("reserved", ctypes.c_int32 * 8)]
+
+
+class Object(ctypes.Structure):
+    """sdr_object (64 bytes)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("n", "root", "x0", "y0", "x1", "y1")] + \
+               [(n, ctypes.c_int64) for n in ("sum_x", "sum_y", "sum256")] + \
+               [("h_min", ctypes.c_float), ("h_max", ctypes.c_float), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_int32)]
+
+
+class ObjectScan(ctypes.Structure):
+    """sdr_object_scan (64 bytes)."""
+    _fields_ = [("flags", ctypes.c_uint32)] + \
+               [(n, ctypes.c_int32) for n in ("area", "n_masked", "n_valid", "n", "n_components", "n_kept", "count",
+                                              "largest_dropped", "frame", "plane", "label")] + \
+               [("reserved", ctypes.c_int32 * 4)]
+
+
 _lib = None
 _path = LIB_PATH
 
@@ -327,6 +350,11 @@ SIGNATURES = [
                                         _c.POINTER(FootprintParams), _vp, _i, _vp, _i, _vp, _vp]),
     ("sdr_plane_footprint", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _vp, _c.POINTER(_c.c_double),
                                  _c.POINTER(FootprintParams), _vp, _i, _vp, _i, _vp]),
+    ("sdr_object_params_default", None, [_c.POINTER(ObjectParams)]),
+    ("sdr_find_objects_device", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _vp, _c.POINTER(_c.c_double),
+                                     _c.POINTER(ObjectParams), _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("sdr_find_objects", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _vp, _c.POINTER(_c.c_double),
+                              _c.POINTER(ObjectParams), _vp, _i, _vp, _vp, _vp, _vp]),
     ("sdr_build_id", _c.c_char_p, []),
     ("sdr_last_error", _c.c_char_p, []),
     ("sdr_abi_version", _i, []),

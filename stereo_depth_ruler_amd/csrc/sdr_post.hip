@@ -4,6 +4,7 @@
 #include "sdr_device.hpp"
 #include "sdr_internal.hpp"
 #include "sdr_sgbm_rules.hpp"
+#include "sdr_unionfind.hpp"
 
 #include <float.h>
 
@@ -170,64 +171,9 @@ void launch_mask_cols(const int16_t* src, int16_t* dst, const Geometry& g, int F
 // Pixel-level work is streaming; global finds and atomics scale with the number of tile
 // components, not with the pixels of a large component.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ int uf_load(const int* P, int i) {
-    return __hip_atomic_load(&P[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// find with path halving; parents only ever decrease (union links the larger root under the
-// smaller), so a no-return atomicMin keeps concurrent unions intact
-__device__ __forceinline__ int uf_find(int* P, int x) {
-    int p = uf_load(P, x);
-    while (p != x) {
-        const int gp = uf_load(P, p);
-        if (gp != p) atomicMin(&P[x], gp);
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-__device__ __forceinline__ void uf_unite(int* P, int a, int b) {
-    for (;;) {
-        a = uf_find(P, a);
-        b = uf_find(P, b);
-        if (a == b) return;
-        if (a < b) {
-            int old = atomicMin(&P[b], a);
-            if (old == b) return;
-            b = old;
-        } else {
-            int old = atomicMin(&P[a], b);
-            if (old == a) return;
-            a = old;
-        }
-    }
-}
+// uf_load / uf_find / uf_unite and lds_find / lds_unite: sdr_unionfind.hpp
 
 constexpr int kCT = 32;
-
-__device__ __forceinline__ int lds_find(int* lab, int x) {
-    int p = __hip_atomic_load(&lab[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    while (p != x) {
-        x = p;
-        p = __hip_atomic_load(&lab[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    return x;
-}
-__device__ __forceinline__ void lds_unite(int* lab, int a, int b) {
-    for (;;) {
-        a = lds_find(lab, a);
-        b = lds_find(lab, b);
-        if (a == b) return;
-        if (a < b) {
-            int old = atomicMin(&lab[b], a);
-            if (old == b) return;
-            b = old;
-        } else {
-            int old = atomicMin(&lab[a], b);
-            if (old == a) return;
-            a = old;
-        }
-    }
-}
 
 __device__ __forceinline__ bool joined(int a, int b, int newVal, int maxDiff) {
     return a != newVal && b != newVal && abs(a - b) <= maxDiff;

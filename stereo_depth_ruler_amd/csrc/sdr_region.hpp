@@ -1,8 +1,8 @@
 // sdr_region.hpp -- the region rule, once: which queries run, which pixels of a rectangle count and
 // how high each lies above the query's plane (steps 1 to 5 of "the relief of a region" in
 // include/sdr/sdr.h, which the footprint takes over), and the frame of a sweep that gives a
-// workgroup a slice of a rectangle's row-major order.  The relief, the footprint, the plane fit and
-// the plane search are written on it.
+// workgroup a slice of a rectangle's row-major order.  The relief, the footprint, the objects, the
+// plane fit and the plane search are written on it.
 #pragma once
 #include "sdr_ruler_shared.hpp"
 
@@ -40,10 +40,12 @@ __device__ __forceinline__ bool query_plane(const sdr_plane* __restrict__ planes
     return true;
 }
 
-// one refusal for the three record types
-static_assert(SDR_RELIEF_OUT_OF_RANGE == 2 && SDR_FOOTPRINT_OUT_OF_RANGE == 2 && SDR_PDIST_OUT_OF_RANGE == 2,
+// one refusal for the four record types
+static_assert(SDR_RELIEF_OUT_OF_RANGE == 2 && SDR_FOOTPRINT_OUT_OF_RANGE == 2 && SDR_PDIST_OUT_OF_RANGE == 2 &&
+                  SDR_OBJECTS_OUT_OF_RANGE == 2,
               "the OUT_OF_RANGE flags share a value");
-static_assert(SDR_RELIEF_NO_PLANE == 4 && SDR_FOOTPRINT_NO_PLANE == 4 && SDR_PDIST_NO_PLANE == 4,
+static_assert(SDR_RELIEF_NO_PLANE == 4 && SDR_FOOTPRINT_NO_PLANE == 4 && SDR_PDIST_NO_PLANE == 4 &&
+                  SDR_OBJECTS_NO_PLANE == 4,
               "the NO_PLANE flags share a value");
 constexpr uint32_t kRegionOutOfRange = 2, kRegionNoPlane = 4;
 

@@ -1,5 +1,5 @@
 // sdr_ruler_shared.hpp -- what the ruler's units (sdr_ruler.hip, sdr_plane.hip, sdr_relief.hip,
-// sdr_footprint.hip) share: on the device the disparity loads, the canonical NaN, the wave
+// sdr_footprint.hip, sdr_objects.hip) share: on the device the disparity loads, the canonical NaN, the wave
 // reductions, a rectangle's range test and the ruler's sample; on the host (ruler_host) the argument
 // guards, the Q and disparity-type plumbing of a launch, the per-thread persistent buffers (held in
 // sdr_host.hpp's ThreadState) and the host-pointer path of the calls that take plane records and queries.  The region rule of the

@@ -170,6 +170,17 @@ class LiveLoop:
         return self.ruler.footprint_device(self.disp, planes, regions, labels=labels, conf=self.conf, cell=cell,
                                            grid=grid, support=support, h_range=h_range, stream=stream)
 
+    def find_objects(self, planes, region, stream, labels=None, h_range=(10.0, 1048576.0), max_diff: float = 1.0,
+                     connectivity: int = 8, min_pixels: int = 64, max_objects: int = 16, labels_out=True):
+        """Ruler.find_objects_device on the same frames, chained like relief(): the (objects, scan,
+        labels) tensors, no synchronise in between; the labels feed relief() and footprint()."""
+        if self.ruler is None:
+            raise RuntimeError("LiveLoop was built without ruler=")
+        return self.ruler.find_objects_device(self.disp, planes, region, labels=labels, conf=self.conf,
+                                              h_range=h_range, max_diff=max_diff, connectivity=connectivity,
+                                              min_pixels=min_pixels, max_objects=max_objects, stream=stream,
+                                              labels_out=labels_out)
+
     def close(self):
         for o in (self.left, self.right, self.wls, self.display):
             if o is not None:

@@ -24,6 +24,12 @@ the definition is in include/sdr/sdr.h).
   of the plane, stray cells dropped by a 3 x 3 support rule, and the minimum-area bounding rectangle
   over 90 whole-degree directions (csrc/sdr_footprint.hip): the length and width of a box on a
   table at whatever angle it lies, with its four 3-D corners.
+* ``Ruler.find_objects(disparity, planes, region, labels=None)`` finds the things that stand on a
+  plane: the connected sets of a rectangle's pixels in a band of heights above a plane record whose
+  disparities step by at most ``max_diff`` from pixel to pixel (tiles labelled in LDS, a lock-free
+  union-find across tile borders, csrc/sdr_objects.hip), the largest first, as records (pixels,
+  bounding box, centroid sums, height sums and extremes) and as a label map that ``relief`` and
+  ``footprint`` take: a mug, a ball or a box seen corner-on gets a label though it is no plane.
 * ``Ruler.find_planes(disparity, region=None)`` finds a region's dominant planes without a prior (a
   box on a table in front of a wall): rounds of seeded three-point hypotheses scored in exact
   integer arithmetic on the pixels no earlier plane has claimed, the winner refitted as
@@ -44,8 +50,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (DISP_F32, DISP_S16, FootprintParams, PlaneParams, PlaneSearchParams, ReliefParams, RulerParams,
-                   SDRError, check, lib)
+from ._lib import (DISP_F32, DISP_S16, FootprintParams, ObjectParams, PlaneParams, PlaneSearchParams, ReliefParams,
+                   RulerParams, SDRError, check, lib)
 from .sgbm import _Q, _is_cuda, torch
 
 MEASUREMENT_DTYPE = np.dtype([
@@ -98,6 +104,20 @@ FOOTPRINT_DTYPE = np.dtype([
     ("label", "<i4"), ("flags", "<u4"), ("reserved", "<i4", (4,))])
 assert FOOTPRINT_DTYPE.itemsize == 256
 FOOTPRINT_VALID, FOOTPRINT_OUT_OF_RANGE, FOOTPRINT_NO_PLANE, FOOTPRINT_EMPTY, FOOTPRINT_CLIPPED = 1, 2, 4, 8, 16
+
+
+# sdr_object, sdr_object_scan and their flags (SDR_OBJECT_*, SDR_OBJECTS_*)
+OBJECT_DTYPE = np.dtype([
+    ("n", "<i4"), ("root", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("sum_x", "<i8"),
+    ("sum_y", "<i8"), ("sum256", "<i8"), ("h_min", "<f4"), ("h_max", "<f4"), ("flags", "<u4"), ("reserved", "<i4")])
+assert OBJECT_DTYPE.itemsize == 64
+OBJECT_SCAN_DTYPE = np.dtype([
+    ("flags", "<u4"), ("area", "<i4"), ("n_masked", "<i4"), ("n_valid", "<i4"), ("n", "<i4"),
+    ("n_components", "<i4"), ("n_kept", "<i4"), ("count", "<i4"), ("largest_dropped", "<i4"), ("frame", "<i4"),
+    ("plane", "<i4"), ("label", "<i4"), ("reserved", "<i4", (4,))])
+assert OBJECT_SCAN_DTYPE.itemsize == 64
+OBJECTS_VALID, OBJECTS_OUT_OF_RANGE, OBJECTS_NO_PLANE, OBJECTS_EMPTY, OBJECTS_TRUNCATED = 1, 2, 4, 8, 16
+OBJECT_VALID, OBJECT_CUT = 1, 2
 
 
 def footprint_length_width(records):
@@ -699,6 +719,110 @@ class Ruler:
         return self._plane_queries_device("footprint_device", lib().sdr_plane_footprint_device,
                                           lambda: self._footprint_params(cell, grid, support, h_range), 256, disparity,
                                           planes, regions, _REGIONS, conf, stream, labels)
+
+    # ---- the objects of a region (sdr.h, "the objects of a region") ----
+    def _object_params(self, h_range, max_diff, connectivity, min_pixels, max_objects) -> ObjectParams:
+        lo, hi = float(h_range[0]), float(h_range[1])
+        max_diff = float(max_diff)
+        if np.isnan(lo) or np.isnan(hi) or lo > hi:
+            raise SDRError(-1, "h_range must be (lo, hi) with lo <= hi, neither NaN")
+        if not (np.isfinite(max_diff) and max_diff >= 0.0):
+            raise SDRError(-1, "max_diff must be finite and >= 0")
+        if connectivity not in (4, 8):
+            raise SDRError(-1, "connectivity must be 4 or 8")
+        if int(min_pixels) != min_pixels or not 1 <= min_pixels <= 2 ** 24:
+            raise SDRError(-1, "min_pixels must be an integer in 1..2^24")
+        if int(max_objects) != max_objects or not 1 <= max_objects <= 64:
+            raise SDRError(-1, "max_objects must be an integer in 1..64")
+        return ObjectParams(self.min_disp, self.conf_min, lo, hi, max_diff, int(connectivity), int(min_pixels),
+                            int(max_objects))
+
+    @staticmethod
+    def _object_query(region) -> np.ndarray:
+        q = as_relief_queries(region)
+        if q.shape[0] != 1:
+            raise SDRError(-1, "find_objects takes one region")
+        return q
+
+    def find_objects(self, disparity, planes, region, labels=None, conf=None, h_range=(10.0, 1048576.0),
+                     max_diff: float = 1.0, connectivity: int = 8, min_pixels: int = 64, max_objects: int = 16,
+                     labels_out: bool = True):
+        """The things standing on a plane: the connected sets of one rectangle's pixels whose height
+        above a plane record lies in h_range (Q's units) and whose disparities step by at most
+        max_diff (px) between neighbours (connectivity 4 or 8), those of at least min_pixels pixels,
+        the largest first, at most max_objects.  planes and labels: as relief() takes them; region:
+        one row {frame, x0, y0, x1, y1, plane, label} (5 or 6 entries: plane 0, label -1); label 255
+        with find_planes' map takes the pixels no plane claimed.  Returns (objects, scan, labels):
+        the objects found as an OBJECT_DTYPE array, one OBJECT_SCAN_DTYPE record (counts, flags),
+        and with labels_out the (H, W) uint8 map of the region's frame, k on object k's pixels and
+        255 elsewhere, which relief() and footprint() take with label k (None without)."""
+        if _is_cuda(disparity):
+            rec, scan, lab = self.find_objects_device(disparity, planes, region, labels, conf, h_range, max_diff,
+                                                      connectivity, min_pixels, max_objects, labels_out=labels_out)
+            sc = scan.cpu().numpy().reshape(-1).view(OBJECT_SCAN_DTYPE)[0]
+            out = rec.cpu().numpy().reshape(-1).view(OBJECT_DTYPE)[:int(sc["count"])].copy()
+            return out, sc, (lab.cpu().numpy() if lab is not None else None)
+        p = self._object_params(h_range, max_diff, connectivity, min_pixels, max_objects)
+        pl = _host_planes(planes)
+        d, c, a = self._host_maps(disparity, conf)
+        F, H, W = d.shape
+        lab_in = _host_labels(labels, d.shape)
+        q = self._object_query(region)
+        P = pl.shape[0]
+        rec = np.zeros(int(max_objects), OBJECT_DTYPE)
+        scan = np.zeros(1, OBJECT_SCAN_DTYPE)
+        lab = np.empty((H, W), np.uint8) if labels_out else None
+        with _on_device(self.device):
+            rc = lib().sdr_find_objects(*a, lab_in.ctypes.data if lab_in is not None else None, _Q(self.Q),
+                                        ctypes.byref(p), pl.ctypes.data if P else None, P, q.ctypes.data,
+                                        rec.ctypes.data, scan.ctypes.data, lab.ctypes.data if lab is not None else None)
+        check(rc)
+        return rec[:int(scan["count"][0])].copy(), scan[0], lab
+
+    def find_objects_device(self, disparity, planes, region, labels=None, conf=None, h_range=(10.0, 1048576.0),
+                            max_diff: float = 1.0, connectivity: int = 8, min_pixels: int = 64, max_objects: int = 16,
+                            stream=None, labels_out=None):
+        """Enqueues the labelling on `stream` (default: the current stream) without synchronising and
+        returns (objects uint8 (max_objects, 64), scan uint8 (64,), labels uint8 (H, W) or None):
+        view the host copies as OBJECT_DTYPE and OBJECT_SCAN_DTYPE; the labels tensor feeds
+        relief_device and footprint_device unchanged.  planes and labels: as find_planes_device
+        returns them or host arrays; region: a host row or a CUDA int32 (1, 8); labels_out: True for
+        a new label tensor, a contiguous CUDA uint8 (H, W) tensor to write into (not `labels`), or
+        None / False for no label map."""
+        if not _is_cuda(disparity):
+            raise SDRError(-5, "find_objects_device expects a CUDA float32 or int16 tensor")
+        p = self._object_params(h_range, max_diff, connectivity, min_pixels, max_objects)
+        dev = disparity.device
+        s = stream if stream is not None else torch.cuda.current_stream(dev.index)
+        with torch.cuda.stream(s):
+            d, conf, a = self._device_maps(disparity, conf)
+            F, H, W = d.shape
+            pl = _device_planes(planes, dev)
+            P = pl.numel() // 128 if pl is not None else 0
+            lab_in = _device_labels(labels, d, dev)
+            if _is_cuda(region):
+                if region.dtype != torch.int32 or tuple(region.shape) != (1, 8):
+                    raise SDRError(-5, "a device region must be an int32 tensor (1, 8)")
+                q = region.contiguous()
+            else:
+                q = self._upload_segments(self._object_query(region), dev, s)
+            lab = None
+            if labels_out is True:
+                lab = torch.empty((H, W), dtype=torch.uint8, device=dev)
+            elif labels_out is not None and labels_out is not False:
+                if (not _is_cuda(labels_out) or labels_out.dtype != torch.uint8 or not labels_out.is_contiguous()
+                        or tuple(labels_out.shape) != (H, W)):
+                    raise SDRError(-5, "labels_out must be a contiguous CUDA uint8 tensor (H, W)")
+                if lab_in is not None and labels_out.data_ptr() == lab_in.data_ptr():
+                    raise SDRError(-1, "labels_out must not be the input label map")
+                lab = labels_out
+            rec = torch.empty((int(max_objects), 64), dtype=torch.uint8, device=dev)
+            scan = torch.empty((64,), dtype=torch.uint8, device=dev)
+            check(lib().sdr_find_objects_device(
+                *a, lab_in.data_ptr() if lab_in is not None else None, _Q(self.Q), ctypes.byref(p),
+                pl.data_ptr() if P else None, P, q.data_ptr(), rec.data_ptr(), scan.data_ptr(),
+                lab.data_ptr() if lab is not None else None, ctypes.c_void_p(s.cuda_stream)))
+        return rec, scan, lab
 
     # ---- XYZ-map mode (the reference's measurement) ----
     def measure_xyz(self, depth_map, segments):
