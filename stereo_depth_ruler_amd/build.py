@@ -18,7 +18,7 @@ SOURCES = ["sdr_cost.hip", "sdr_cost3.hip", "sdr_cost3k2.hip", "sdr_cost_generic
            "sdr_cloud.hip", "sdr_display.hip", "sdr_ruler.hip", "sdr_plane.hip", "sdr_relief.hip", "sdr_footprint.hip", "sdr_objects.hip",
            "sdr_plan.hip", "sdr_staging.hip", "sdr_handle.hip", "sdr_engine.hip", "sdr_entries.hip"]
 HEADERS = ["sdr_device.hpp", "sdr_internal.hpp", "sdr_sgbm_rules.hpp", "sdr_cost_kernel.hpp", "sdr_fgs.hpp", "sdr_wls_plan.hpp", "sdr_ruler_shared.hpp", "sdr_region.hpp", "sdr_unionfind.hpp",
-           "sdr_host.hpp", "sdr_plan.hpp", "sdr_staging.hpp", "sdr_handle.hpp", "sdr_voxel_plan.hpp"]
+           "sdr_host.hpp", "sdr_plan.hpp", "sdr_staging.hpp", "sdr_handle.hpp", "sdr_voxel_plan.hpp", "sdr_layout.hpp"]
 ARCH = os.environ.get("SDR_OFFLOAD_ARCH", "gfx950")
 
 

@@ -73,13 +73,14 @@ int sdr_reproject_device(const float* d_disp, int W, int H, size_t disp_stride, 
     int rc = check_dims(W, H, disp_stride, F);
     if (rc) return rc;
     if (xyz_stride < (size_t)W * 3) return set_error(SDR_ERR_ARG, "xyz_stride < 3*width");
-    int* mins = nullptr;
-    if (handle_missing) SDR_HIP(sdr::scratch_alloc((void**)&mins, F * sizeof(int), (hipStream_t)stream));
-    sdr::launch_reproject_f32(d_disp, W, H, disp_stride, disp_stride * H, Q, handle_missing, mins,
-                              d_xyz, xyz_stride, xyz_stride * H, F, (hipStream_t)stream);
-    if (mins) SDR_HIP(sdr::scratch_free(mins, (hipStream_t)stream));
-    SDR_HIP(hipGetLastError());
-    return SDR_OK;
+    // the frames' minima, when missing values are handled
+    sdr::ScratchLayout lay;
+    const auto s_mins = lay.take<int>((size_t)F);
+    sdr::Scratch sc((hipStream_t)stream);
+    if (handle_missing && (rc = sc.open(lay))) return rc;
+    sdr::launch_reproject_f32(d_disp, W, H, disp_stride, disp_stride * H, Q, handle_missing,
+                              handle_missing ? sc.at(s_mins) : nullptr, d_xyz, xyz_stride, xyz_stride * H, F, sc.st);
+    return sc.finish();
 }
 
 int sdr_filter_speckles_device(int16_t* d_img, int W, int H, int F, int newVal, int maxSpeckleSize,
@@ -91,13 +92,13 @@ int sdr_filter_speckles_device(int16_t* d_img, int W, int H, int F, int newVal, 
     if (maxSpeckleSize <= 0) return SDR_OK;  // OpenCV: nothing to do
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)F * W * H;
-    int* scratch = nullptr;
-    SDR_HIP(sdr::scratch_alloc((void**)&scratch, n * 8, st));
-    sdr::launch_speckle(d_img, d_img, W, H, F, newVal, maxSpeckleSize, maxDiff, scratch, scratch + n,
+    sdr::ScratchLayout lay;
+    const auto s_labels = lay.take<int>(n), s_sizes = lay.take<int>(n);
+    sdr::Scratch sc(st);
+    if ((rc = sc.open(lay))) return rc;
+    sdr::launch_speckle(d_img, d_img, W, H, F, newVal, maxSpeckleSize, maxDiff, sc.at(s_labels), sc.at(s_sizes),
                         nullptr, st);
-    SDR_HIP(sdr::scratch_free(scratch, st));
-    SDR_HIP(hipGetLastError());
-    return SDR_OK;
+    return sc.finish();
 }
 
 int sdr_disp16_reproject_device(const int16_t* d_disp, int W, int H, size_t disp_stride,
@@ -109,17 +110,20 @@ int sdr_disp16_reproject_device(const int16_t* d_disp, int W, int H, size_t disp
     if (xyz_stride < (size_t)W * 3) return set_error(SDR_ERR_ARG, "xyz_stride < 3*width");
     if (handle_missing && disp_stride != (size_t)W)
         return set_error(SDR_ERR_ARG, "handle_missing needs a dense disparity (disp_stride == width)");
-    int* mins = nullptr;
     hipStream_t st = (hipStream_t)stream;
+    // the frames' partial minima, when missing values are handled
+    sdr::ScratchLayout lay;
+    const auto s_mins = lay.take<int>((size_t)F * sdr::kMinSlots);
+    sdr::Scratch sc(st);
+    int* mins = nullptr;
     if (handle_missing) {
-        SDR_HIP(sdr::scratch_alloc((void**)&mins, F * sdr::kMinSlots * sizeof(int), st));
+        if ((rc = sc.open(lay))) return rc;
+        mins = sc.at(s_mins);
         sdr::launch_min_s16(d_disp, (size_t)W * H, disp_stride * H, F, mins, st);
     }
     sdr::launch_reproject_s16(d_disp, W, H, disp_stride, disp_stride * H, Q, handle_missing, mins,
                               d_xyz, xyz_stride, xyz_stride * H, F, st);
-    if (mins) SDR_HIP(sdr::scratch_free(mins, st));
-    SDR_HIP(hipGetLastError());
-    return SDR_OK;
+    return sc.finish();
 }
 
 int sdr_reproject(const float* disp, int W, int H, size_t disp_stride, const double Q[16],

@@ -468,11 +468,13 @@ int sdr_plane_footprint_device(const void* d_disp, int disp_type, size_t stride,
     const size_t G = (size_t)FP.grid, gbytes = G * G * sizeof(unsigned);  // 1 KiB .. 4 MiB a query
     const int KB = std::min(K, std::min(kFootBatch, (int)(kFootGridBytes / gbytes)));  // >= 1
     // scratch of a batch: {grids, states}
-    const size_t o_st = (size_t)KB * gbytes;
-    char* sc = nullptr;
-    SDR_HIP(sdr::scratch_alloc((void**)&sc, o_st + (size_t)KB * sizeof(sdr::FootState), st));
-    unsigned* grids = (unsigned*)sc;
-    sdr::FootState* states = (sdr::FootState*)(sc + o_st);
+    sdr::ScratchLayout lay;
+    const auto s_grids = lay.take<unsigned>((size_t)KB * G * G);
+    const auto s_states = lay.take<sdr::FootState>((size_t)KB);
+    sdr::Scratch sc(st);
+    if ((rc = sc.open(lay))) return rc;
+    unsigned* grids = sc.at(s_grids);
+    sdr::FootState* states = sc.at(s_states);
     const unsigned slices = sdr::region_slices(W, H);
     const unsigned tiles = (unsigned)((G + sdr::kFootTile - 1) / sdr::kFootTile);
     const dim3 block(sdr::kRegionThreads), small(sdr::kFootFinish);
@@ -493,11 +495,7 @@ int sdr_plane_footprint_device(const void* d_disp, int disp_type, size_t stride,
     };
     for (int k0 = 0; k0 < K && e == hipSuccess; k0 += KB)
         with_disp(disp_type, d_disp, [&](auto* disp) { batch(disp, k0, std::min(K - k0, KB)); });
-    const hipError_t le = hipGetLastError();
-    SDR_HIP(sdr::scratch_free(sc, st));
-    SDR_HIP(e);
-    SDR_HIP(le);
-    return SDR_OK;
+    return sc.finish(e);
 }
 
 int sdr_plane_footprint(const void* disp, int disp_type, size_t stride, size_t frame_stride, int W, int H, int F,

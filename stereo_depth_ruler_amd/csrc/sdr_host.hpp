@@ -1,8 +1,10 @@
 // sdr_host.hpp -- what the host side of every unit shares: the one hipError_t check, the size
 // checks of the C entries, the release of device buffers, the device and stream binding of the
-// auxiliary handles (Bound) and the per-thread state of the host-pointer entries (ThreadState).
+// auxiliary handles (Bound), the per-thread state of the host-pointer entries (ThreadState) and the
+// owner of a device call's stream-ordered scratch (Scratch).
 #pragma once
 #include "sdr_internal.hpp"
+#include "sdr_layout.hpp"
 
 #include <initializer_list>
 #include <string>
@@ -97,6 +99,42 @@ struct ThreadState : Res {
         SDR_HIP(hipSetDevice(dev));
         SDR_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         device = dev;
+        return SDR_OK;
+    }
+};
+
+// The stream-ordered scratch of one call on one stream: one block of the library's pool
+// (scratch_alloc), laid out by a ScratchLayout.  An entry opens it, resolves its slices, launches and
+// returns finish(); a return before that frees the block in the destructor.
+struct Scratch {
+    hipStream_t st;
+    char* base = nullptr;  // non-null: a block is open
+    explicit Scratch(hipStream_t s) : st(s) {}
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() {
+        if (base) (void)scratch_free(base, st);
+    }
+
+    int open(const ScratchLayout& layout) {
+        SDR_HIP(scratch_alloc((void**)&base, layout.total, st));
+        // the layout aligns offsets; the slices are aligned only on a base that is
+        if ((uintptr_t)base % kSliceAlign) return set_error(SDR_ERR_DEVICE, "scratch block is not 256-byte aligned");
+        return SDR_OK;
+    }
+    template <typename T>
+    T* at(const Slice<T>& s) const {
+        return (T*)(base + s.off);
+    }
+    // after the call's last launch: frees the block (if one is open) on the stream and reports the
+    // first failure of the free, of `e` (an earlier HIP call of the entry) and of the launches
+    int finish(hipError_t e = hipSuccess) {
+        const hipError_t le = hipGetLastError();
+        char* block = base;
+        base = nullptr;
+        if (block) SDR_HIP(scratch_free(block, st));
+        SDR_HIP(e);
+        SDR_HIP(le);
         return SDR_OK;
     }
 };

@@ -661,18 +661,21 @@ int sdr_find_objects_device(const void* d_disp, int disp_type, size_t stride, si
                      (unsigned)((H + sdr::kObjTile - 1) / sdr::kObjTile));
     // scratch, sized for the frame (the query is device memory): {parents, sizes, candidates, the
     // tiles' counts, the slices' counts, state}
-    const size_t o_sz = px * sizeof(int), o_cand = 2 * o_sz;
-    const size_t o_tiles = o_cand + (size_t)slices * OP.max_objects * sizeof(unsigned long long);
-    const size_t o_slices = o_tiles + (size_t)tiles.x * tiles.y * sizeof(sdr::ObjTileCount);
-    const size_t o_state = o_slices + (size_t)slices * sizeof(sdr::ObjSliceCount);
-    char* sc = nullptr;
-    SDR_HIP(sdr::scratch_alloc((void**)&sc, o_state + sizeof(sdr::ObjState), st));
-    int* Pa = (int*)sc;
-    int* Sz = (int*)(sc + o_sz);
-    unsigned long long* cand = (unsigned long long*)(sc + o_cand);
-    sdr::ObjTileCount* tcnt = (sdr::ObjTileCount*)(sc + o_tiles);
-    sdr::ObjSliceCount* scnt = (sdr::ObjSliceCount*)(sc + o_slices);
-    sdr::ObjState* S = (sdr::ObjState*)(sc + o_state);
+    sdr::ScratchLayout lay;
+    const auto s_parents = lay.take<int>(px);
+    const auto s_sizes = lay.take<int>(px);
+    const auto s_cand = lay.take<unsigned long long>((size_t)slices * OP.max_objects);
+    const auto s_tiles = lay.take<sdr::ObjTileCount>((size_t)tiles.x * tiles.y);
+    const auto s_slices = lay.take<sdr::ObjSliceCount>((size_t)slices);
+    const auto s_state = lay.take<sdr::ObjState>(1);
+    sdr::Scratch sc(st);
+    if (int rc = sc.open(lay)) return rc;
+    int* Pa = sc.at(s_parents);
+    int* Sz = sc.at(s_sizes);
+    unsigned long long* cand = sc.at(s_cand);
+    sdr::ObjTileCount* tcnt = sc.at(s_tiles);
+    sdr::ObjSliceCount* scnt = sc.at(s_slices);
+    sdr::ObjState* S = sc.at(s_state);
     const int has_labels = d_labels_in ? 1 : 0;
     // border pixels of the largest rectangle: ((W - 1) / 32) * H + ((H - 1) / 32) * W <= 2^20
     const size_t borders = (size_t)((W - 1) / sdr::kObjTile) * H + (size_t)((H - 1) / sdr::kObjTile) * W;
@@ -700,11 +703,7 @@ int sdr_find_objects_device(const void* d_disp, int disp_type, size_t stride, si
             hipLaunchKernelGGL(sdr::k_obj_finish, dim3(1), dim3(sdr::kObjMax), 0, st, W, H, F, has_labels, OP, d_planes,
                                P, d_query, (const sdr::ObjState*)S, d_objects, d_scan);
         });
-    const hipError_t le = hipGetLastError();
-    SDR_HIP(sdr::scratch_free(sc, st));
-    SDR_HIP(e);
-    SDR_HIP(le);
-    return SDR_OK;
+    return sc.finish(e);
 }
 
 int sdr_find_objects(const void* disp, int disp_type, size_t stride, size_t frame_stride, int W, int H, int F,
@@ -714,27 +713,19 @@ int sdr_find_objects(const void* disp, int disp_type, size_t stride, size_t fram
     int rc = check_objects_call(disp, disp_type, stride, frame_stride, W, H, F, labels_in, Q, params, planes, P, query,
                                 objects, scan, labels_out);
     if (rc) return rc;
-    HostState* S = nullptr;
-    if ((rc = host_state(&S))) return rc;
-    const size_t px = (size_t)W * H;
-    // the thread's record buffer: {objects, scan, labels}
-    const size_t o_scan = (size_t)params->max_objects * sizeof(sdr_object), o_lab = o_scan + sizeof(sdr_object_scan);
-    if ((rc = upload_maps(S, disp, disp_type, stride, frame_stride, W, H, F, conf)) ||
-        (rc = upload_queries(S, planes, P, query, sizeof(sdr_relief_query), labels_in, (size_t)F * px,
-                             o_lab + (labels_out ? px : 0))))
-        return rc;
-    char* out = (char*)S->out.p;
-    rc = sdr_find_objects_device(S->map.p, disp_type, (size_t)W, px, W, H, F, conf ? (const float*)S->conf.p : nullptr,
-                                 labels_in ? (const uint8_t*)S->prof.p : nullptr, Q, params,
-                                 P ? (const sdr_plane*)S->planes.p : nullptr, P, (const sdr_relief_query*)S->segs.p,
-                                 (sdr_object*)out, (sdr_object_scan*)(out + o_scan),
-                                 labels_out ? (uint8_t*)(out + o_lab) : nullptr, S->st);
-    if (rc) return rc;
-    SDR_HIP(hipMemcpyAsync(objects, out, o_scan, hipMemcpyDeviceToHost, S->st));
-    SDR_HIP(hipMemcpyAsync(scan, out + o_scan, sizeof(sdr_object_scan), hipMemcpyDeviceToHost, S->st));
-    if (labels_out) SDR_HIP(hipMemcpyAsync(labels_out, out + o_lab, px, hipMemcpyDeviceToHost, S->st));
-    SDR_HIP(hipStreamSynchronize(S->st));
-    return SDR_OK;
+    HostCall c;
+    const HostCall::Maps m = c.maps(disp, disp_type, stride, frame_stride, W, H, F, conf);
+    const sdr_plane* d_planes = c.input(c.S->planes, planes, (size_t)P);
+    const sdr_relief_query* d_query = c.input(c.S->rows, query, 1);
+    const uint8_t* d_labels_in = c.input(c.S->labels, labels_in, (size_t)F * W * H);
+    const auto s_objects = c.output(objects, (size_t)params->max_objects);
+    const auto s_scan = c.output(scan, 1);
+    const auto s_labels = c.output(labels_out, labels_out ? (size_t)W * H : 0);
+    if ((rc = c.ready())) return rc;
+    rc = sdr_find_objects_device(m.disp, disp_type, m.stride, m.fstride, W, H, F, m.conf, d_labels_in, Q, params,
+                                 d_planes, P, d_query, c.at(s_objects), c.at(s_scan),
+                                 labels_out ? c.at(s_labels) : nullptr, c.stream());
+    return rc ? rc : c.finish();
 }
 
 }  // extern "C"

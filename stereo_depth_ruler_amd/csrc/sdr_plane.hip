@@ -733,10 +733,13 @@ int sdr_fit_planes_device(const void* d_disp, int disp_type, size_t stride, size
     hipStream_t st = (hipStream_t)stream;
     const sdr::Q16 q = make_q16(Q);
     const int sweeps = params->iterations + 2;
-    const size_t per = (size_t)sweeps * sdr::kPlaneSlots, bytes = (size_t)K * per * sizeof(long long);
-    long long* acc = nullptr;
-    SDR_HIP(sdr::scratch_alloc((void**)&acc, bytes, st));
-    SDR_HIP(hipMemsetAsync(acc, 0, bytes, st));
+    const size_t per = (size_t)sweeps * sdr::kPlaneSlots;
+    sdr::ScratchLayout lay;
+    const auto s_acc = lay.take<long long>((size_t)K * per);
+    sdr::Scratch sc(st);
+    if ((rc = sc.open(lay))) return rc;
+    long long* acc = sc.at(s_acc);
+    SDR_HIP(hipMemsetAsync(acc, 0, s_acc.bytes(), st));
     const unsigned slices = sdr::region_slices(W, H);
     for (int s = 0; s < sweeps; s++)
         for (int k0 = 0; k0 < K; k0 += 65535) {  // the grid's y extent
@@ -749,10 +752,7 @@ int sdr_fit_planes_device(const void* d_disp, int disp_type, size_t stride, size
         }
     hipLaunchKernelGGL(sdr::k_plane_finish, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, st, d_regions, K, W, H,
                        F, q, *params, (const long long*)acc, d_planes);
-    const hipError_t le = hipGetLastError();
-    SDR_HIP(sdr::scratch_free(acc, st));
-    SDR_HIP(le);
-    return SDR_OK;
+    return sc.finish();
 }
 
 void sdr_plane_search_params_default(sdr_plane_search_params* p) {
@@ -781,22 +781,21 @@ int sdr_find_planes_device(const void* d_disp, int disp_type, size_t stride, siz
     // scratch: {state, the rounds' accumulators, the rounds' scores} zeroed, the hypotheses of one
     // round (every round writes all M before it reads them), the claim map when the caller has none
     const size_t per = (size_t)(P.iterations + 2) * sdr::kPlaneSlots;
-    const size_t o_acc = 64, o_sc = o_acc + (size_t)NP * per * sizeof(long long);
-    const size_t o_hyp = (o_sc + (size_t)NP * M * sizeof(unsigned) + 63) & ~(size_t)63;
-    const size_t o_lab = o_hyp + (size_t)M * sizeof(sdr::SearchHyp);
-    char* sc = nullptr;
-    SDR_HIP(sdr::scratch_alloc((void**)&sc, o_lab + (d_labels ? 0 : px), st));
-    sdr::SearchState* state = (sdr::SearchState*)sc;
-    long long* acc = (long long*)(sc + o_acc);
-    unsigned* scores = (unsigned*)(sc + o_sc);
-    sdr::SearchHyp* hyp = (sdr::SearchHyp*)(sc + o_hyp);
-    uint8_t* labels = d_labels ? d_labels : (uint8_t*)(sc + o_lab);
-    hipError_t e = hipMemsetAsync(sc, 0, o_hyp, st);
-    if (e == hipSuccess) e = hipMemsetAsync(labels, 0xff, px, st);
-    if (e != hipSuccess) {
-        (void)sdr::scratch_free(sc, st);
-        SDR_HIP(e);
-    }
+    sdr::ScratchLayout lay;
+    const auto s_state = lay.take<sdr::SearchState>(1);
+    const auto s_acc = lay.take<long long>((size_t)NP * per);
+    const auto s_scores = lay.take<unsigned>((size_t)NP * M);
+    const auto s_hyp = lay.take<sdr::SearchHyp>((size_t)M);
+    const auto s_lab = lay.take<uint8_t>(d_labels ? 0 : px);
+    sdr::Scratch sc(st);
+    if ((rc = sc.open(lay))) return rc;
+    sdr::SearchState* state = sc.at(s_state);
+    long long* acc = sc.at(s_acc);
+    unsigned* scores = sc.at(s_scores);
+    sdr::SearchHyp* hyp = sc.at(s_hyp);
+    uint8_t* labels = d_labels ? d_labels : sc.at(s_lab);
+    SDR_HIP(hipMemsetAsync(state, 0, s_hyp.off, st));  // everything ahead of the hypotheses
+    SDR_HIP(hipMemsetAsync(labels, 0xff, px, st));
     const unsigned slices = sdr::region_slices(W, H);
     const dim3 sgrid(slices), sblock(sdr::kRegionThreads), dgrid((unsigned)((M + 63) / 64)), one(1), wave(64);
     const dim3 cgrid(slices, (unsigned)((M + sdr::kSearchChunk - 1) / sdr::kSearchChunk));
@@ -822,10 +821,7 @@ int sdr_find_planes_device(const void* d_disp, int disp_type, size_t stride, siz
                            P, d_region, labels, r, (const sdr::SearchState*)state, (const long long*)A);
     };
     for (int r = 0; r < NP; r++) with_disp(disp_type, d_disp, [&](auto* disp) { round(disp, r); });
-    const hipError_t le = hipGetLastError();
-    SDR_HIP(sdr::scratch_free(sc, st));
-    SDR_HIP(le);
-    return SDR_OK;
+    return sc.finish();
 }
 
 int sdr_find_planes(const void* disp, int disp_type, size_t stride, size_t frame_stride, int W, int H, int F,
@@ -836,27 +832,19 @@ int sdr_find_planes(const void* disp, int disp_type, size_t stride, size_t frame
     if (rc) return rc;
     if (!count) return rfail(SDR_ERR_ARG, "null argument");
     if ((rc = check_search_params(params))) return rc;
-    HostState* S = nullptr;
-    if ((rc = host_state(&S))) return rc;
-    const int NP = params->max_planes;
-    const size_t px = (size_t)W * H, rbytes = (size_t)NP * sizeof(sdr_plane_search_round);
-    // out: {count, padding to 16 bytes, the rounds}; prof: the labels
-    if ((rc = upload_maps(S, disp, disp_type, stride, frame_stride, W, H, F, conf)) ||
-        (rc = sdr::ensure(S->segs, sizeof(sdr_segment))) || (rc = sdr::ensure(S->planes, (size_t)NP * sizeof(sdr_plane))) ||
-        (rc = sdr::ensure(S->out, 16 + rbytes)) || (rc = sdr::ensure(S->prof, labels ? px : 0)))
-        return rc;
-    SDR_HIP(hipMemcpyAsync(S->segs.p, region, sizeof(sdr_segment), hipMemcpyHostToDevice, S->st));
-    rc = sdr_find_planes_device(S->map.p, disp_type, (size_t)W, px, W, H, F, conf ? (const float*)S->conf.p : nullptr, Q,
-                                params, (const sdr_segment*)S->segs.p, (sdr_plane*)S->planes.p, (int32_t*)S->out.p,
-                                (sdr_plane_search_round*)((char*)S->out.p + 16), labels ? (uint8_t*)S->prof.p : nullptr,
-                                S->st);
-    if (rc) return rc;
-    SDR_HIP(hipMemcpyAsync(planes, S->planes.p, (size_t)NP * sizeof(sdr_plane), hipMemcpyDeviceToHost, S->st));
-    SDR_HIP(hipMemcpyAsync(count, S->out.p, sizeof(int32_t), hipMemcpyDeviceToHost, S->st));
-    if (rounds) SDR_HIP(hipMemcpyAsync(rounds, (char*)S->out.p + 16, rbytes, hipMemcpyDeviceToHost, S->st));
-    if (labels) SDR_HIP(hipMemcpyAsync(labels, S->prof.p, px, hipMemcpyDeviceToHost, S->st));
-    SDR_HIP(hipStreamSynchronize(S->st));
-    return SDR_OK;
+    const size_t NP = (size_t)params->max_planes;
+    HostCall c;
+    const HostCall::Maps m = c.maps(disp, disp_type, stride, frame_stride, W, H, F, conf);
+    const sdr_segment* d_region = c.input(c.S->rows, region, 1);
+    const auto s_planes = c.output(planes, NP);
+    const auto s_count = c.output(count, 1);
+    const auto s_rounds = c.output(rounds, NP);  // the device form always writes them
+    const auto s_labels = c.output(labels, labels ? (size_t)W * H : 0);
+    if ((rc = c.ready())) return rc;
+    rc = sdr_find_planes_device(m.disp, disp_type, m.stride, m.fstride, W, H, F, m.conf, Q, params, d_region,
+                                c.at(s_planes), c.at(s_count), c.at(s_rounds), labels ? c.at(s_labels) : nullptr,
+                                c.stream());
+    return rc ? rc : c.finish();
 }
 
 int sdr_plane_distance_device(const void* d_disp, int disp_type, size_t stride, size_t frame_stride, int W,
@@ -884,20 +872,14 @@ int sdr_fit_planes(const void* disp, int disp_type, size_t stride, size_t frame_
     int rc = check_plane_maps(disp, disp_type, stride, frame_stride, W, H, F, Q, params, regions, K, planes);
     if (rc || (rc = check_plane_params(params))) return rc;
     if (K == 0) return SDR_OK;
-    HostState* S = nullptr;
-    if ((rc = host_state(&S))) return rc;
-    if ((rc = upload_maps(S, disp, disp_type, stride, frame_stride, W, H, F, conf)) ||
-        (rc = sdr::ensure(S->segs, (size_t)K * sizeof(sdr_segment))) ||
-        (rc = sdr::ensure(S->planes, (size_t)K * sizeof(sdr_plane))))
-        return rc;
-    SDR_HIP(hipMemcpyAsync(S->segs.p, regions, (size_t)K * sizeof(sdr_segment), hipMemcpyHostToDevice, S->st));
-    rc = sdr_fit_planes_device(S->map.p, disp_type, (size_t)W, (size_t)W * H, W, H, F,
-                               conf ? (const float*)S->conf.p : nullptr, Q, params, (const sdr_segment*)S->segs.p,
-                               K, (sdr_plane*)S->planes.p, S->st);
-    if (rc) return rc;
-    SDR_HIP(hipMemcpyAsync(planes, S->planes.p, (size_t)K * sizeof(sdr_plane), hipMemcpyDeviceToHost, S->st));
-    SDR_HIP(hipStreamSynchronize(S->st));
-    return SDR_OK;
+    HostCall c;
+    const HostCall::Maps m = c.maps(disp, disp_type, stride, frame_stride, W, H, F, conf);
+    const sdr_segment* d_regions = c.input(c.S->rows, regions, (size_t)K);
+    const auto s_planes = c.output(planes, (size_t)K);
+    if ((rc = c.ready())) return rc;
+    rc = sdr_fit_planes_device(m.disp, disp_type, m.stride, m.fstride, W, H, F, m.conf, Q, params, d_regions, K,
+                               c.at(s_planes), c.stream());
+    return rc ? rc : c.finish();
 }
 
 int sdr_plane_distance(const void* disp, int disp_type, size_t stride, size_t frame_stride, int W, int H,
@@ -907,20 +889,15 @@ int sdr_plane_distance(const void* disp, int disp_type, size_t stride, size_t fr
     int rc = check_plane_maps(disp, disp_type, stride, frame_stride, W, H, F, Q, params, queries, K, out);
     if (rc || (rc = check_query_params(params, planes, P))) return rc;
     if (K == 0) return SDR_OK;
-    HostState* S = nullptr;
-    if ((rc = host_state(&S))) return rc;
-    if ((rc = upload_maps(S, disp, disp_type, stride, frame_stride, W, H, F, conf)) ||
-        (rc = upload_queries(S, planes, P, queries, (size_t)K * sizeof(sdr_plane_query), nullptr, 0,
-                             (size_t)K * sizeof(struct sdr_plane_distance))))
-        return rc;
-    rc = sdr_plane_distance_device(S->map.p, disp_type, (size_t)W, (size_t)W * H, W, H, F,
-                                   conf ? (const float*)S->conf.p : nullptr, Q, params,
-                                   P ? (const sdr_plane*)S->planes.p : nullptr, P,
-                                   (const sdr_plane_query*)S->segs.p, K, (struct sdr_plane_distance*)S->out.p, S->st);
-    if (rc) return rc;
-    SDR_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(struct sdr_plane_distance), hipMemcpyDeviceToHost, S->st));
-    SDR_HIP(hipStreamSynchronize(S->st));
-    return SDR_OK;
+    HostCall c;
+    const HostCall::Maps m = c.maps(disp, disp_type, stride, frame_stride, W, H, F, conf);
+    const sdr_plane* d_planes = c.input(c.S->planes, planes, (size_t)P);
+    const sdr_plane_query* d_queries = c.input(c.S->rows, queries, (size_t)K);
+    const auto s_out = c.output(out, (size_t)K);
+    if ((rc = c.ready())) return rc;
+    rc = sdr_plane_distance_device(m.disp, disp_type, m.stride, m.fstride, W, H, F, m.conf, Q, params, d_planes, P,
+                                   d_queries, K, c.at(s_out), c.stream());
+    return rc ? rc : c.finish();
 }
 
 }  // extern "C"

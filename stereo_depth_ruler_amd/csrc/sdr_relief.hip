@@ -372,16 +372,17 @@ int sdr_plane_relief_device(const void* d_disp, int disp_type, size_t stride, si
     const sdr_relief_params RP = *params;
     const int nq = RP.nq, KB = std::min(K, kReliefBatch);
     // scratch of a batch, all of it zeroed: {states, pass 1's histograms, pass 2's, pass 3's}
-    const size_t o_h1 = (size_t)KB * sizeof(sdr::ReliefState);
-    const size_t o_h2 = o_h1 + (size_t)KB * sdr::kReliefBins * sizeof(unsigned);
-    const size_t o_h3 = o_h2 + (size_t)KB * nq * sdr::kReliefBins * sizeof(unsigned);
-    const size_t bytes = o_h3 + (size_t)KB * nq * sdr::kReliefLastBins * sizeof(unsigned);
-    char* sc = nullptr;
-    SDR_HIP(sdr::scratch_alloc((void**)&sc, bytes, st));
-    sdr::ReliefState* states = (sdr::ReliefState*)sc;
-    unsigned* h1 = (unsigned*)(sc + o_h1);
-    unsigned* h2 = (unsigned*)(sc + o_h2);
-    unsigned* h3 = (unsigned*)(sc + o_h3);
+    sdr::ScratchLayout lay;
+    const auto s_states = lay.take<sdr::ReliefState>((size_t)KB);
+    const auto s_h1 = lay.take<unsigned>((size_t)KB * sdr::kReliefBins);
+    const auto s_h2 = lay.take<unsigned>((size_t)KB * nq * sdr::kReliefBins);
+    const auto s_h3 = lay.take<unsigned>((size_t)KB * nq * sdr::kReliefLastBins);
+    sdr::Scratch sc(st);
+    if ((rc = sc.open(lay))) return rc;
+    sdr::ReliefState* states = sc.at(s_states);
+    unsigned* h1 = sc.at(s_h1);
+    unsigned* h2 = sc.at(s_h2);
+    unsigned* h3 = sc.at(s_h3);
     const unsigned slices = sdr::region_slices(W, H);
     const dim3 block(sdr::kRegionThreads);
     const size_t lds1 = sdr::kReliefBins * sizeof(unsigned), lds2 = (size_t)nq * lds1,
@@ -391,7 +392,7 @@ int sdr_plane_relief_device(const void* d_disp, int disp_type, size_t stride, si
         using T = disp_elem_t<decltype(disp)>;
         const sdr_relief_query* qs = d_queries + k0;
         const dim3 sgrid(slices, (unsigned)kb), pgrid((unsigned)kb);
-        if ((e = hipMemsetAsync(sc, 0, bytes, st)) != hipSuccess) return;
+        if ((e = hipMemsetAsync(sc.base, 0, lay.total, st)) != hipSuccess) return;
         hipLaunchKernelGGL((sdr::k_relief_sweep<T, 1>), sgrid, block, lds1, st, disp, stride, frame_stride, W, H, F,
                            d_conf, d_labels, q, RP, d_planes, P, qs, states, h1);
         hipLaunchKernelGGL(sdr::k_relief_pick1, pgrid, block, 0, st, W, H, F, d_labels ? 1 : 0, RP, d_planes, P, qs,
@@ -408,11 +409,7 @@ int sdr_plane_relief_device(const void* d_disp, int disp_type, size_t stride, si
     };
     for (int k0 = 0; k0 < K && e == hipSuccess; k0 += KB)
         with_disp(disp_type, d_disp, [&](auto* disp) { batch(disp, k0, std::min(K - k0, KB)); });
-    const hipError_t le = hipGetLastError();
-    SDR_HIP(sdr::scratch_free(sc, st));
-    SDR_HIP(e);
-    SDR_HIP(le);
-    return SDR_OK;
+    return sc.finish(e);
 }
 
 int sdr_plane_relief(const void* disp, int disp_type, size_t stride, size_t frame_stride, int W, int H, int F,

@@ -365,26 +365,17 @@ int sdr_measure_disp(const void* disp, int disp_type, size_t stride, size_t fram
     int rc = check_disp_args(disp, disp_type, stride, frame_stride, W, H, F, Q, params, segs, K, out, profile);
     if (rc) return rc;
     if (K == 0) return SDR_OK;
-    HostState* S = nullptr;
-    if ((rc = host_state(&S))) return rc;
-    const size_t px = (size_t)W * H;
-    const bool prof = profile && params->profile && params->profile_cap > 0;
-    const size_t prof_bytes = prof ? (size_t)K * params->profile_cap * 16 : 0;
-    if ((rc = sdr::ensure(S->segs, (size_t)K * sizeof(sdr_segment))) ||
-        (rc = sdr::ensure(S->out, (size_t)K * sizeof(sdr_measurement))) || (rc = sdr::ensure(S->prof, prof_bytes)) ||
-        (rc = upload_maps(S, disp, disp_type, stride, frame_stride, W, H, F, conf)))
-        return rc;
-    SDR_HIP(hipMemcpyAsync(S->segs.p, segs, (size_t)K * sizeof(sdr_segment), hipMemcpyHostToDevice, S->st));
-    // rows the kernel leaves untouched keep the caller's values
-    if (prof) SDR_HIP(hipMemcpyAsync(S->prof.p, profile, prof_bytes, hipMemcpyHostToDevice, S->st));
-    rc = sdr_measure_disp_device(S->map.p, disp_type, (size_t)W, px, W, H, F, conf ? (const float*)S->conf.p : nullptr,
-                                 Q, params, (const sdr_segment*)S->segs.p, K, (sdr_measurement*)S->out.p,
-                                 prof ? (float*)S->prof.p : nullptr, S->st);
-    if (rc) return rc;
-    SDR_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(sdr_measurement), hipMemcpyDeviceToHost, S->st));
-    if (prof) SDR_HIP(hipMemcpyAsync(profile, S->prof.p, prof_bytes, hipMemcpyDeviceToHost, S->st));
-    SDR_HIP(hipStreamSynchronize(S->st));
-    return SDR_OK;
+    HostCall c;
+    const HostCall::Maps m = c.maps(disp, disp_type, stride, frame_stride, W, H, F, conf);
+    const sdr_segment* d_segs = c.input(c.S->rows, segs, (size_t)K);
+    // the profile rows, 4 floats each, when the call writes any
+    const bool prof = params->profile && params->profile_cap > 0;
+    float* d_profile = c.inout(c.S->prof, prof ? profile : nullptr, (size_t)K * params->profile_cap * 4);
+    const auto s_out = c.output(out, (size_t)K);
+    if ((rc = c.ready())) return rc;
+    rc = sdr_measure_disp_device(m.disp, disp_type, m.stride, m.fstride, W, H, F, m.conf, Q, params, d_segs, K,
+                                 c.at(s_out), d_profile, c.stream());
+    return rc ? rc : c.finish();
 }
 
 int sdr_measure_xyz(const float* xyz, size_t xyz_stride, size_t xyz_frame_stride, int W, int H, int F,
@@ -392,20 +383,13 @@ int sdr_measure_xyz(const float* xyz, size_t xyz_stride, size_t xyz_frame_stride
     int rc = check_xyz_args(xyz, xyz_stride, xyz_frame_stride, W, H, F, segs, K, out);
     if (rc) return rc;
     if (K == 0) return SDR_OK;
-    HostState* S = nullptr;
-    if ((rc = host_state(&S))) return rc;
-    const size_t px = (size_t)W * H;
-    if ((rc = sdr::ensure(S->map, (size_t)F * px * 12)) || (rc = sdr::ensure(S->segs, (size_t)K * sizeof(sdr_segment))) ||
-        (rc = sdr::ensure(S->out, (size_t)K * sizeof(sdr_measurement))))
-        return rc;
-    if ((rc = upload_rows(S->map.p, xyz, (size_t)W * 12, xyz_stride * 4, xyz_frame_stride * 4, H, F, S->st))) return rc;
-    SDR_HIP(hipMemcpyAsync(S->segs.p, segs, (size_t)K * sizeof(sdr_segment), hipMemcpyHostToDevice, S->st));
-    rc = sdr_measure_xyz_device((const float*)S->map.p, (size_t)W * 3, px * 3, W, H, F, (const sdr_segment*)S->segs.p,
-                                K, (sdr_measurement*)S->out.p, S->st);
-    if (rc) return rc;
-    SDR_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(sdr_measurement), hipMemcpyDeviceToHost, S->st));
-    SDR_HIP(hipStreamSynchronize(S->st));
-    return SDR_OK;
+    HostCall c;
+    const float* d_xyz = (const float*)c.rows(c.S->map, xyz, (size_t)W * 12, xyz_stride * 4, xyz_frame_stride * 4, H, F);
+    const sdr_segment* d_segs = c.input(c.S->rows, segs, (size_t)K);
+    const auto s_out = c.output(out, (size_t)K);
+    if ((rc = c.ready())) return rc;
+    rc = sdr_measure_xyz_device(d_xyz, (size_t)W * 3, (size_t)W * H * 3, W, H, F, d_segs, K, c.at(s_out), c.stream());
+    return rc ? rc : c.finish();
 }
 
 int sdr_measurements_csv(const int* image_index, const sdr_segment* segs, const sdr_measurement* records,

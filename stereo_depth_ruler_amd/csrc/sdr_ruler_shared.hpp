@@ -2,8 +2,8 @@
 // sdr_footprint.hip, sdr_objects.hip) share: on the device the disparity loads, the canonical NaN, the wave
 // reductions, a rectangle's range test and the ruler's sample; on the host (ruler_host) the argument
 // guards, the Q and disparity-type plumbing of a launch, the per-thread persistent buffers (held in
-// sdr_host.hpp's ThreadState) and the host-pointer path of the calls that take plane records and queries.  The region rule of the
-// relief and the footprint is in sdr_region.hpp.
+// sdr_host.hpp's ThreadState) and the staged host-pointer call over them (HostCall).  The region
+// rule of the relief and the footprint is in sdr_region.hpp.
 #pragma once
 #include <string>
 #include <type_traits>
@@ -180,10 +180,12 @@ inline int check_plane_maps(const void* disp, int disp_type, size_t stride, size
     return SDR_OK;
 }
 
-// the device buffers of the host-pointer calls, kept by the thread (sdr_host.hpp ThreadState)
+// the device buffers of the host-pointer calls, kept by the thread (sdr_host.hpp ThreadState): the
+// maps, the confidence, the query rows (segments, regions, points), the outputs of one call, the
+// profile, the plane records and the label maps that go in
 struct HostBufs {
-    sdr::Buf map, conf, segs, out, prof, planes;
-    void release() { sdr::free_bufs({&map, &conf, &segs, &out, &prof, &planes}); }
+    sdr::Buf map, conf, rows, out, prof, planes, labels;
+    void release() { sdr::free_bufs({&map, &conf, &rows, &out, &prof, &planes, &labels}); }
 };
 using HostState = sdr::ThreadState<HostBufs>;
 
@@ -194,41 +196,110 @@ inline int host_state(HostState** out) {
     return S.acquire();
 }
 
-// rows of `row_bytes` of F frames of H rows into a dense device buffer
-inline int upload_rows(void* dst, const void* src, size_t row_bytes, size_t src_row, size_t src_frame, int H,
-                       int F, hipStream_t st) {
-    for (int f = 0; f < F; f++)
-        SDR_HIP(hipMemcpy2DAsync((char*)dst + (size_t)f * row_bytes * H, row_bytes,
-                                   (const char*)src + (size_t)f * src_frame, src_row, row_bytes, H,
-                                   hipMemcpyHostToDevice, st));
-    return SDR_OK;
-}
-
-// the host-pointer calls' maps into the thread's persistent buffers (dense rows)
-inline int upload_maps(HostState* S, const void* disp, int disp_type, size_t stride, size_t fstride, int W, int H,
-                       int F, const float* conf) {
-    const size_t es = disp_type == SDR_DISP_F32 ? 4 : 2, px = (size_t)W * H;
+// One host-pointer call over the thread's state, from its guards on: the inputs are staged into the
+// thread's buffers on the thread's stream, the outputs get places in S->out (sdr_layout.hpp's rule)
+// and the host pointers they go back to, the entry runs its device form on stream() and returns
+// finish().  The first failure sticks in `rc`: every later operation does nothing and hands out
+// null, and ready() and finish() return it.
+struct HostCall {
+    struct Maps {
+        const void* disp;
+        const float* conf;
+        size_t stride, fstride;  // of the dense device map, in elements
+    };
+    struct Back {
+        void* host;
+        const sdr::Buf* buf;
+        size_t off, bytes;
+    };
+    HostState* S = nullptr;
     int rc;
-    if ((rc = sdr::ensure(S->map, (size_t)F * px * es)) || (rc = sdr::ensure(S->conf, conf ? (size_t)F * px * 4 : 0)))
-        return rc;
-    if ((rc = upload_rows(S->map.p, disp, (size_t)W * es, stride * es, fstride * es, H, F, S->st))) return rc;
-    if (conf) SDR_HIP(hipMemcpyAsync(S->conf.p, conf, (size_t)F * px * 4, hipMemcpyHostToDevice, S->st));
-    return SDR_OK;
-}
+    sdr::ScratchLayout outs;
+    Back back[4];  // the most outputs a call has (the plane search)
+    int nback = 0;
 
-// the plane records, the queries and the optional label maps of a host-pointer call into the
-// thread's buffers (planes; segs; prof), and room for its records (out)
-inline int upload_queries(HostState* S, const sdr_plane* planes, int P, const void* queries, size_t query_bytes,
-                          const uint8_t* labels, size_t label_bytes, size_t out_bytes) {
-    int rc;
-    if ((rc = sdr::ensure(S->segs, query_bytes)) || (rc = sdr::ensure(S->planes, (size_t)P * sizeof(sdr_plane))) ||
-        (rc = sdr::ensure(S->prof, labels ? label_bytes : 0)) || (rc = sdr::ensure(S->out, out_bytes)))
+    HostCall() : rc(host_state(&S)) {}
+    void* stream() const { return S->st; }
+
+    int hip(hipError_t e, const char* what) {
+        if (e != hipSuccess && !rc) rc = sdr::set_error(SDR_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
         return rc;
-    SDR_HIP(hipMemcpyAsync(S->segs.p, queries, query_bytes, hipMemcpyHostToDevice, S->st));
-    if (P) SDR_HIP(hipMemcpyAsync(S->planes.p, planes, (size_t)P * sizeof(sdr_plane), hipMemcpyHostToDevice, S->st));
-    if (labels) SDR_HIP(hipMemcpyAsync(S->prof.p, labels, label_bytes, hipMemcpyHostToDevice, S->st));
-    return SDR_OK;
-}
+    }
+    // `bytes` of room in a buffer of the thread; null on a failure
+    void* room(sdr::Buf& b, size_t bytes) {
+        if (!rc) rc = sdr::ensure(b, bytes);
+        return rc ? nullptr : b.p;
+    }
+    void copy_back(void* host, const sdr::Buf& b, size_t off, size_t bytes) {
+        if (rc || !host || !bytes) return;
+        if (nback == (int)(sizeof back / sizeof back[0])) {
+            rc = rfail(SDR_ERR_ARG, "too many outputs of a host call");
+            return;
+        }
+        back[nback++] = Back{host, &b, off, bytes};
+    }
+
+    // F frames of H rows of `row_bytes` (rows src_row, frames src_frame bytes apart) as dense rows
+    void* rows(sdr::Buf& b, const void* src, size_t row_bytes, size_t src_row, size_t src_frame, int H, int F) {
+        char* dst = (char*)room(b, (size_t)F * H * row_bytes);
+        for (int f = 0; f < F && !rc; f++)
+            hip(hipMemcpy2DAsync(dst + (size_t)f * row_bytes * H, row_bytes, (const char*)src + (size_t)f * src_frame,
+                                 src_row, row_bytes, H, hipMemcpyHostToDevice, S->st),
+                "hipMemcpy2DAsync (map rows)");
+        return rc ? nullptr : dst;
+    }
+    // the disparity maps and the optional dense confidence maps
+    Maps maps(const void* disp, int disp_type, size_t stride, size_t fstride, int W, int H, int F, const float* conf) {
+        const size_t es = disp_type == SDR_DISP_F32 ? 4 : 2;
+        Maps m{};
+        m.disp = rows(S->map, disp, (size_t)W * es, stride * es, fstride * es, H, F);
+        m.conf = input(S->conf, conf, conf ? (size_t)F * W * H : 0);
+        m.stride = (size_t)W;
+        m.fstride = (size_t)W * H;
+        return m;
+    }
+    // an input array in a buffer of the thread; null for an absent or empty one
+    template <typename T>
+    T* input(sdr::Buf& b, const T* host, size_t count) {
+        if (!host || !count) return nullptr;
+        T* d = (T*)room(b, count * sizeof(T));
+        if (!rc) hip(hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, S->st), "hipMemcpyAsync (input)");
+        return rc ? nullptr : d;
+    }
+    // an array that goes in and comes back (the profile: the rows the kernel leaves untouched keep
+    // the caller's values)
+    template <typename T>
+    T* inout(sdr::Buf& b, T* host, size_t count) {
+        T* d = input(b, host, count);
+        if (d) copy_back(host, b, 0, count * sizeof(T));
+        return d;
+    }
+    // room for `count` records in S->out, which finish() copies to `host` (null: to nowhere)
+    template <typename T>
+    sdr::Slice<T> output(T* host, size_t count) {
+        const sdr::Slice<T> s = outs.take<T>(count);
+        copy_back(host, S->out, s.off, s.bytes());
+        return s;
+    }
+    // after the last output(): S->out holds them all
+    int ready() {
+        room(S->out, outs.total);
+        return rc;
+    }
+    template <typename T>
+    T* at(const sdr::Slice<T>& s) const {
+        return (T*)((char*)S->out.p + s.off);
+    }
+    // after the device form: the registered copies back, then one wait for the stream
+    int finish() {
+        for (int i = 0; i < nback && !rc; i++)
+            hip(hipMemcpyAsync(back[i].host, (const char*)back[i].buf->p + back[i].off, back[i].bytes,
+                               hipMemcpyDeviceToHost, S->st),
+                "hipMemcpyAsync (output)");
+        if (!rc) hip(hipStreamSynchronize(S->st), "hipStreamSynchronize");
+        return rc;
+    }
+};
 
 // The host-pointer form of an entry that measures regions against plane records (the relief, the
 // footprint): `check` is the entry's parameter guard, `entry` its device form.
@@ -240,20 +311,16 @@ inline int region_host_call(Check check, Entry entry, const void* disp, int disp
     int rc = check_plane_maps(disp, disp_type, stride, frame_stride, W, H, F, Q, params, queries, K, out);
     if (rc || (rc = check(params, planes, P))) return rc;
     if (K == 0) return SDR_OK;
-    HostState* S = nullptr;
-    if ((rc = host_state(&S))) return rc;
-    const size_t px = (size_t)W * H;
-    if ((rc = upload_maps(S, disp, disp_type, stride, frame_stride, W, H, F, conf)) ||
-        (rc = upload_queries(S, planes, P, queries, (size_t)K * sizeof(sdr_relief_query), labels, (size_t)F * px,
-                             (size_t)K * sizeof(Rec))))
-        return rc;
-    rc = entry(S->map.p, disp_type, (size_t)W, px, W, H, F, conf ? (const float*)S->conf.p : nullptr,
-               labels ? (const uint8_t*)S->prof.p : nullptr, Q, params, P ? (const sdr_plane*)S->planes.p : nullptr, P,
-               (const sdr_relief_query*)S->segs.p, K, (Rec*)S->out.p, S->st);
-    if (rc) return rc;
-    SDR_HIP(hipMemcpyAsync(out, S->out.p, (size_t)K * sizeof(Rec), hipMemcpyDeviceToHost, S->st));
-    SDR_HIP(hipStreamSynchronize(S->st));
-    return SDR_OK;
+    HostCall c;
+    const HostCall::Maps m = c.maps(disp, disp_type, stride, frame_stride, W, H, F, conf);
+    const sdr_plane* d_planes = c.input(c.S->planes, planes, (size_t)P);
+    const sdr_relief_query* d_queries = c.input(c.S->rows, queries, (size_t)K);
+    const uint8_t* d_labels = c.input(c.S->labels, labels, (size_t)F * W * H);
+    const auto s_out = c.output(out, (size_t)K);
+    if ((rc = c.ready())) return rc;
+    rc = entry(m.disp, disp_type, m.stride, m.fstride, W, H, F, m.conf, d_labels, Q, params, d_planes, P, d_queries,
+               K, c.at(s_out), c.stream());
+    return rc ? rc : c.finish();
 }
 
 }  // namespace ruler_host

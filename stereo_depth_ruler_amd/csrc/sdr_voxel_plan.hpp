@@ -10,6 +10,8 @@
 #include <algorithm>
 #include <cmath>
 
+#include "sdr_layout.hpp"
+
 namespace sdr {
 
 constexpr int kMinMaxBlocks = 512;                              // k_minmax: at most this many partials
@@ -25,10 +27,14 @@ struct VoxelParams {
 // ---- the arena ----------------------------------------------------------------------------------
 // Everything a call keeps on the device, in one block: the min/max partials, the 64-bit keys
 // before and after the sort, the heads and their scanned positions, the sort's ping-pong (voxel,
-// point) arrays, its histograms and the scan's block totals.  Every slice starts 256-byte aligned.
+// point) arrays, its histograms and the scan's block totals, laid out by sdr_layout.hpp's rule.
 struct VoxelArena {
+    // a layout slice as (offset, bytes): the call resolves it to the element type it took
     struct Slice {
-        size_t off, bytes;
+        size_t off = 0, bytes = 0;
+        Slice() = default;
+        template <typename T>
+        Slice(const sdr::Slice<T>& s) : off(s.off), bytes(s.bytes()) {}
     };
     int nb_rs, nh, nb_scan;  // radix-sort tiles, histogram entries (256 a tile), scan segments
     Slice partial, keys, sorted, head, pos, kv[4], hist, spart;
@@ -40,22 +46,17 @@ inline VoxelArena voxel_arena(int n) {
     a.nb_rs = (n + kRsTile - 1) / kRsTile;
     a.nh = 256 * a.nb_rs;
     a.nb_scan = (std::max(n, a.nh) + kScanSeg - 1) / kScanSeg;
-    size_t used = 0;
-    auto take = [&used](size_t bytes) {
-        const VoxelArena::Slice s{(used + 255) & ~(size_t)255, bytes};
-        used = s.off + bytes;
-        return s;
-    };
+    ScratchLayout l;
     const size_t un = (size_t)n;
-    a.partial = take(sizeof(float) * 7 * kMinMaxBlocks);
-    a.keys = take(sizeof(uint64_t) * un);
-    a.sorted = take(sizeof(uint64_t) * un);
-    a.head = take(sizeof(int) * un);
-    a.pos = take(sizeof(int) * un);
-    for (auto& s : a.kv) s = take(sizeof(uint32_t) * un);
-    a.hist = take(sizeof(int) * (size_t)a.nh);
-    a.spart = take(sizeof(int) * (size_t)a.nb_scan);
-    a.total = used;
+    a.partial = l.take<float>((size_t)7 * kMinMaxBlocks);
+    a.keys = l.take<uint64_t>(un);
+    a.sorted = l.take<uint64_t>(un);
+    a.head = l.take<int>(un);
+    a.pos = l.take<int>(un);
+    for (auto& s : a.kv) s = l.take<uint32_t>(un);
+    a.hist = l.take<int>((size_t)a.nh);
+    a.spart = l.take<int>((size_t)a.nb_scan);
+    a.total = l.total;
     return a;
 }
 

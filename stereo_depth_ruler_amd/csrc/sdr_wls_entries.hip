@@ -234,15 +234,16 @@ int sdr_fgs_filter_device(const uint8_t* d_guide, size_t gstride, int w, int h, 
     hipStream_t st = (hipStream_t)stream;
     std::vector<float> lut;
     fgs_lut_host(sigma, &lut);
-    // stream-ordered scratch: the weight table, and the plan's FGS arrays in one block
-    float* dlut = nullptr;
-    float* scr = nullptr;
+    // stream-ordered scratch, one block: the weight table, then the plan's FGS arrays
     const size_t px = (size_t)w * h;
-    SDR_HIP(sdr::scratch_alloc((void**)&dlut, sizeof(float) * lut.size(), st));
-    SDR_HIP(sdr::scratch_alloc((void**)&scr, sizeof(float) * pair.n.fgs_total(), st));
-    SDR_HIP(hipMemcpyAsync(dlut, lut.data(), sizeof(float) * lut.size(), hipMemcpyHostToDevice, st));
+    sdr::ScratchLayout lay;
+    const auto s_lut = lay.take<float>(lut.size()), s_fgs = lay.take<float>(pair.n.fgs_total());
+    sdr::Scratch sc(st);
+    if (const int rc = sc.open(lay)) return rc;
+    float* dlut = sc.at(s_lut);
+    SDR_HIP(hipMemcpyAsync(dlut, lut.data(), s_lut.bytes(), hipMemcpyHostToDevice, st));
     WlsBufs b{nullptr, nullptr, d_guide, gstride, 0, dlut};
-    b.s = sdr::carve_fgs(pair, scr);
+    b.s = sdr::carve_fgs(pair, sc.at(s_fgs));
     int bad = 0;
     for (int i = 0; i < nimg; i += 2) {
         const bool two = nimg - i >= 2;
@@ -250,9 +251,7 @@ int sdr_fgs_filter_device(const uint8_t* d_guide, size_t gstride, int w, int h, 
         b.R1 = two ? d_img + (i + 1) * px : nullptr;
         bad |= sdr::launch_fgs(two ? pair : last, b, st, nullptr);
     }
-    SDR_HIP(hipGetLastError());
-    SDR_HIP(sdr::scratch_free(dlut, st));
-    SDR_HIP(sdr::scratch_free(scr, st));
+    if (const int rc = sc.finish()) return rc;
     // the host LUT vector dies here: wait for its upload before returning
     SDR_HIP(hipStreamSynchronize(st));
     return bad ? refuse(sdr::kPcrLineLimit) : SDR_OK;
