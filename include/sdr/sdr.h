@@ -1123,9 +1123,68 @@ int sdr_sgbm_kernel_time(sdr_sgbm* h, int kind, int reset, float* total_ms, int*
  * host-pointer entry points compute one frame and never take the sweeps. */
 int sdr_sgbm_last_status(sdr_sgbm* h);
 /* Test hooks.  SDR_DEBUG_SWEEP_SPIN: polls a sweep's neighbour wait makes before it gives up
- * (<= 0: the default, about a second); a small value forces the failure path above. */
-enum { SDR_DEBUG_SWEEP_SPIN = 1 };
+ * (<= 0: the default, about a second); a small value forces the failure path above.
+ * SDR_DEBUG_PLAN_CUS: the compute-unit count this handle's calls give the two chain-count
+ * thresholds of the path launches (two chains a wave in k_paths_tc above 4 x CUs chains, two
+ * columns a workgroup in k_south_wta above 8 x CUs, and through them the 12-bit record format);
+ * <= 0: the device's own count.  1 sends a frame of a few hundred chains to the two-column kernels
+ * and a large value keeps it off them, on any GPU.  Both forms compute the same maps, so the knob
+ * changes which kernel runs and nothing else.  It never reaches the sweeps' tiling, the cost
+ * kernels' row bands or anything else that sizes a resident grid: a sweep sized for compute units
+ * that are not there would wait on a workgroup that never runs. */
+enum { SDR_DEBUG_SWEEP_SPIN = 1, SDR_DEBUG_PLAN_CUS = 2 };
 int sdr_sgbm_debug_knob(sdr_sgbm* h, int knob, int value);
+
+/* Which kernels a matcher call launches: the record the launchers themselves switch on, so a test
+ * can assert the instantiation a shape reaches.  Template arguments as in csrc/sdr_paths.hip:
+ * dpl = disparities a lane of a chain wave (2, 4, 8: D <= 128, 256, 512), pad = D below its class's
+ * 64 * dpl, r12 = 12-bit records, np = the directions the fused pass reads (P - 1), tc = two
+ * columns a workgroup. */
+enum {
+    SDR_SGBM_COST_NONE = 0,
+    SDR_SGBM_COST_ONE_PASS = 1, /* k_cost<nr, k, cn>: nr = blockSize rows, k = disparity pairs a lane */
+    SDR_SGBM_COST_CENSUS = 2,   /* the census cost kernel (nr and k as above, cn = 1) */
+    SDR_SGBM_COST_GENERIC = 3   /* the two-pass cost (blockSize > 11 or D > 256); nr = k = 0 */
+};
+enum {
+    SDR_SGBM_PATHS_NONE = 0,
+    SDR_SGBM_PATHS_CHAIN = 1, /* k_paths<dpl, pad, r12> */
+    SDR_SGBM_PATHS_TC = 2     /* k_paths_tc<pad> (dpl 4: two chains a wave) */
+};
+enum {
+    SDR_SGBM_SOUTH_NONE = 0,
+    SDR_SGBM_SOUTH_WTA = 1,  /* k_south_wta<dpl, pad, np, tc, r12> */
+    SDR_SGBM_SOUTH_SWEEP = 2 /* batched MODE_HH: k_sweep16<dw, pad, up> twice (up, then down + WTA) */
+};
+enum {
+    SDR_SGBM_POST_NONE = 0,
+    SDR_SGBM_POST_SPECKLE = 1,     /* LR check and median inside the speckle filter's labelling */
+    SDR_SGBM_POST_MEDIAN_LR = 2,   /* k_median3_lr */
+    SDR_SGBM_POST_MEDIAN_COLS = 3  /* k_median3_cols (the LR check cannot fire) */
+};
+typedef struct sdr_sgbm_launches {
+    int32_t cost_kernel, cost_nr, cost_k, cost_cn;
+    int32_t paths_kernel, paths_dpl, paths_pad, paths_r12;
+    int32_t south_kernel, south_dpl, south_pad, south_np, south_tc, south_r12;
+    int32_t sweep_dw, sweep_pad;             /* a sweep: disparity words a lane (4, 8), D < 32 * dw */
+    int32_t sweep_nslots[2], sweep_ntiles[2]; /* [0] the down pass, [1] the up pass */
+    int32_t post;
+    int32_t paths_chains, south_chains; /* chains of the two launches, all frames (a sweep: 0 south) */
+    int32_t cus;                        /* the compute units the two thresholds were taken at */
+    int32_t reserved[2];
+} sdr_sgbm_launches;
+/* The launches of one call of nframes frames of width x height x channels under p and the cost
+ * type.  cus = 0 asks the current device for its compute units; any other value keeps the call off
+ * the GPU.  Off the GPU a batch that could sweep (MODE_HH, >= 8 frames, D <= 256) is reported as
+ * SDR_SGBM_SOUTH_SWEEP with zero nslots and ntiles -- the tiling needs the device's occupancy
+ * query -- and on it a batch whose tiles do not fit the resident grid reports the chains it takes
+ * instead.  SDR_PATH_REC=16 in the environment is honoured as a new handle would.  A call the
+ * engine would refuse returns that status; a frame that matches no column reports no launch. */
+int sdr_sgbm_plan_query(const sdr_sgbm_params* p, int cost, int width, int height, int nframes,
+                        int channels, int cus, sdr_sgbm_launches* out);
+/* What the handle's last call launched (of a paired class call: the left handle's, both matchers'
+ * frames in one batch); SDR_ERR_ARG before the first call that ran the stages. */
+int sdr_sgbm_last_plan(const sdr_sgbm* h, sdr_sgbm_launches* out);
 
 /* Device self-test of the cross-lane primitives the kernels rely on (DPP wave shifts,
  * permlane swaps); fills 4 failure counters, all zero on a healthy gfx950. */
@@ -1160,7 +1219,13 @@ int sdr_stream_probe_ex(int device, size_t bytes, int iters, double* gbs3);
  *    (0 <= e <= P2) of 8 consecutive disparities d0..d0+7.  As three little-endian u32 w0, w1, w2:
  *    e[d0+2j] = w_j & 0xfff and e[d0+2j+1] = (w_j >> 16) & 0xfff for j = 0..2; e[d0+6] =
  *    (w0 >> 12 & 0xf) | (w1 >> 12 & 0xf) << 4 | (w2 >> 12 & 0xf) << 8, and e[d0+7] the same from
- *    bits 28..31.  A pixel's R records take R*D*3/2 bytes; the rest of a frame's span is unused. */
+ *    bits 28..31.  A pixel's R records take R*D*3/2 bytes; the rest of a frame's span is unused.
+ *  - a batch that swept (MODE_HH, >= 8 frames; sdr_sgbm_last_plan says SDR_SGBM_SOUTH_SWEEP):
+ *    [F][H][W1][3][D] s16, frames 3*H*W1*D*2 bytes apart: record 0 = L of E, record 1 = L of W,
+ *    record 2 = the up record, min(32767, L_N + L_NE + L_NW) -- the saturating sum of the three
+ *    bottom-to-top directions' path costs, written by the up sweep.  The down sweep adds S, SE and
+ *    SW on chip; path costs are non-negative, so the grouped saturating sum equals the sum of all
+ *    eight in the order above. */
 int sdr_sgbm_debug_stage(const sdr_sgbm* h, int stage, void* host_dst, size_t bytes);
 
 /* Page-locked host memory (the role of cv::cuda::HostMem): host buffers from sdr_host_alloc that

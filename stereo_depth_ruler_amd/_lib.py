@@ -77,6 +77,51 @@ def fgs_plan(w, h, nframes=1, nimg=2, num_iter=3, solver=FGS_THOMAS, cus=0):
     return plan
 
 
+COST_KERNELS = {0: "none", 1: "k_cost", 2: "census", 3: "generic"}  # SDR_SGBM_COST_*
+PATHS_KERNELS = {0: "none", 1: "k_paths", 2: "k_paths_tc"}              # SDR_SGBM_PATHS_*
+SOUTH_KERNELS = {0: "none", 1: "k_south_wta", 2: "sweep"}               # SDR_SGBM_SOUTH_*
+POST_ROUTES = {0: "none", 1: "speckle", 2: "median3_lr", 3: "median3_cols"}  # SDR_SGBM_POST_*
+
+
+class SgbmLaunches(ctypes.Structure):
+    """sdr_sgbm_launches (sdr_sgbm_plan_query, sdr_sgbm_last_plan)."""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "cost_kernel", "cost_nr", "cost_k", "cost_cn", "paths_kernel", "paths_dpl", "paths_pad",
+        "paths_r12", "south_kernel", "south_dpl", "south_pad", "south_np", "south_tc", "south_r12",
+        "sweep_dw", "sweep_pad")] + \
+               [("sweep_nslots", ctypes.c_int32 * 2), ("sweep_ntiles", ctypes.c_int32 * 2)] + \
+               [(n, ctypes.c_int32) for n in ("post", "paths_chains", "south_chains", "cus")] + \
+               [("reserved", ctypes.c_int32 * 2)]
+
+    def as_dict(self):
+        """{"cost": (family, NR, K, CN), "paths": (family, DPL, PAD, R12), "south": ("k_south_wta",
+        DPL, PAD, NP, TC, R12) or ("sweep", DW, PAD) or ("none",), "sweep_shape": ((nslots, ntiles)
+        of the down pass, of the up pass), "post": route, "paths_chains", "south_chains", "cus"}."""
+        paths = (PATHS_KERNELS[self.paths_kernel],)
+        if self.paths_kernel:
+            paths += (self.paths_dpl, bool(self.paths_pad), bool(self.paths_r12))
+        south = (SOUTH_KERNELS[self.south_kernel],)
+        if self.south_kernel == 1:
+            south += (self.south_dpl, bool(self.south_pad), self.south_np, bool(self.south_tc),
+                      bool(self.south_r12))
+        elif self.south_kernel == 2:
+            south += (self.sweep_dw, bool(self.sweep_pad))
+        return {"cost": (COST_KERNELS[self.cost_kernel], self.cost_nr, self.cost_k, self.cost_cn),
+                "paths": paths, "south": south,
+                "sweep_shape": tuple((self.sweep_nslots[i], self.sweep_ntiles[i]) for i in range(2)),
+                "post": POST_ROUTES[self.post], "paths_chains": self.paths_chains,
+                "south_chains": self.south_chains, "cus": self.cus}
+
+
+def sgbm_plan(params, w, h, nframes=1, channels=1, cost=0, cus=0):
+    """The kernels a matcher call of nframes frames of w x h takes under `params` (SgbmParams), as
+    SgbmLaunches.as_dict(); cus = 0 asks the current device, any other value stays off the GPU."""
+    out = SgbmLaunches()
+    check(lib().sdr_sgbm_plan_query(ctypes.byref(params), int(cost), int(w), int(h), int(nframes),
+                                    int(channels), int(cus), ctypes.byref(out)))
+    return out.as_dict()
+
+
 class Segment(ctypes.Structure):
     """sdr_segment."""
     _fields_ = [(n, ctypes.c_int32) for n in ("frame", "x0", "y0", "x1", "y1")]
@@ -317,6 +362,8 @@ SIGNATURES = [
     ("sdr_stream_probe", _i, [_i, _sz, _i, _c.POINTER(_c.c_double)]),
     ("sdr_stream_probe_ex", _i, [_i, _sz, _i, _c.POINTER(_c.c_double)]),
     ("sdr_sgbm_debug_knob", _i, [_vp, _i, _i]),
+    ("sdr_sgbm_plan_query", _i, [_PP, _i, _i, _i, _i, _i, _i, _c.POINTER(SgbmLaunches)]),
+    ("sdr_sgbm_last_plan", _i, [_vp, _c.POINTER(SgbmLaunches)]),
     ("sdr_ruler_params_default", None, [_c.POINTER(RulerParams)]),
     ("sdr_measure_disp_device", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _c.POINTER(_c.c_double),
                                      _c.POINTER(RulerParams), _vp, _i, _vp, _vp, _vp]),

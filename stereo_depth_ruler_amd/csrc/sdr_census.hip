@@ -366,10 +366,10 @@ static void launch_census_t(const Geometry& g, CostArgs a, int F, hipStream_t st
 }
 
 // SH2 <= 5 and D <= 256 (check_frame refuses the rest under the census cost)
-void launch_cost_census(const Geometry& g, const CostArgs& a, int F, hipStream_t st) {
+void launch_cost_census(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st) {
     if (a.row_end <= a.row_begin && a.naux == 0) return;
-    const int NR = 2 * g.SH2 + 1;
-    const bool k2 = g.D > 128;
+    const int NR = c.nr;
+    const bool k2 = c.k == 2;
 #define SDR_CENSUS(NRV)                                              \
     case NRV:                                                        \
         if (k2) launch_census_t<NRV, 2>(g, a, F, st);                \

@@ -169,11 +169,16 @@ size_t cost_sink_bytes(const Geometry& g) { return (size_t)(g.W1 + 64) * g.D * 2
 // SH2 <= 5 and D <= 256: k_cost (one pass, register ring); otherwise launch_cost_generic
 bool cost_supported(const Geometry& g) { return g.SH2 == g.SW2 && g.D <= 512; }
 
-void launch_cost(const Geometry& g, const CostArgs& a, int F, hipStream_t st) {
+CostChoice cost_choice(const Geometry& g, int cn, bool census) {
+    if (!census && (g.SH2 > 5 || g.D > 256)) return {SDR_SGBM_COST_GENERIC, 0, 0, cn};
+    return {census ? SDR_SGBM_COST_CENSUS : SDR_SGBM_COST_ONE_PASS, 2 * g.SH2 + 1, g.D > 128 ? 2 : 1, cn};
+}
+
+void launch_cost(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st) {
     if (a.row_end <= a.row_begin && a.naux == 0) return;
-    if (a.pl.cn == 3) return launch_cost_cn3(g, a, F, st);
-    const int NR = 2 * g.SH2 + 1;
-    const bool k2 = g.D > 128;
+    if (c.cn == 3) return launch_cost_cn3(g, a, c, F, st);
+    const int NR = c.nr;
+    const bool k2 = c.k == 2;
 #define SDR_COST(NRV)                                                 \
     case NRV:                                                         \
         if (k2) launch_cost_t<NRV, 2, 1>(g, a, F, st);                \

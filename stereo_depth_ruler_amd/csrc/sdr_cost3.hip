@@ -6,11 +6,11 @@
 
 namespace sdr {
 
-void launch_cost_cn3_k2(const Geometry& g, const CostArgs& a, int F, hipStream_t st);
+void launch_cost_cn3_k2(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st);
 
-void launch_cost_cn3(const Geometry& g, const CostArgs& a, int F, hipStream_t st) {
-    if (g.D > 128) return launch_cost_cn3_k2(g, a, F, st);
-    switch (2 * g.SH2 + 1) {
+void launch_cost_cn3(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st) {
+    if (c.k == 2) return launch_cost_cn3_k2(g, a, c, F, st);
+    switch (c.nr) {
         case 1: launch_cost_t<1, 1, 3>(g, a, F, st); break;
         case 3: launch_cost_t<3, 1, 3>(g, a, F, st); break;
         case 5: launch_cost_t<5, 1, 3>(g, a, F, st); break;

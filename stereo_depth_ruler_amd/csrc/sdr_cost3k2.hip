@@ -4,8 +4,8 @@
 
 namespace sdr {
 
-void launch_cost_cn3_k2(const Geometry& g, const CostArgs& a, int F, hipStream_t st) {
-    switch (2 * g.SH2 + 1) {
+void launch_cost_cn3_k2(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st) {
+    switch (c.nr) {
         case 1: launch_cost_t<1, 2, 3>(g, a, F, st); break;
         case 3: launch_cost_t<3, 2, 3>(g, a, F, st); break;
         case 5: launch_cost_t<5, 2, 3>(g, a, F, st); break;

@@ -8,9 +8,11 @@
 // What a call does is decided once, by its plan (sdr_plan.hpp); the stages below read it.
 // No host synchronisation, allocation or copy happens inside the enqueue once scratch is sized,
 // so the sequence can be captured into a hipGraph by the caller.
+#include "sdr_device.hpp"
 #include "sdr_handle.hpp"
 
 #include <algorithm>
+#include <cstdlib>
 #include <map>
 #include <mutex>
 
@@ -151,9 +153,10 @@ void stage_cost(sdr_sgbm* h, const Plan& p, const sdr::Planes& planes) {
     KTimer kt(h, SDR_KERNEL_COST);
     // blockSize 13..17 (within the int16 domain) or D > 256: the two-pass cost through the
     // idle L records
-    if (p.census()) sdr::launch_cost_census(g, ca, p.F, h->stream);
-    else if (g.SH2 > 5 || g.D > 256) sdr::launch_cost_generic(g, ca, p.F, (uint32_t*)h->Lr.p, h->stream);
-    else sdr::launch_cost(g, ca, p.F, h->stream);
+    const sdr::CostChoice cc = sdr::cost_choice(g, p.cn, p.census());
+    if (cc.kernel == SDR_SGBM_COST_CENSUS) sdr::launch_cost_census(g, ca, cc, p.F, h->stream);
+    else if (cc.kernel == SDR_SGBM_COST_GENERIC) sdr::launch_cost_generic(g, ca, p.F, (uint32_t*)h->Lr.p, h->stream);
+    else sdr::launch_cost(g, ca, cc, p.F, h->stream);
 }
 
 void add_dir(sdr::PathLaunch& pl, int dir, int nch, int H, int16_t* out) {
@@ -170,19 +173,25 @@ void add_dir(sdr::PathLaunch& pl, int dir, int nch, int H, int16_t* out) {
 // The directions of the two path launches.  pls, k_paths: every direction except the
 // top-to-bottom one, each into its own L record (in the order E, W, [S], SE, SW, N, NE, NW that
 // k_wta_lr's sum uses); plS, k_south_wta: the top-to-bottom chains fused with the WTA, reading
-// the other P-1 records.
-void path_dirs(const sdr_sgbm* h, const Plan& p, sdr::PathLaunch& pls, sdr::PathLaunch& plS) {
+// the other P-1 records.  v: the call's volumes (all null for a plan query, which reads the
+// launches' shapes alone).
+struct Volumes {
+    int16_t *C, *Lr, *Caux;
+};
+int16_t* at(int16_t* base, size_t off) { return base ? base + off : nullptr; }
+
+void path_dirs(const Volumes& v, const Plan& p, sdr::PathLaunch& pls, sdr::PathLaunch& plS) {
     const sdr::Geometry& g = p.e.g;
     const int H = g.H;
-    int16_t* Lr = vol_L(h, p);
-    int16_t* Caux = vol_Caux(h, p);
-    pls.C = plS.C = vol_C(h, p);
+    int16_t* Lr = v.Lr;
+    int16_t* Caux = v.Caux;
+    pls.C = plS.C = v.C;
     pls.cs_fstride = plS.cs_fstride = p.cells;
     pls.l_fstride = plS.l_fstride = p.lfs;
     pls.l_pix = plS.l_pix = p.nrec * g.D;
     pls.aux_fstride = plS.aux_fstride = p.aux_fstride;
     int nbuf = 0;
-    auto buf = [&]() { return Lr + (size_t)(nbuf++) * g.D; };
+    auto buf = [&]() { return at(Lr, (size_t)(nbuf++) * g.D); };
     const int nE = H, nS = g.W1, nD = g.W1 + H - 1;
     // longest chains first: the E/W rows (W1 steps) are dispatched before the shorter ones
     add_dir(pls, sdr::DIR_E, nE, H, buf());
@@ -196,7 +205,7 @@ void path_dirs(const sdr_sgbm* h, const Plan& p, sdr::PathLaunch& pls, sdr::Path
             d.yend = sp.end;
             d.write_from = sp.out0;
             if (sp.aux_rows) {
-                d.Caux = Caux + p.aux_off(s);
+                d.Caux = at(Caux, p.aux_off(s));
                 d.aux_row0 = sp.s0;
                 d.aux_rows = sp.aux_rows;
             }
@@ -225,7 +234,7 @@ void path_dirs(const sdr_sgbm* h, const Plan& p, sdr::PathLaunch& pls, sdr::Path
         r.lo = sp.out0;
         r.hi = sp.end;
         r.s0 = sp.s0;
-        r.aux = Caux + p.aux_off(s);
+        r.aux = at(Caux, p.aux_off(s));
     }
     for (sdr::PathLaunch* pl : {&pls, &plS}) {
         pl->prefix[0] = 0;
@@ -238,16 +247,52 @@ void path_dirs(const sdr_sgbm* h, const Plan& p, sdr::PathLaunch& pls, sdr::Path
 // written once and read once) and the fused pass rebuilds L = C - e exactly.  Not the sweep
 // (k_sweep16 reads int16 records, and its up record is a sum of three), not 3WAY, and only
 // where both launchers dispatch a kernel that implements it; the buffer keeps its int16 size.
-void record_format(sdr_sgbm* h, Plan& p, sdr::PathLaunch& pls, sdr::PathLaunch& plS) {
+// rec16: SDR_PATH_REC=16 (sdr_sgbm::rec16); cus: the compute units of the launchers' thresholds.
+void record_format(const Volumes& v, Plan& p, sdr::PathLaunch& pls, sdr::PathLaunch& plS, bool rec16, int cus) {
     const sdr::Geometry& g = p.e.g;
-    p.rec12 = !h->rec16 && !p.sweep && g.P2 >= 0 && g.P2 <= 4095 &&
+    p.rec12 = !rec16 && !p.sweep && g.P2 >= 0 && g.P2 <= 4095 &&
               (p.e.mode == SDR_MODE_SGBM || p.e.mode == SDR_MODE_HH || p.e.mode == SDR_MODE_HH4) &&
-              sdr::path_rec12_supported(g, pls, plS, p.nrec + 1, p.F);
+              sdr::path_rec12_supported(g, pls, plS, p.nrec + 1, p.F, cus);
     if (!p.rec12) return;
     const int recel = g.D * 3 / 4;  // int16 elements of one direction's record
     pls.rec12 = plS.rec12 = 1;
     pls.l_pix = plS.l_pix = p.nrec * recel;
-    for (int i = 0; i < pls.ndirs; i++) pls.d[i].out = vol_L(h, p) + (size_t)i * recel;
+    for (int i = 0; i < pls.ndirs; i++) pls.d[i].out = at(v.Lr, (size_t)i * recel);
+}
+
+// The two path launches of a plan whose sweep decision is made (plan_sweep), the record format and
+// the kernel of every launch; p.launches is the record sdr_sgbm_last_plan and sdr_sgbm_plan_query
+// hand out, and pc / sc -- the same values -- are what the launchers switch on.  cus holds for
+// the chain-count thresholds alone (SDR_DEBUG_PLAN_CUS): nothing here sizes a grid.
+struct PathChoices {
+    sdr::PathsChoice pc;
+    sdr::SouthChoice sc;
+};
+PathChoices plan_launches(const Volumes& v, Plan& p, sdr::PathLaunch& pls, sdr::PathLaunch& plS, bool rec16,
+                          int cus) {
+    const sdr::Geometry& g = p.e.g;
+    path_dirs(v, p, pls, plS);
+    record_format(v, p, pls, plS, rec16, cus);
+    PathChoices ch;
+    ch.pc = sdr::paths_choice(g, pls, p.F, cus);
+    ch.sc = sdr::south_choice(g, plS, p.nrec + 1, p.F, cus);
+    const sdr::CostChoice cc = sdr::cost_choice(g, p.cn, p.census());
+    sdr_sgbm_launches& o = p.launches;
+    o = sdr_sgbm_launches{};
+    o.cost_kernel = cc.kernel, o.cost_nr = cc.nr, o.cost_k = cc.k, o.cost_cn = cc.cn;
+    o.paths_kernel = ch.pc.kernel, o.paths_dpl = ch.pc.dpl, o.paths_pad = ch.pc.pad, o.paths_r12 = ch.pc.r12;
+    o.paths_chains = ch.pc.chains;
+    o.south_kernel = ch.sc.kernel, o.south_dpl = ch.sc.dpl, o.south_pad = ch.sc.pad, o.south_np = ch.sc.np;
+    o.south_tc = ch.sc.tc, o.south_r12 = ch.sc.r12, o.south_chains = ch.sc.chains;
+    if (p.sweep) {
+        o.south_kernel = SDR_SGBM_SOUTH_SWEEP;
+        o.sweep_dw = g.D <= 128 ? 4 : 8;  // launch_sweep's classes
+        o.sweep_pad = g.D < 32 * o.sweep_dw;
+        for (int up = 0; up < 2; up++) o.sweep_nslots[up] = p.shp[up].nslots, o.sweep_ntiles[up] = p.shp[up].ntiles;
+    }
+    o.post = p.speckle() ? SDR_SGBM_POST_SPECKLE : p.lr_skipped ? SDR_SGBM_POST_MEDIAN_COLS : SDR_SGBM_POST_MEDIAN_LR;
+    o.cus = cus;
+    return ch;
 }
 
 // Batched MODE_HH: the up sweep into record 2, then the down sweep with the WTA.
@@ -290,7 +335,7 @@ int stage_sweep(sdr_sgbm* h, const Plan& p) {
 }
 
 // The top-to-bottom chains fused with the WTA (a batch that swept has run it in the down sweep).
-void stage_south_wta(sdr_sgbm* h, const Plan& p, const sdr::PathLaunch& plS) {
+void stage_south_wta(sdr_sgbm* h, const Plan& p, const sdr::PathLaunch& plS, const sdr::SouthChoice& sc) {
     sdr::SouthWtaArgs wa{};
     wa.L = vol_L(h, p);
     wa.npaths = p.nrec + 1;
@@ -300,7 +345,7 @@ void stage_south_wta(sdr_sgbm* h, const Plan& p, const sdr::PathLaunch& plS) {
     wa.uniq = p.e.uniq;
     wa.uniq_simd = p.e.uniq_simd;
     KTimer kt(h, SDR_KERNEL_WTA_LR);
-    sdr::launch_south_wta(p.e.g, plS, wa, p.F, h->stream);
+    sdr::launch_south_wta(p.e.g, plS, wa, sc, p.F, h->stream);
 }
 
 // LR check, median and speckle filter into dst, the frame minima, and the sweep's verdict.
@@ -379,13 +424,14 @@ int enqueue_compute(sdr_sgbm* h, Plan& planned, const Io& io, int16_t** final_di
     if (h->timing) SDR_HIP(hipEventRecord(h->ev[1], st));
 
     sdr::PathLaunch pls{}, plS{};
-    path_dirs(h, p, pls, plS);
-    record_format(h, p, pls, plS);
-    { KTimer kt(h, SDR_KERNEL_PATHS); sdr::launch_paths(p.e.g, pls, p.F, st); }
+    // (the debug knob's compute units reach the two chain-count thresholds, nothing else)
+    const int cus = h->plan_cus > 0 ? h->plan_cus : sdr::device_cus();
+    const PathChoices ch = plan_launches({vol_C(h, p), vol_L(h, p), vol_Caux(h, p)}, p, pls, plS, h->rec16, cus);
+    { KTimer kt(h, SDR_KERNEL_PATHS); sdr::launch_paths(p.e.g, pls, ch.pc, p.F, st); }
     if (p.sweep && (rc = stage_sweep(h, p))) return rc;
     if (h->timing) SDR_HIP(hipEventRecord(h->ev[2], st));
 
-    if (!p.sweep) stage_south_wta(h, p, plS);
+    if (!p.sweep) stage_south_wta(h, p, plS, ch.sc);
     if ((rc = stage_post(h, p, dst, io.out_min))) return rc;
     if (h->timing) SDR_HIP(hipEventRecord(h->ev[3], st));
     SDR_HIP(retire(h));
@@ -420,6 +466,38 @@ size_t sdr_sgbm_scratch_bytes_ex(const sdr_sgbm_params* p, int cost, int width, 
         return 0;
     }
     return sdr::plan_scratch_bytes(pl);
+}
+
+int sdr_sgbm_plan_query(const sdr_sgbm_params* p, int cost, int width, int height, int nframes, int channels,
+                        int cus, sdr_sgbm_launches* out) {
+    if (!p || !out) return fail(SDR_ERR_ARG, "null argument");
+    if (width <= 0 || height <= 0 || nframes <= 0 || cus < 0) return fail(SDR_ERR_ARG, "bad size, frame count or cus");
+    Plan pl = sdr::make_plan(*p, cost, width, height, nframes, channels);
+    if (pl.rc) return refuse(pl);
+    *out = sdr_sgbm_launches{};
+    out->cus = cus ? cus : sdr::device_cus();
+    if (pl.empty) return SDR_OK;
+    const sdr::Geometry& g = pl.e.g;
+    // the sweep decision of size_scratch: on the device its tiling, off it the batch's eligibility
+    // (sweep_shape asks the device for the kernels' occupancy; it takes no batch past D = 256)
+    sdr::SweepShape shp[2] = {};
+    const bool eligible = pl.sweep_batch() && g.D <= 256;
+    for (int up = 0; up < 2 && eligible; up++)
+        shp[up] = cus ? sdr::SweepShape{0, 0, 1, 0, 0} : sdr::sweep_shape(g, pl.F, up != 0);
+    sdr::plan_sweep(&pl, shp);
+    sdr::PathLaunch pls{}, plS{};
+    const char* rec = getenv("SDR_PATH_REC");
+    plan_launches({nullptr, nullptr, nullptr}, pl, pls, plS, rec && atoi(rec) == 16, out->cus);
+    *out = pl.launches;
+    if (cus) out->sweep_nslots[0] = out->sweep_nslots[1] = 0;  // eligible, shape unknown
+    return SDR_OK;
+}
+
+int sdr_sgbm_last_plan(const sdr_sgbm* h, sdr_sgbm_launches* out) {
+    if (!h || !out) return fail(SDR_ERR_ARG, "null argument");
+    if (!h->last.launches.cost_kernel) return fail(SDR_ERR_ARG, "no call has run the stages on this handle yet");
+    *out = h->last.launches;
+    return SDR_OK;
 }
 
 int sdr_sgbm_compute_device(sdr_sgbm* h, const uint8_t* dL, const uint8_t* dR, int W, int H,

@@ -269,6 +269,10 @@ int sdr_sgbm_last_status(sdr_sgbm* h) {
 
 int sdr_sgbm_debug_knob(sdr_sgbm* h, int knob, int value) {
     if (!h) return set_error(SDR_ERR_ARG, "null handle");
+    if (knob == SDR_DEBUG_PLAN_CUS) {
+        h->plan_cus = value > 0 ? value : 0;
+        return SDR_OK;
+    }
     if (knob != SDR_DEBUG_SWEEP_SPIN) return set_error(SDR_ERR_ARG, "unknown knob");
     h->sweep_spin = value > 0 ? value : sdr::kSweepSpin;
     return SDR_OK;

@@ -26,6 +26,10 @@ struct sdr_sgbm {
     sdr::Buf sweep, status;
     int* status_host = nullptr;
     int sweep_spin = sdr::kSweepSpin;  // debug knob SDR_DEBUG_SWEEP_SPIN
+    // debug knob SDR_DEBUG_PLAN_CUS: the compute units paths_two_chain and south_two_col count
+    // with (0: the device's).  Read by enqueue_compute's plan_launches alone -- never by anything
+    // that sizes a resident grid (the sweeps' tiling, the cost kernels' row bands)
+    int plan_cus = 0;
     // SDR_PATH_REC=16 in the environment when the handle was created: int16 path-cost records
     // always (A/B and tests; the default takes 12-bit records where enqueue_compute can)
     bool rec16 = false;

@@ -212,15 +212,28 @@ struct SouthWtaArgs {
     size_t disp_fstride;
     int uniq, uniq_simd;
 };
-void launch_south_wta(const Geometry& g, const PathLaunch& pl, const SouthWtaArgs& a, int F,
-                      hipStream_t st);
-// The launchers' own choices of a two-chain k_paths / two-column k_south_wta (both keep int16
-// records), and whether the kernels launch_paths(pls) and launch_south_wta(plS, npaths) would
+// The kernel of each path launch, chosen once per call from the launch, the frames, the record
+// format (PathLaunch::rec12) and the compute units `cus` the chain-count thresholds hold for; the
+// launchers dispatch on this record and sdr_sgbm_plan_query / sdr_sgbm_last_plan report it
+// (kernel: SDR_SGBM_PATHS_* / SDR_SGBM_SOUTH_*, NONE for a launch without chains).
+struct PathsChoice {
+    int kernel, dpl, pad, r12, chains;
+};
+struct SouthChoice {
+    int kernel, dpl, pad, np, tc, r12, chains;
+};
+PathsChoice paths_choice(const Geometry& g, const PathLaunch& pl, int F, int cus);
+SouthChoice south_choice(const Geometry& g, const PathLaunch& pl, int npaths, int F, int cus);
+void launch_south_wta(const Geometry& g, const PathLaunch& pl, const SouthWtaArgs& a, const SouthChoice& c,
+                      int F, hipStream_t st);
+// The choices' two thresholds -- a two-chain k_paths / two-column k_south_wta (both keep int16
+// records) -- and whether the kernels launch_paths(pls) and launch_south_wta(plS, npaths) would
 // dispatch both implement the 12-bit record format: D = 128 exactly, one chain or column a wave,
 // 4, 5 or 8 paths.
-bool paths_two_chain(const Geometry& g, const PathLaunch& pl, int F);
-bool south_two_col(const Geometry& g, const PathLaunch& pl, int npaths, int F);
-bool path_rec12_supported(const Geometry& g, const PathLaunch& pls, const PathLaunch& plS, int npaths, int F);
+bool paths_two_chain(const Geometry& g, const PathLaunch& pl, int F, int cus);
+bool south_two_col(const Geometry& g, const PathLaunch& pl, int npaths, int F, int cus);
+bool path_rec12_supported(const Geometry& g, const PathLaunch& pls, const PathLaunch& plS, int npaths, int F,
+                          int cus);
 
 // The right view's WTA keys (SouthWtaArgs::d2), one word a pixel: kD2None until a left pixel
 // claims it, then d2_key of the claiming pixel with the smallest key.  x: the claiming pixel's
@@ -255,12 +268,20 @@ void launch_prefilter(const uint8_t* L, const uint8_t* R, size_t stride, size_t 
                       int H, int F, int ftzero, const Planes& pl, hipStream_t st, int split = 1 << 30,
                       uint32_t* d2fill = nullptr);
 bool cost_supported(const Geometry& g);
-void launch_cost(const Geometry& g, const CostArgs& a, int F, hipStream_t st);
+// The cost kernel of a call (kernel: SDR_SGBM_COST_*): k_cost<nr, k, cn> or the census kernel in
+// one pass, nr = 2 SH2 + 1 box rows and k = packed pairs a lane (2: D > 128); blockSize > 11 or
+// D > 256 takes the two-pass generic cost (nr = k = 0).  stage_cost and the launchers dispatch on it.
+struct CostChoice {
+    int kernel, nr, k, cn;
+};
+CostChoice cost_choice(const Geometry& g, int cn, bool census);
+// (kernel SDR_SGBM_COST_ONE_PASS)
+void launch_cost(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st);
 // blockSize > 11 (SH2 > 5) or D > 256 (sdr_cost_generic.hip): two passes through a scratch volume h1 of
 // cost_generic_scratch_bytes (the L-record buffer, idle until the path kernels)
 size_t cost_generic_scratch_bytes(const Geometry& g, int F);
 void launch_cost_generic(const Geometry& g, const CostArgs& a, int F, uint32_t* h1, hipStream_t st);
-void launch_cost_cn3(const Geometry& g, const CostArgs& a, int F, hipStream_t st);  // pl.cn == 3
+void launch_cost_cn3(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st);  // cn == 3
 // ---- census matching cost (sdr_census.hip; the definition: sdr.h SDR_COST_CENSUS_9X7) ----
 // 9x7 census descriptors of both images of F frames, desc u64 [F][2][H][W] (index 0: the frame's
 // left-role image, 1: its right-role image; frames >= split take the images swapped); d2fill as
@@ -270,8 +291,8 @@ void launch_census(const uint8_t* L, const uint8_t* R, size_t stride, size_t fst
 // launch_cost with the Hamming distance of the descriptors as the pixel cost (SH2 <= 5, D <= 256):
 // a.pl.L / a.pl.R are the left-role / right-role descriptor planes, u64 [H][W] a frame, frames
 // pl.fstrideL / pl.fstrideR u64 elements apart
-void launch_cost_census(const Geometry& g, const CostArgs& a, int F, hipStream_t st);
-void launch_paths(const Geometry& g, const PathLaunch& pl, int F, hipStream_t st);
+void launch_cost_census(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st);
+void launch_paths(const Geometry& g, const PathLaunch& pl, const PathsChoice& c, int F, hipStream_t st);
 void launch_median3(const int16_t* src, int16_t* dst, int W, int H, int F, hipStream_t st);
 // median of the LR-checked map (computed per tile from the WTA map and the right-view keys)
 void launch_median3_lr(const LrSrc& lr, int16_t* dst, int F, hipStream_t st);

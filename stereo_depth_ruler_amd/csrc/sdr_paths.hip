@@ -309,34 +309,53 @@ __global__ __launch_bounds__(256) void k_paths_tc(Geometry g, PathLaunch pl) {
 }
 
 // the two-chain kernel for this launch?  D <= 128, no redirected 3WAY rows, every direction with
-// chains of one length, and more chains than the chip's SIMDs (with fewer, one chain per wave
-// already has a SIMD each and the one-chain step is the cheaper one)
-bool paths_two_chain(const Geometry& g, const PathLaunch& pl, int F) {
+// chains of one length, and more chains than the SIMDs of `cus` compute units (with fewer, one
+// chain per wave already has a SIMD each and the one-chain step is the cheaper one)
+bool paths_two_chain(const Geometry& g, const PathLaunch& pl, int F, int cus) {
     if (g.D > 128 || pl.nredir > 0) return false;
     for (int i = 0; i < pl.ndirs; i++)
         if (pl.d[i].dir != DIR_E && pl.d[i].dir != DIR_W && pl.d[i].dir != DIR_N) return false;
-    return (long)pl.prefix[pl.ndirs] * F > 4L * device_cus();
+    return (long)pl.prefix[pl.ndirs] * F > 4L * cus;
 }
 
-void launch_paths(const Geometry& g, const PathLaunch& pl, int F, hipStream_t st) {
+// D's class: disparities a lane of a chain wave, and whether D is below the class's 64 * dpl
+static int dpl_of(int D) { return D <= 128 ? 2 : D <= 256 ? 4 : 8; }
+
+PathsChoice paths_choice(const Geometry& g, const PathLaunch& pl, int F, int cus) {
+    PathsChoice c{SDR_SGBM_PATHS_NONE, 0, 0, 0, 0};
     const int total = pl.prefix[pl.ndirs];
-    if (total <= 0) return;
-    if (paths_two_chain(g, pl, F)) {
+    if (total <= 0) return c;
+    c.chains = total * F;
+    c.dpl = dpl_of(g.D);
+    c.pad = g.D < 64 * c.dpl;
+    if (paths_two_chain(g, pl, F, cus)) {
+        c.kernel = SDR_SGBM_PATHS_TC;
+        c.dpl = 4;  // two chains of 32 lanes a wave
+        return c;
+    }
+    c.kernel = SDR_SGBM_PATHS_CHAIN;
+    c.r12 = c.dpl == 2 && !c.pad && pl.rec12;
+    return c;
+}
+
+void launch_paths(const Geometry& g, const PathLaunch& pl, const PathsChoice& c, int F, hipStream_t st) {
+    if (c.kernel == SDR_SGBM_PATHS_NONE) return;
+    if (c.kernel == SDR_SGBM_PATHS_TC) {
         const dim3 grid2((pair_workgroups(pl) + 3) / 4, F);
-        if (g.D < 128) hipLaunchKernelGGL((k_paths_tc<true>), grid2, dim3(256), 0, st, g, pl);
+        if (c.pad) hipLaunchKernelGGL((k_paths_tc<true>), grid2, dim3(256), 0, st, g, pl);
         else hipLaunchKernelGGL((k_paths_tc<false>), grid2, dim3(256), 0, st, g, pl);
         return;
     }
-    dim3 grid((total + 3) / 4, F);
-    if (g.D <= 128) {
-        if (g.D < 128) hipLaunchKernelGGL((k_paths<2, true>), grid, dim3(256), 0, st, g, pl);
-        else if (pl.rec12) hipLaunchKernelGGL((k_paths<2, false, true>), grid, dim3(256), 0, st, g, pl);
+    dim3 grid((pl.prefix[pl.ndirs] + 3) / 4, F);
+    if (c.dpl == 2) {
+        if (c.pad) hipLaunchKernelGGL((k_paths<2, true>), grid, dim3(256), 0, st, g, pl);
+        else if (c.r12) hipLaunchKernelGGL((k_paths<2, false, true>), grid, dim3(256), 0, st, g, pl);
         else hipLaunchKernelGGL((k_paths<2, false>), grid, dim3(256), 0, st, g, pl);
-    } else if (g.D <= 256) {
-        if (g.D < 256) hipLaunchKernelGGL((k_paths<4, true>), grid, dim3(256), 0, st, g, pl);
+    } else if (c.dpl == 4) {
+        if (c.pad) hipLaunchKernelGGL((k_paths<4, true>), grid, dim3(256), 0, st, g, pl);
         else hipLaunchKernelGGL((k_paths<4, false>), grid, dim3(256), 0, st, g, pl);
     } else {
-        if (g.D < 512) hipLaunchKernelGGL((k_paths<8, true>), grid, dim3(256), 0, st, g, pl);
+        if (c.pad) hipLaunchKernelGGL((k_paths<8, true>), grid, dim3(256), 0, st, g, pl);
         else hipLaunchKernelGGL((k_paths<8, false>), grid, dim3(256), 0, st, g, pl);
     }
 }
@@ -686,61 +705,77 @@ __global__ __launch_bounds__(256) void k_lr_apply(Geometry g0, const int16_t* __
         out[fo + (size_t)y * g.W + x] = (int16_t)lr_at(g, raw + fo, d2 + fo, x, y, d12);
 }
 
-// two columns per workgroup when the chains far outnumber what the chip holds at once (short,
-// latency-bound chains: the class path's 3WAY stripes), D <= 128, up to 5 paths
-bool south_two_col(const Geometry& g, const PathLaunch& pl, int npaths, int F) {
-    return g.D <= 128 && npaths <= 5 && (long)pl.prefix[pl.ndirs] * F > 8L * device_cus();
+// two columns per workgroup when the chains far outnumber what `cus` compute units hold at once
+// (short, latency-bound chains: the class path's 3WAY stripes), D <= 128, up to 5 paths
+bool south_two_col(const Geometry& g, const PathLaunch& pl, int npaths, int F, int cus) {
+    return g.D <= 128 && npaths <= 5 && (long)pl.prefix[pl.ndirs] * F > 8L * cus;
 }
 
-bool path_rec12_supported(const Geometry& g, const PathLaunch& pls, const PathLaunch& plS, int npaths, int F) {
+bool path_rec12_supported(const Geometry& g, const PathLaunch& pls, const PathLaunch& plS, int npaths, int F,
+                          int cus) {
     return g.D == 128 && (npaths == 4 || npaths == 5 || npaths == 8) && pls.nredir == 0 &&
-           !paths_two_chain(g, pls, F) && !south_two_col(g, plS, npaths, F);
+           !paths_two_chain(g, pls, F, cus) && !south_two_col(g, plS, npaths, F, cus);
+}
+
+SouthChoice south_choice(const Geometry& g, const PathLaunch& pl, int npaths, int F, int cus) {
+    SouthChoice c{SDR_SGBM_SOUTH_NONE, 0, 0, 0, 0, 0, 0};
+    if (pl.prefix[pl.ndirs] <= 0) return c;
+    c.kernel = SDR_SGBM_SOUTH_WTA;
+    c.chains = pl.prefix[pl.ndirs] * F;
+    c.dpl = dpl_of(g.D);
+    c.pad = g.D < 64 * c.dpl;
+    // the directions the fused pass reads: 3, 4, 5 paths, and 8 for every other count
+    c.np = npaths == 3 ? 2 : npaths == 4 ? 3 : npaths == 5 ? 4 : 7;
+    // the engine's decision (path_rec12_supported): one column, 4, 5 or 8 paths
+    c.r12 = c.dpl == 2 && !c.pad && pl.rec12;
+    c.tc = !c.r12 && c.dpl == 2 && south_two_col(g, pl, npaths, F, cus);  // at most 5 paths: np 2, 3, 4
+    return c;
 }
 
 template <int DPL, bool PAD>
-static void launch_south_np(const Geometry& g, const PathLaunch& pl, const SouthWtaArgs& a, int F,
-                            hipStream_t st) {
+static void launch_south_np(const Geometry& g, const PathLaunch& pl, const SouthWtaArgs& a, const SouthChoice& c,
+                            int F, hipStream_t st) {
     dim3 grid(pl.prefix[pl.ndirs], F);
     dim3 block(64 * (1 + kSouthConsumers));
     if constexpr (DPL == 2 && !PAD) {
-        if (pl.rec12) {  // the engine's decision (path_rec12_supported): one column, 4, 5 or 8 paths
-            switch (a.npaths) {
-            case 4: hipLaunchKernelGGL((k_south_wta<2, false, 3, false, true>), grid, block, 0, st, g, pl, a); return;
-            case 5: hipLaunchKernelGGL((k_south_wta<2, false, 4, false, true>), grid, block, 0, st, g, pl, a); return;
+        if (c.r12) {
+            switch (c.np) {
+            case 3: hipLaunchKernelGGL((k_south_wta<2, false, 3, false, true>), grid, block, 0, st, g, pl, a); return;
+            case 4: hipLaunchKernelGGL((k_south_wta<2, false, 4, false, true>), grid, block, 0, st, g, pl, a); return;
             default: hipLaunchKernelGGL((k_south_wta<2, false, 7, false, true>), grid, block, 0, st, g, pl, a); return;
             }
         }
     }
     if constexpr (DPL == 2) {
-        if (south_two_col(g, pl, a.npaths, F)) {
+        if (c.tc) {
             const dim3 grid2(pair_workgroups(pl), F);
-            switch (a.npaths) {
-            case 3: hipLaunchKernelGGL((k_south_wta<2, PAD, 2, true>), grid2, block, 0, st, g, pl, a); return;
-            case 4: hipLaunchKernelGGL((k_south_wta<2, PAD, 3, true>), grid2, block, 0, st, g, pl, a); return;
+            switch (c.np) {
+            case 2: hipLaunchKernelGGL((k_south_wta<2, PAD, 2, true>), grid2, block, 0, st, g, pl, a); return;
+            case 3: hipLaunchKernelGGL((k_south_wta<2, PAD, 3, true>), grid2, block, 0, st, g, pl, a); return;
             default: hipLaunchKernelGGL((k_south_wta<2, PAD, 4, true>), grid2, block, 0, st, g, pl, a); return;
             }
         }
     }
-    switch (a.npaths) {
-    case 3: hipLaunchKernelGGL((k_south_wta<DPL, PAD, 2>), grid, block, 0, st, g, pl, a); break;
-    case 4: hipLaunchKernelGGL((k_south_wta<DPL, PAD, 3>), grid, block, 0, st, g, pl, a); break;
-    case 5: hipLaunchKernelGGL((k_south_wta<DPL, PAD, 4>), grid, block, 0, st, g, pl, a); break;
+    switch (c.np) {
+    case 2: hipLaunchKernelGGL((k_south_wta<DPL, PAD, 2>), grid, block, 0, st, g, pl, a); break;
+    case 3: hipLaunchKernelGGL((k_south_wta<DPL, PAD, 3>), grid, block, 0, st, g, pl, a); break;
+    case 4: hipLaunchKernelGGL((k_south_wta<DPL, PAD, 4>), grid, block, 0, st, g, pl, a); break;
     default: hipLaunchKernelGGL((k_south_wta<DPL, PAD, 7>), grid, block, 0, st, g, pl, a); break;
     }
 }
 
-void launch_south_wta(const Geometry& g, const PathLaunch& pl, const SouthWtaArgs& a, int F,
-                      hipStream_t st) {
-    if (pl.prefix[pl.ndirs] <= 0) return;
-    if (g.D <= 128) {
-        if (g.D < 128) launch_south_np<2, true>(g, pl, a, F, st);
-        else launch_south_np<2, false>(g, pl, a, F, st);
-    } else if (g.D <= 256) {
-        if (g.D < 256) launch_south_np<4, true>(g, pl, a, F, st);
-        else launch_south_np<4, false>(g, pl, a, F, st);
+void launch_south_wta(const Geometry& g, const PathLaunch& pl, const SouthWtaArgs& a, const SouthChoice& c,
+                      int F, hipStream_t st) {
+    if (c.kernel != SDR_SGBM_SOUTH_WTA) return;
+    if (c.dpl == 2) {
+        if (c.pad) launch_south_np<2, true>(g, pl, a, c, F, st);
+        else launch_south_np<2, false>(g, pl, a, c, F, st);
+    } else if (c.dpl == 4) {
+        if (c.pad) launch_south_np<4, true>(g, pl, a, c, F, st);
+        else launch_south_np<4, false>(g, pl, a, c, F, st);
     } else {
-        if (g.D < 512) launch_south_np<8, true>(g, pl, a, F, st);
-        else launch_south_np<8, false>(g, pl, a, F, st);
+        if (c.pad) launch_south_np<8, true>(g, pl, a, c, F, st);
+        else launch_south_np<8, false>(g, pl, a, c, F, st);
     }
 }
 

@@ -67,6 +67,8 @@ struct Plan {
     // [pass][slots][tiles][2] counters, then the edge ring (sized for either pass)
     size_t flags_n[2] = {0, 0}, sweep_flags = 0, edge_bytes = 0;
     bool rec12 = false;      // 12-bit path-cost records (PathLaunch::rec12)
+    // the kernel of every launch, as the launchers switch on it (sdr_sgbm_last_plan)
+    sdr_sgbm_launches launches{};
 
     bool census() const { return e.cost == SDR_COST_CENSUS_9X7; }
     bool speckle() const { return e.speckle_ws > 0; }

@@ -21,7 +21,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import SDRError, SgbmParams, check, lib
+from ._lib import SDRError, SgbmLaunches, SgbmParams, check, lib
 
 try:  # torch is plumbing (device memory / streams); numpy-only use needs no torch
     import torch
@@ -36,7 +36,7 @@ COST_BT, COST_CENSUS = 0, 1
 (KERNEL_PREFILTER, KERNEL_COST, KERNEL_PATHS, KERNEL_WTA_LR, KERNEL_MEDIAN, KERNEL_SPECKLE,
  KERNEL_REPROJECT, KERNEL_LR_CHECK, KERNEL_SWEEP, KERNEL_WLS_PREP, KERNEL_FGS, KERNEL_WLS_FINAL,
  KERNEL_SWEEP_DOWN, KERNEL_FGS_COEF) = range(14)
-DEBUG_SWEEP_SPIN = 1  # sdr_sgbm_debug_knob
+DEBUG_SWEEP_SPIN, DEBUG_PLAN_CUS = 1, 2  # sdr_sgbm_debug_knob
 
 
 def _is_cuda(x) -> bool:
@@ -296,8 +296,15 @@ class StereoSGBM:
         check(lib().sdr_sgbm_last_status(self._h))
 
     def set_debug_knob(self, knob: int, value: int):
-        """Test hook (sdr_sgbm_debug_knob): DEBUG_SWEEP_SPIN = polls before a sweep wait gives up."""
+        """Test hook (sdr_sgbm_debug_knob): DEBUG_SWEEP_SPIN = polls before a sweep wait gives up;
+        DEBUG_PLAN_CUS = the compute units the path launches' chain-count thresholds count with."""
         check(lib().sdr_sgbm_debug_knob(self._h, int(knob), int(value)))
+
+    def last_plan(self) -> dict:
+        """The kernels the last compute launched (sdr_sgbm_last_plan), as _lib.sgbm_plan's dict."""
+        out = SgbmLaunches()
+        check(lib().sdr_sgbm_last_plan(self._h, ctypes.byref(out)))
+        return out.as_dict()
 
     def enable_timing(self, level=1):
         """0 off, 1 per-stage events, 2 per-stage + per-kernel-launch events."""

@@ -168,11 +168,15 @@ def _c_div(n, d):
     return np.sign(n) * (np.abs(n) // d)
 
 
-def _wta_rows(S, e, W, minX1):
-    """A.8 + A.9 on saturated sums S [rows][W1][D] -> disparity rows [rows][W] (1/16 px)."""
-    rows, W1, D = S.shape
+D2_NONE = 0xffffffff  # a right-view column no left pixel claimed (the engine's stage 5)
+
+
+def wta_map(S, e):
+    """A.8 on saturated sums S [rows][W1][D]: the winner-take-all disparity of every matched pixel
+    [rows][W1] (1/16 px, INVALID where uniqueness rejects the winner or every S saturated), with the
+    winners' index `best`, their cost `minS` and the accepted mask."""
+    D = S.shape[-1]
     inv = (e["minD"] - 1) * 16
-    out = np.full((rows, W), inv, np.int64)
     best = S.argmin(-1)  # first minimum
     minS = S.min(-1)
     dd = np.arange(D)
@@ -197,35 +201,57 @@ def _wta_rows(S, e, W, minX1):
     Sp = np.take_along_axis(S, bp[..., None], -1)[..., 0]
     den = np.maximum(Sm + Sp - 2 * minS, 1)
     d16 = best * 16 + np.where(inner, _c_div((Sm - Sp) * 16 + den, 2 * den), 0) + e["minD"] * 16
+    return np.where(reject, inv, d16), best, minS, ~reject
+
+
+def disp2_keys(best, minS, acc, e, W, minX1):
+    """The right view's WTA as the engine's stage 5 stores it, [rows][W] u32: per right-view column
+    x2 = x + minX1 - best - minD the accepted left pixel with the smallest minS, ties to the largest
+    x (OpenCV scans x descending and replaces only on a strictly smaller cost), as
+    minS << 16 | 0xffff - x (x: matched-range column); D2_NONE where no pixel claims the column."""
+    rows, W1 = best.shape
+    keys = np.full((rows, W), D2_NONE, np.int64)
     xs = np.arange(W1)
     for r in range(rows):
-        acc = ~reject[r]
-        out[r, minX1 + xs[acc]] = d16[r, acc]
-        # disp2: right-view WTA; per target column the smallest minS wins, ties -> the largest x
-        # (OpenCV scans x descending and replaces only on a strictly smaller cost)
-        disp2 = np.full(W, inv, np.int64)
-        xa = xs[acc]
-        x2 = xa + minX1 - best[r, acc] - e["minD"]
+        xa = xs[acc[r]]
+        x2 = xa + minX1 - best[r, acc[r]] - e["minD"]
         inr = (x2 >= 0) & (x2 < W)
-        xa, x2, ms, b = xa[inr], x2[inr], minS[r, acc][inr], best[r, acc][inr]
-        order = np.lexsort((-xa, ms, x2))
-        first = np.ones(order.size, bool)
-        first[1:] = x2[order][1:] != x2[order][:-1]
-        win = order[first]
-        disp2[x2[win]] = b[win] + e["minD"]
-        # A.9: invalidate when both floor/ceil correspondences disagree by more than disp12MaxDiff
+        k = (minS[r, acc[r]][inr] << 16) | (0xffff - xa[inr])
+        np.minimum.at(keys[r], x2[inr], k)
+    return keys.astype(np.uint32)
+
+
+def lr_verdict(raw, keys, e, minX1, W1):
+    """A.9 on the WTA map raw [rows][W] and the right view's keys: a matched pixel is invalidated
+    when both its floor and ceil correspondences disagree by more than disp12MaxDiff."""
+    rows, W = raw.shape
+    inv = (e["minD"] - 1) * 16
+    out = raw.astype(np.int64).copy()
+    xx = np.arange(W)
+    k = keys.astype(np.int64)
+    # the disparity a key stands for: its pixel's column minus the right-view column
+    disp2 = np.where(k == D2_NONE, inv, (0xffff - (k & 0xffff)) + minX1 - xx[None, :])
+    for r in range(rows):
         d1 = out[r]
-        xx = np.arange(W)
         chk = (xx >= minX1) & (xx < minX1 + W1) & (d1 != inv)
         lo, hi = d1 >> 4, (d1 + 15) >> 4
         bad = np.ones(W, bool)
         for dv in (lo, hi):
             xs2 = xx - dv
             inb = (xs2 >= 0) & (xs2 < W)
-            t = disp2[np.clip(xs2, 0, W - 1)]
+            t = disp2[r][np.clip(xs2, 0, W - 1)]
             bad &= inb & (t >= e["minD"]) & (np.abs(t - dv) > e["d12"])
         out[r, chk & bad] = inv
     return out
+
+
+def _wta_rows(S, e, W, minX1):
+    """A.8 + A.9 on saturated sums S [rows][W1][D] -> disparity rows [rows][W] (1/16 px)."""
+    rows, W1, _ = S.shape
+    d16, best, minS, acc = wta_map(S, e)
+    raw = np.full((rows, W), (e["minD"] - 1) * 16, np.int64)
+    raw[:, minX1:minX1 + W1] = d16
+    return lr_verdict(raw, disp2_keys(best, minS, acc, e, W, minX1), e, minX1, W1)
 
 
 def sgm_full_volume(L, R, minD, D, bs, P1, P2, d12, cap, uniq, ws=0, sr=0, mode=SGM_SGBM,

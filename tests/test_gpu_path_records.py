@@ -10,6 +10,7 @@ from contextlib import contextmanager
 import numpy as np
 import pytest
 
+import path_cases
 import stereo_depth_ruler_amd as sdr
 from stereo_depth_ruler_amd import _lib
 from stereo_depth_ruler_amd import synthetic as S
@@ -150,14 +151,7 @@ def test_two_frame_batch(gpu, oracle):
 
 def decode_rec12(raw, H, W1, nrec):
     """Stage 4's 12-bit records (sdr.h) -> e [H][W1][nrec][D]."""
-    w = raw.reshape(H, W1, nrec, D // 8, 3).astype(np.int64)
-    e = np.empty((H, W1, nrec, D // 8, 8), np.int64)
-    for j in range(3):
-        e[..., 2 * j] = w[..., j] & 0xfff
-        e[..., 2 * j + 1] = (w[..., j] >> 16) & 0xfff
-    e[..., 6] = sum(((w[..., j] >> 12) & 0xf) << (4 * j) for j in range(3))
-    e[..., 7] = sum(((w[..., j] >> 28) & 0xf) << (4 * j) for j in range(3))
-    return e.reshape(H, W1, nrec, D)
+    return path_cases.decode_rec12(raw, H, W1, nrec, D)
 
 
 @pytest.mark.gpu
