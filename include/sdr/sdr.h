@@ -1077,6 +1077,117 @@ int sdr_find_objects(const void* disp, int disp_type, size_t stride, size_t fram
                      int P, const sdr_relief_query* query, sdr_object* objects,
                      sdr_object_scan* scan, uint8_t* labels_out);
 
+/* ---- the clearance of two labelled things: the smallest 3-D distance between two pixel sets ----
+ * sdr_clearance* takes the pixels of a rectangle that carry one label of a label map (set A) and
+ * those that carry another (set B), gives every pixel the ruler's sample taken over its own set, and
+ * reports the closest pair of points, one of each set: the distance, where it is attained, and its
+ * split along and across a plane record's normal (the floor the two things stand on).  The result is
+ * a minimum with an index tie-break over all pairs: it depends neither on the order the pairs are
+ * visited in nor on the order the workgroups finish in, and every output is defined to the bit.
+ *   - Query {frame, x0, y0, x1, y1, plane, label_a, label_b}.  Region: the plane fit's rule
+ *     (xs, xe, ys, ye, rw, rh, area; u = x - xs, v = y - ys).  A dense uint8 label map is required.
+ *     A frame outside [0, F) or a corner outside the image, a label outside 0..255, or
+ *     label_a == label_b: SDR_CLEARANCE_OUT_OF_RANGE, nothing read, every count (area too) 0, every
+ *     float and double the canonical NaN, the pixel coordinates -1.  Otherwise `plane` outside
+ *     [0, P) or a record without SDR_PLANE_OK: SDR_CLEARANCE_NO_PLANE, the maps are not read, area
+ *     is the region's, the other counts 0, the floats NaN, the pixel coordinates -1.
+ *   - Member of set S (S = A with label_a, S = B with label_b): a pixel of the rectangle that passes
+ *     the relief's steps 1 to 5 with S's label (mask, validity, float XYZ, h, hf, X / Y / Z finite
+ *     and fabsf(hf) < 1048576.0f), then h_lo <= hf && hf <= h_hi (float comparisons, the
+ *     footprint's band).  n_a and n_b count the members.
+ *   - Point of a member at (x, y): the window [y - radius, y + radius] x [x - radius, x + radius]
+ *     clipped to the RECTANGLE (not the image); the disparities (as step 2 reads them) of the
+ *     window's pixels that are members of the same set, in the window's row-major order; fewer than
+ *     min_count of them: no point.  Otherwise d_med is their lower median, element (n - 1) / 2 in
+ *     ascending order (equal values in window order: the ruler's selection), XYZ the float
+ *     reprojection of (x, y, d_med) (step 3's formula), and the member has a point iff X, Y and Z
+ *     are finite.  m_a and m_b count the points.  With radius 0 and min_count 1 a member's point
+ *     is its own.
+ *   - Pair (p a point of A, q a point of B): v = q - p per component in float;
+ *     s = (v0*v0 + v1*v1) + v2*v2 in double from the float v, no contraction (sdr_measure_disp's
+ *     distance expression; never NaN, as the points are finite; it may be +inf).
+ *   - Result: the pair of the smallest s, ties to the smaller index v * rw + u of p, then of q.
+ *     distance = sqrt(s); along = (nx*v0 + ny*v1) + nz*v2 in double with the record's normal
+ *     (positive: B's point is farther from the plane on the camera's side); across =
+ *     sqrt(max(s - along*along, 0.0)) with max(t, 0.0) = t > 0.0 ? t : 0.0 (0.0 for a NaN t, which
+ *     an infinite s can give).  xa, ya, xb, yb are the two pixels in image coordinates, p_a, p_b
+ *     the two points, d_a, d_b their d_med.
+ *   - m_a == 0 or m_b == 0: SDR_CLEARANCE_EMPTY, the counts as found, the floats NaN, the pixel
+ *     coordinates -1.  Otherwise SDR_CLEARANCE_VALID.  Every NaN written is the canonical quiet NaN.
+ *   - frame, plane, label_a and label_b of a record are its query's in every case. */
+typedef struct sdr_clearance_query { /* 32 bytes */
+    int32_t frame, x0, y0, x1, y1; /* the rectangle, the plane fit's region rule */
+    int32_t plane;                 /* index into the P plane records */
+    int32_t label_a, label_b;      /* 0..255 each, different */
+} sdr_clearance_query;
+
+typedef struct sdr_clearance_params { /* 64 bytes */
+    float min_disp, conf_min;      /* the ruler's validity rule */
+    float h_lo, h_hi;              /* members have h_lo <= hf <= h_hi; not NaN, h_lo <= h_hi */
+    int32_t radius;                /* the same-set sample's window radius, 0..4 */
+    int32_t min_count;             /* same-set pixels a window must hold, >= 1 */
+    int32_t reserved[10];          /* 0 */
+} sdr_clearance_params;
+
+enum {
+    SDR_CLEARANCE_VALID = 1, SDR_CLEARANCE_OUT_OF_RANGE = 2, SDR_CLEARANCE_NO_PLANE = 4,
+    SDR_CLEARANCE_EMPTY = 8
+};
+
+/* the most queries a call takes (they run one behind another on the stream) */
+enum { SDR_CLEARANCE_MAX_QUERIES = 64 };
+
+/* The record shares its name with the host entry point below, as sdr_plane_distance does: it has no
+ * typedef and is written `struct sdr_clearance`. */
+struct sdr_clearance { /* 128 bytes */
+    double distance;               /* sqrt(s) of the closest pair, Q's units */
+    double along, across;          /* its parts along the plane's normal (signed) and in the plane */
+    float p_a[3], p_b[3];          /* the two points */
+    float d_a, d_b;                /* their median disparities (px) */
+    int32_t xa, ya, xb, yb;        /* their pixels, image coordinates; -1 without a pair */
+    int32_t area, n_a, n_b, m_a, m_b;
+    int32_t frame, plane, label_a, label_b; /* the query's */
+    uint32_t flags;                /* SDR_CLEARANCE_* */
+    int32_t reserved[4];           /* 0 */
+};
+
+/* {-1.0f, 0.0f, -1048576.0f, 1048576.0f, 0, 1, {0, ...}} */
+void sdr_clearance_params_default(sdr_clearance_params* p);
+/* K queries on device maps against the P records of d_planes (the maps, planes and labels arguments
+ * are sdr_plane_relief_device's; d_labels must not be NULL), asynchronous on `stream`: a fixed
+ * sequence of launches a query, one query behind another, with no host synchronisation and no
+ * workgroup that waits on another (a sweep that marks the members, a sweep that samples them and
+ * appends the points to one list a set, the bounds of every 256 points, all pairs of the two lists
+ * block against block, the record).  A pair of blocks is skipped only where a lower bound of its s
+ * from the blocks' bounds is strictly greater than an s already found, so the record is the brute
+ * force's.  d_out: K struct sdr_clearance.  K == 0 is SDR_OK with no launch.  The queries are device
+ * memory, so the stream-ordered scratch is sized for the frame and serves every query in turn:
+ * 21 bytes a pixel of width * height (a mark, a median and a 16-byte point), 304 bytes for every
+ * 256 pixels (two blocks' bounds and sixteen candidates) and at most 2 KB of state and alignment:
+ * 5.1 MB for 640 x 360, whatever K and whatever the rectangles; 372 MB for the largest map the host
+ * admits (2^24 pixels), which a caller with such maps has to have free.
+ * The host refuses, before any device call and with SDR_ERR_ARG: what sdr_plane_relief_device
+ * refuses of the maps and planes, a null d_labels, K < 0 or K > SDR_CLEARANCE_MAX_QUERIES, h_lo
+ * or h_hi NaN or h_lo > h_hi, a radius outside 0..4, min_count < 1, a non-zero reserved field of
+ * the parameters. */
+int sdr_clearance_device(const void* d_disp, int disp_type, size_t stride, size_t frame_stride,
+                         int width, int height, int nframes, const float* d_conf,
+                         const uint8_t* d_labels, const double Q[16],
+                         const sdr_clearance_params* params, const sdr_plane* d_planes, int P,
+                         const sdr_clearance_query* d_queries, int K, struct sdr_clearance* d_out,
+                         void* stream);
+/* Measurement hook, process-wide and safe to call from any thread (an atomic the entries read once
+ * a call).  SDR_DEBUG_CLEARANCE_PRUNE: 0 makes every block pair run, any other value (the default)
+ * lets the calls that start afterwards skip block pairs as above; the records do not change, only
+ * the time does (scripts/clearance_bench.py).  An unknown knob is SDR_ERR_ARG. */
+enum { SDR_DEBUG_CLEARANCE_PRUNE = 1 };
+int sdr_clearance_debug_knob(int knob, int value);
+/* Host-pointer version (synchronous; per-thread persistent device buffers as sdr_fit_planes). */
+int sdr_clearance(const void* disp, int disp_type, size_t stride, size_t frame_stride, int width,
+                  int height, int nframes, const float* conf, const uint8_t* labels,
+                  const double Q[16], const sdr_clearance_params* params, const sdr_plane* planes,
+                  int P, const sdr_clearance_query* queries, int K, struct sdr_clearance* out);
+
 /* Bytes of device scratch the handle holds for the given frame shape (for capacity planning);
  * 0 when compute would refuse the shape or parameters.  sdr_sgbm_scratch_bytes is the CV_8UC1
  * figure, sdr_sgbm_scratch_bytes_cn takes the channel count (1 or 3: colour input holds three

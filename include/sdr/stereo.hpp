@@ -450,6 +450,7 @@ using Relief = sdr_relief;
 using Footprint = sdr_footprint;
 using Object = sdr_object;
 using ObjectScan = sdr_object_scan;
+using Clearance = struct sdr_clearance;  // the C record shares its name with a function
 struct Point {
     int x = 0, y = 0;
 };
@@ -714,6 +715,41 @@ public:
                          int label = -1, const Mat* conf = nullptr) const {
         return find_objects(disparity, std::vector<Plane>{plane}, sdr_relief_query{0, a.x, a.y, b.x, b.y, 0, label, 0},
                             labels_in, conf);
+    }
+    // The clearance of pairs of labelled things {frame, x0, y0, x1, y1, plane, label_a, label_b}
+    // (sdr.h, "the clearance of two labelled things"): the smallest 3-D distance between a point of
+    // label_a and a point of label_b of `labels` (the map find_objects or find_planes returned), each
+    // pixel's point the ruler's sample (radius, min_count) over the pixels of its own label, with the
+    // two pixels and points and the distance's parts along and across the plane's normal; h_lo / h_hi:
+    // only the pixels whose height above the plane lies between them
+    std::vector<Clearance> clearance(const Mat& disparity, const std::vector<Plane>& planes,
+                                     const std::vector<sdr_clearance_query>& pairs, const Mat& labels,
+                                     const Mat* conf = nullptr, float h_lo = -1048576.0f,
+                                     float h_hi = 1048576.0f) const {
+        check_maps(disparity, conf, "clearance");
+        check_labels(disparity, &labels);
+        const size_t es = elem_size(disparity.type);
+        sdr_clearance_params cp;
+        sdr_clearance_params_default(&cp);
+        cp.min_disp = p_.min_disp;
+        cp.conf_min = p_.conf_min;
+        cp.h_lo = h_lo;
+        cp.h_hi = h_hi;
+        cp.radius = p_.radius;
+        cp.min_count = p_.min_count;
+        std::vector<Clearance> out(pairs.size());
+        check(sdr_clearance(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16,
+                            disparity.step / es, disparity.step / es * disparity.rows, disparity.cols, disparity.rows,
+                            1, conf ? conf->ptr<float>(0) : nullptr, labels.data, q_, &cp,
+                            planes.empty() ? nullptr : planes.data(), (int)planes.size(),
+                            pairs.empty() ? nullptr : pairs.data(), (int)pairs.size(),
+                            out.empty() ? nullptr : out.data()));
+        return out;
+    }
+    Clearance clearance(const Mat& disparity, const Plane& plane, Point a, Point b, const Mat& labels, int label_a,
+                        int label_b, const Mat* conf = nullptr) const {
+        return clearance(disparity, std::vector<Plane>{plane},
+                         {sdr_clearance_query{0, a.x, a.y, b.x, b.y, 0, label_a, label_b}}, labels, conf)[0];
     }
 
 private:

@@ -23,6 +23,8 @@ from .ruler import (  # noqa: F401
     footprint_length_width,
     OBJECT_CUT, OBJECT_DTYPE, OBJECT_SCAN_DTYPE, OBJECT_VALID, OBJECTS_EMPTY, OBJECTS_NO_PLANE, OBJECTS_OUT_OF_RANGE,
     OBJECTS_TRUNCATED, OBJECTS_VALID,
+    CLEARANCE_DTYPE, CLEARANCE_EMPTY, CLEARANCE_NO_PLANE, CLEARANCE_OUT_OF_RANGE, CLEARANCE_VALID,
+    as_clearance_queries,
 )
 from .stereo_disparity import StereoDisparity  # noqa: F401
 
@@ -41,4 +43,6 @@ __all__ = [
     "FOOTPRINT_CLIPPED", "footprint_length_width",
     "OBJECT_DTYPE", "OBJECT_SCAN_DTYPE", "OBJECT_VALID", "OBJECT_CUT", "OBJECTS_VALID", "OBJECTS_OUT_OF_RANGE",
     "OBJECTS_NO_PLANE", "OBJECTS_EMPTY", "OBJECTS_TRUNCATED",
+    "CLEARANCE_DTYPE", "CLEARANCE_VALID", "CLEARANCE_OUT_OF_RANGE", "CLEARANCE_NO_PLANE", "CLEARANCE_EMPTY",
+    "as_clearance_queries",
 ]

@@ -248,6 +248,31 @@ class ObjectScan(ctypes.Structure):
                [("reserved", ctypes.c_int32 * 4)]
 
 
+class ClearanceQuery(ctypes.Structure):
+    """sdr_clearance_query (32 bytes)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("frame", "x0", "y0", "x1", "y1", "plane", "label_a", "label_b")]
+
+
+class ClearanceParams(ctypes.Structure):
+    """sdr_clearance_params (64 bytes)."""
+    _fields_ = [(n, ctypes.c_float) for n in ("min_disp", "conf_min", "h_lo", "h_hi")] + \
+               [("radius", ctypes.c_int32), ("min_count", ctypes.c_int32), ("reserved", ctypes.c_int32 * 10)]
+
+
+class Clearance(ctypes.Structure):
+    """sdr_clearance (128 bytes)."""
+    _fields_ = [("distance", ctypes.c_double), ("along", ctypes.c_double), ("across", ctypes.c_double),
+                ("p_a", ctypes.c_float * 3), ("p_b", ctypes.c_float * 3), ("d_a", ctypes.c_float),
+                ("d_b", ctypes.c_float)] + \
+               [(n, ctypes.c_int32) for n in ("xa", "ya", "xb", "yb", "area", "n_a", "n_b", "m_a", "m_b", "frame",
+                                              "plane", "label_a", "label_b")] + \
+               [("flags", ctypes.c_uint32), ("reserved", ctypes.c_int32 * 4)]
+
+
+CLEARANCE_MAX_QUERIES = 64  # SDR_CLEARANCE_MAX_QUERIES
+DEBUG_CLEARANCE_PRUNE = 1   # SDR_DEBUG_CLEARANCE_PRUNE (sdr_clearance_debug_knob)
+
+
 _lib = None
 _path = LIB_PATH
 
@@ -402,6 +427,12 @@ SIGNATURES = [
                                      _c.POINTER(ObjectParams), _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     ("sdr_find_objects", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _vp, _c.POINTER(_c.c_double),
                               _c.POINTER(ObjectParams), _vp, _i, _vp, _vp, _vp, _vp]),
+    ("sdr_clearance_params_default", None, [_c.POINTER(ClearanceParams)]),
+    ("sdr_clearance_device", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _vp, _c.POINTER(_c.c_double),
+                                  _c.POINTER(ClearanceParams), _vp, _i, _vp, _i, _vp, _vp]),
+    ("sdr_clearance", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _vp, _c.POINTER(_c.c_double),
+                           _c.POINTER(ClearanceParams), _vp, _i, _vp, _i, _vp]),
+    ("sdr_clearance_debug_knob", _i, [_i, _i]),
     ("sdr_build_id", _c.c_char_p, []),
     ("sdr_last_error", _c.c_char_p, []),
     ("sdr_abi_version", _i, []),

@@ -2,7 +2,7 @@
 // how high each lies above the query's plane (steps 1 to 5 of "the relief of a region" in
 // include/sdr/sdr.h, which the footprint takes over), and the frame of a sweep that gives a
 // workgroup a slice of a rectangle's row-major order.  The relief, the footprint, the objects, the
-// plane fit and the plane search are written on it.
+// clearance, the plane fit and the plane search are written on it.
 #pragma once
 #include "sdr_ruler_shared.hpp"
 
@@ -40,12 +40,12 @@ __device__ __forceinline__ bool query_plane(const sdr_plane* __restrict__ planes
     return true;
 }
 
-// one refusal for the four record types
+// one refusal for the five record types
 static_assert(SDR_RELIEF_OUT_OF_RANGE == 2 && SDR_FOOTPRINT_OUT_OF_RANGE == 2 && SDR_PDIST_OUT_OF_RANGE == 2 &&
-                  SDR_OBJECTS_OUT_OF_RANGE == 2,
+                  SDR_OBJECTS_OUT_OF_RANGE == 2 && SDR_CLEARANCE_OUT_OF_RANGE == 2,
               "the OUT_OF_RANGE flags share a value");
 static_assert(SDR_RELIEF_NO_PLANE == 4 && SDR_FOOTPRINT_NO_PLANE == 4 && SDR_PDIST_NO_PLANE == 4 &&
-                  SDR_OBJECTS_NO_PLANE == 4,
+                  SDR_OBJECTS_NO_PLANE == 4 && SDR_CLEARANCE_NO_PLANE == 4,
               "the NO_PLANE flags share a value");
 constexpr uint32_t kRegionOutOfRange = 2, kRegionNoPlane = 4;
 

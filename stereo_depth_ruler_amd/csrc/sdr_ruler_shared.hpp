@@ -1,5 +1,5 @@
 // sdr_ruler_shared.hpp -- what the ruler's units (sdr_ruler.hip, sdr_plane.hip, sdr_relief.hip,
-// sdr_footprint.hip, sdr_objects.hip) share: on the device the disparity loads, the canonical NaN, the wave
+// sdr_footprint.hip, sdr_objects.hip, sdr_clearance.hip) share: on the device the disparity loads, the canonical NaN, the wave
 // reductions, a rectangle's range test and the ruler's sample; on the host (ruler_host) the argument
 // guards, the Q and disparity-type plumbing of a launch, the per-thread persistent buffers (held in
 // sdr_host.hpp's ThreadState) and the staged host-pointer call over them (HostCall).  The region
@@ -74,9 +74,39 @@ struct RulerSample {
     bool valid;
 };
 
-// One sample by one wave (every lane returns the same values): the window's <= 81 values two a
-// lane, the valid mask as two ballots, the lower median by counting, for each lane's values, the
-// valid values that sort before them (ties by window index), then the reprojection.
+// The selection of one sample by one wave (every lane returns the same values): a window's <= 81
+// values two a lane (value j = lane + 64 * k of the window's cnt), `ok` which of them count; the
+// number that count, and with at least max(min_count, 1) of them *dmed their lower median, by
+// counting, for each lane's values, the values that sort before them (ties by window index).
+__device__ __forceinline__ int ruler_select(const float (&v)[2], const bool (&ok)[2], int cnt, int min_count,
+                                            int lane, float* dmed) {
+    const unsigned long long m0 = __ballot(ok[0]), m1 = __ballot(ok[1]);
+    const int n = __popcll(m0) + __popcll(m1);
+    if (n < min_count || n == 0) return n;
+    int rank[2] = {0, 0};
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        unsigned long long m = k ? m1 : m0;
+        while (m) {
+            const int c = __builtin_ctzll(m);
+            m &= m - 1;
+            const float vc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v[k]), c));
+            const int jc = c + 64 * k;
+            rank[0] += (vc < v[0] || (vc == v[0] && jc < lane)) ? 1 : 0;
+            if (cnt > 64) rank[1] += (vc < v[1] || (vc == v[1] && jc < lane + 64)) ? 1 : 0;  // radius 4 only
+        }
+    }
+    const int want = (n - 1) >> 1;
+    const unsigned long long h0 = __ballot(ok[0] && rank[0] == want);
+    const unsigned long long h1 = __ballot(ok[1] && rank[1] == want);
+    // exactly one valid value has rank `want`
+    *dmed = h0 ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v[0]), __builtin_ctzll(h0)))
+               : __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v[1]), __builtin_ctzll(h1 | (1ull << 63))));
+    return n;
+}
+
+// One sample by one wave (every lane returns the same values): the window's valid values, their
+// selection (above), then the reprojection.
 template <typename T>
 __device__ __forceinline__ RulerSample ruler_sample(const T* __restrict__ disp, size_t stride,
                                                     const float* __restrict__ conf, int W, int H,
@@ -103,31 +133,12 @@ __device__ __forceinline__ RulerSample ruler_sample(const T* __restrict__ disp, 
             ok[k] = isfinite(d) && d > P.min_disp && (!conf || c >= P.conf_min);
         }
     }
-    const unsigned long long m0 = __ballot(ok[0]), m1 = __ballot(ok[1]);
     RulerSample s;
-    s.n = __popcll(m0) + __popcll(m1);
     s.d = s.xyz[0] = s.xyz[1] = s.xyz[2] = ruler_nan();
     s.valid = false;
+    float dmed = 0.f;
+    s.n = ruler_select(v, ok, cnt, P.min_count, lane, &dmed);
     if (s.n < P.min_count || s.n == 0) return s;
-    int rank[2] = {0, 0};
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        unsigned long long m = k ? m1 : m0;
-        while (m) {
-            const int c = __builtin_ctzll(m);
-            m &= m - 1;
-            const float vc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v[k]), c));
-            const int jc = c + 64 * k;
-            rank[0] += (vc < v[0] || (vc == v[0] && jc < lane)) ? 1 : 0;
-            if (cnt > 64) rank[1] += (vc < v[1] || (vc == v[1] && jc < lane + 64)) ? 1 : 0;  // radius 4 only
-        }
-    }
-    const int want = (s.n - 1) >> 1;
-    const unsigned long long h0 = __ballot(ok[0] && rank[0] == want);
-    const unsigned long long h1 = __ballot(ok[1] && rank[1] == want);
-    // exactly one valid value has rank `want`
-    const float dmed = h0 ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v[0]), __builtin_ctzll(h0)))
-                          : __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v[1]), __builtin_ctzll(h1 | (1ull << 63))));
     s.d = dmed;
     reproject_px(Q, x, y, (double)dmed, 0.0, 0, s.xyz);
     s.valid = finite3(s.xyz);
@@ -302,19 +313,19 @@ struct HostCall {
 };
 
 // The host-pointer form of an entry that measures regions against plane records (the relief, the
-// footprint): `check` is the entry's parameter guard, `entry` its device form.
-template <typename Params, typename Rec, typename Check, typename Entry>
+// footprint, the clearance): `check` is the entry's parameter guard, `entry` its device form.
+template <typename Params, typename Query, typename Rec, typename Check, typename Entry>
 inline int region_host_call(Check check, Entry entry, const void* disp, int disp_type, size_t stride,
                             size_t frame_stride, int W, int H, int F, const float* conf, const uint8_t* labels,
                             const double* Q, const Params* params, const sdr_plane* planes, int P,
-                            const sdr_relief_query* queries, int K, Rec* out) {
+                            const Query* queries, int K, Rec* out) {
     int rc = check_plane_maps(disp, disp_type, stride, frame_stride, W, H, F, Q, params, queries, K, out);
     if (rc || (rc = check(params, planes, P))) return rc;
     if (K == 0) return SDR_OK;
     HostCall c;
     const HostCall::Maps m = c.maps(disp, disp_type, stride, frame_stride, W, H, F, conf);
     const sdr_plane* d_planes = c.input(c.S->planes, planes, (size_t)P);
-    const sdr_relief_query* d_queries = c.input(c.S->rows, queries, (size_t)K);
+    const Query* d_queries = c.input(c.S->rows, queries, (size_t)K);
     const uint8_t* d_labels = c.input(c.S->labels, labels, (size_t)F * W * H);
     const auto s_out = c.output(out, (size_t)K);
     if ((rc = c.ready())) return rc;

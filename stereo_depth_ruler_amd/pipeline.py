@@ -181,6 +181,15 @@ class LiveLoop:
                                               min_pixels=min_pixels, max_objects=max_objects, stream=stream,
                                               labels_out=labels_out)
 
+    def clearance(self, planes, pairs, stream, labels, h_range=None):
+        """Ruler.clearance_device on the same frames, chained like relief(): `labels` the tensor
+        find_objects returned, pairs rows {frame, x0, y0, x1, y1, plane, label_a, label_b}: the
+        (K, 128) clearance records tensor, no synchronise in between."""
+        if self.ruler is None:
+            raise RuntimeError("LiveLoop was built without ruler=")
+        return self.ruler.clearance_device(self.disp, planes, pairs, labels, conf=self.conf, h_range=h_range,
+                                           stream=stream)
+
     def close(self):
         for o in (self.left, self.right, self.wls, self.display):
             if o is not None:

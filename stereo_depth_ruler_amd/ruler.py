@@ -30,6 +30,11 @@ the definition is in include/sdr/sdr.h).
   union-find across tile borders, csrc/sdr_objects.hip), the largest first, as records (pixels,
   bounding box, centroid sums, height sums and extremes) and as a label map that ``relief`` and
   ``footprint`` take: a mug, a ball or a box seen corner-on gets a label though it is no plane.
+* ``Ruler.clearance(disparity, planes, pairs, labels)`` measures the gap between two of those things:
+  the smallest 3-D distance between a point of one label and a point of another, each pixel's point
+  the ruler's sample taken over its own label's pixels (``radius``, ``min_count``), found by all pairs
+  block against block with an exact prune on the blocks' bounds (csrc/sdr_clearance.hip), with the two
+  pixels and points where it is attained and its parts along and across the floor's normal.
 * ``Ruler.find_planes(disparity, region=None)`` finds a region's dominant planes without a prior (a
   box on a table in front of a wall): rounds of seeded three-point hypotheses scored in exact
   integer arithmetic on the pixels no earlier plane has claimed, the winner refitted as
@@ -50,7 +55,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (DISP_F32, DISP_S16, FootprintParams, ObjectParams, PlaneParams, PlaneSearchParams, ReliefParams,
+from ._lib import (DISP_F32, DISP_S16, ClearanceParams, FootprintParams, ObjectParams, PlaneParams, PlaneSearchParams, ReliefParams,
                    RulerParams, SDRError, check, lib)
 from .sgbm import _Q, _is_cuda, torch
 
@@ -120,6 +125,16 @@ OBJECTS_VALID, OBJECTS_OUT_OF_RANGE, OBJECTS_NO_PLANE, OBJECTS_EMPTY, OBJECTS_TR
 OBJECT_VALID, OBJECT_CUT = 1, 2
 
 
+# sdr_clearance and its flags (SDR_CLEARANCE_*)
+CLEARANCE_DTYPE = np.dtype([
+    ("distance", "<f8"), ("along", "<f8"), ("across", "<f8"), ("p_a", "<f4", (3,)), ("p_b", "<f4", (3,)),
+    ("d_a", "<f4"), ("d_b", "<f4"), ("xa", "<i4"), ("ya", "<i4"), ("xb", "<i4"), ("yb", "<i4"), ("area", "<i4"),
+    ("n_a", "<i4"), ("n_b", "<i4"), ("m_a", "<i4"), ("m_b", "<i4"), ("frame", "<i4"), ("plane", "<i4"),
+    ("label_a", "<i4"), ("label_b", "<i4"), ("flags", "<u4"), ("reserved", "<i4", (4,))])
+assert CLEARANCE_DTYPE.itemsize == 128
+CLEARANCE_VALID, CLEARANCE_OUT_OF_RANGE, CLEARANCE_NO_PLANE, CLEARANCE_EMPTY = 1, 2, 4, 8
+
+
 def footprint_length_width(records):
     """(length, width) = (max, min) of each FOOTPRINT_DTYPE record's sides (NaN without a rectangle)."""
     side = np.asarray(records)["side"]
@@ -142,6 +157,20 @@ def as_relief_queries(regions) -> np.ndarray:
     q[:, 6] = -1
     q[:, :r.shape[1]] = r
     return q
+
+
+def as_clearance_queries(pairs) -> np.ndarray:
+    """(K, 8) int32 {frame, x0, y0, x1, y1, plane, label_a, label_b} from rows of 8 / one tuple."""
+    r = np.asarray(pairs)
+    if r.size == 0:
+        return np.zeros((0, 8), np.int32)
+    if r.ndim == 1:
+        r = r[None, :]
+    if r.ndim != 2 or r.shape[1] != 8:
+        raise SDRError(-1, "pairs must be (K, 8) {frame, x0, y0, x1, y1, plane, label_a, label_b}")
+    if r.dtype.kind not in "iu":
+        raise SDRError(-1, "pairs must be integers")
+    return np.ascontiguousarray(r, dtype=np.int32)
 
 
 def as_queries(points) -> np.ndarray:
@@ -182,6 +211,7 @@ def as_segments(segments) -> np.ndarray:
 _RECTANGLES = (as_segments, "regions", 5)
 _POINTS = (as_queries, "points", 4)
 _REGIONS = (as_relief_queries, "regions", 8)
+_PAIRS = (as_clearance_queries, "pairs", 8)
 _NO_LABELS = object()  # an entry that takes no label map
 
 
@@ -823,6 +853,43 @@ class Ruler:
                 pl.data_ptr() if P else None, P, q.data_ptr(), rec.data_ptr(), scan.data_ptr(),
                 lab.data_ptr() if lab is not None else None, ctypes.c_void_p(s.cuda_stream)))
         return rec, scan, lab
+
+    # ---- the clearance of two labelled things (sdr.h, "the clearance of two labelled things") ----
+    def _clearance_params(self, h_range) -> ClearanceParams:
+        lo, hi = (-1048576.0, 1048576.0) if h_range is None else (float(h_range[0]), float(h_range[1]))
+        if np.isnan(lo) or np.isnan(hi) or lo > hi:
+            raise SDRError(-1, "h_range must be (lo, hi) with lo <= hi, neither NaN")
+        if not 0 <= self.radius <= 4 or self.min_count < 1:
+            raise SDRError(-1, "the clearance takes a ruler with radius in 0..4 and min_count >= 1")
+        return ClearanceParams(self.min_disp, self.conf_min, lo, hi, self.radius, self.min_count)
+
+    def clearance(self, disparity, planes, pairs, labels, conf=None, h_range=None):
+        """The gaps between K pairs of labelled things: a CLEARANCE_DTYPE array of K.  planes: as
+        relief() takes them; pairs: rows {frame, x0, y0, x1, y1, plane, label_a, label_b}; labels: the
+        uint8 (H, W) / (F, H, W) map find_objects or find_planes returns (required).  Each pixel of a
+        label has for its point the ruler's sample (radius, min_count) over the pixels of the same
+        label; a record holds the smallest 3-D distance between a point of label_a and a point of
+        label_b, the two pixels and points, and the distance's parts along the plane's normal and in
+        the plane; h_range: (lo, hi), only pixels whose height above the plane lies in it."""
+        if labels is None:
+            raise SDRError(-1, "clearance needs a label map")
+        if _is_cuda(disparity):
+            out = self.clearance_device(disparity, planes, pairs, labels, conf, h_range)
+            return out.cpu().numpy().reshape(-1).view(CLEARANCE_DTYPE)
+        return self._plane_queries(lib().sdr_clearance, lambda: self._clearance_params(h_range), CLEARANCE_DTYPE,
+                                   disparity, planes, pairs, _PAIRS, conf, labels)
+
+    def clearance_device(self, disparity, planes, pairs, labels, conf=None, h_range=None, stream=None):
+        """Enqueues the clearances on `stream` (default: the current stream) and returns a uint8
+        tensor (K, 128) without synchronising (view its host copy as CLEARANCE_DTYPE).  planes and
+        labels: as find_planes_device and find_objects_device return them (the floor, the objects and
+        their gap then chain on one stream with no host round trip) or host arrays; pairs: host rows
+        or a CUDA int32 (K, 8)."""
+        if labels is None:
+            raise SDRError(-1, "clearance needs a label map")
+        return self._plane_queries_device("clearance_device", lib().sdr_clearance_device,
+                                          lambda: self._clearance_params(h_range), 128, disparity, planes, pairs,
+                                          _PAIRS, conf, stream, labels)
 
     # ---- XYZ-map mode (the reference's measurement) ----
     def measure_xyz(self, depth_map, segments):
