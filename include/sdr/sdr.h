@@ -1242,8 +1242,14 @@ int sdr_sgbm_last_status(sdr_sgbm* h);
  * and a large value keeps it off them, on any GPU.  Both forms compute the same maps, so the knob
  * changes which kernel runs and nothing else.  It never reaches the sweeps' tiling, the cost
  * kernels' row bands or anything else that sizes a resident grid: a sweep sized for compute units
- * that are not there would wait on a workgroup that never runs. */
-enum { SDR_DEBUG_SWEEP_SPIN = 1, SDR_DEBUG_PLAN_CUS = 2 };
+ * that are not there would wait on a workgroup that never runs.
+ * SDR_DEBUG_COST_ROWS: the rows of a row band of the one-pass cost kernels (k_cost, the census cost
+ * kernel); <= 0: the launcher's own rule, the tallest band that fills the device's resident-block
+ * slots in one pass and at least 4 rows -- which gives every small frame 4-row bands, whose row loop
+ * never completes an unrolled trip.  Any height >= 1 computes the same volume (a cost block waits on
+ * no other block), so the knob moves the band borders and nothing else; sdr_sgbm_last_plan reports
+ * the height and the band count a launch took.  The two-pass generic cost ignores it. */
+enum { SDR_DEBUG_SWEEP_SPIN = 1, SDR_DEBUG_PLAN_CUS = 2, SDR_DEBUG_COST_ROWS = 3 };
 int sdr_sgbm_debug_knob(sdr_sgbm* h, int knob, int value);
 
 /* Which kernels a matcher call launches: the record the launchers themselves switch on, so a test
@@ -1282,7 +1288,10 @@ typedef struct sdr_sgbm_launches {
     int32_t post;
     int32_t paths_chains, south_chains; /* chains of the two launches, all frames (a sweep: 0 south) */
     int32_t cus;                        /* the compute units the two thresholds were taken at */
-    int32_t reserved[2];
+    /* the last one-pass cost launch: rows of a main row band and the number of main bands (3WAY's
+     * stripe-start bands come on top).  0 for the generic cost, and from sdr_sgbm_plan_query: the
+     * launcher's rule needs the device's occupancy query */
+    int32_t cost_rows, cost_bands;
 } sdr_sgbm_launches;
 /* The launches of one call of nframes frames of width x height x channels under p and the cost
  * type.  cus = 0 asks the current device for its compute units; any other value keeps the call off
@@ -1319,7 +1328,14 @@ int sdr_stream_probe_ex(int device, size_t bytes, int iters, double* gbs3);
  * when the LR check cannot fire), 6 = MODE_SGBM_3WAY's stripe-start cost rows [F][stripes][rows][W1][D]
  * s16 (rows = the largest stripe's count); stage 1 holds values only in the matched columns,
  * 7 = the census descriptors [F][2][H][W] u64 (index 0: the frame's left-role image, 1: its
- * right-role image; an error when the last compute used SDR_COST_BT).
+ * right-role image; an error when the last compute used SDR_COST_BT),
+ * 8 = the prefilter's left operands [F][H][W][3*cn] u32, per channel c the words 3c..3c+2 of 16-bit
+ * halves {sobel | sobel_lo << 16} {sobel_hi | raw << 16} {raw_lo | raw_hi << 16} (lo / hi: the
+ * Birchfield-Tomasi envelope of the value and its two half-sample neighbours), 9 = the right
+ * operands [F][3*cn][H][W] u64, per channel c the planes 3c..3c+2 of words q(x) | q(max(x-1, 0)) << 16
+ * with q = {sobel | sobel_lo << 32} {sobel_hi | raw << 32} {raw_lo | raw_hi << 32} (stages 8 and 9:
+ * an error when the last compute used the census cost; a frame of a paired batch's second half
+ * holds its roles swapped).
  *
  * Stage 4, the path-cost records, pixel-interleaved in the summation order E, W, [N,] SE, SW[, NE,
  * NW] (R = P-1 directions; frames R*H*W1*D*2 bytes apart in either format):

@@ -90,13 +90,15 @@ class SgbmLaunches(ctypes.Structure):
         "paths_r12", "south_kernel", "south_dpl", "south_pad", "south_np", "south_tc", "south_r12",
         "sweep_dw", "sweep_pad")] + \
                [("sweep_nslots", ctypes.c_int32 * 2), ("sweep_ntiles", ctypes.c_int32 * 2)] + \
-               [(n, ctypes.c_int32) for n in ("post", "paths_chains", "south_chains", "cus")] + \
-               [("reserved", ctypes.c_int32 * 2)]
+               [(n, ctypes.c_int32) for n in ("post", "paths_chains", "south_chains", "cus", "cost_rows",
+                                                "cost_bands")]
 
     def as_dict(self):
         """{"cost": (family, NR, K, CN), "paths": (family, DPL, PAD, R12), "south": ("k_south_wta",
         DPL, PAD, NP, TC, R12) or ("sweep", DW, PAD) or ("none",), "sweep_shape": ((nslots, ntiles)
-        of the down pass, of the up pass), "post": route, "paths_chains", "south_chains", "cus"}."""
+        of the down pass, of the up pass), "post": route, "paths_chains", "south_chains", "cus",
+        "cost_rows", "cost_bands" (the rows of a row band and the main bands of a one-pass cost
+        launch; 0 from a plan query)}."""
         paths = (PATHS_KERNELS[self.paths_kernel],)
         if self.paths_kernel:
             paths += (self.paths_dpl, bool(self.paths_pad), bool(self.paths_r12))
@@ -110,7 +112,8 @@ class SgbmLaunches(ctypes.Structure):
                 "paths": paths, "south": south,
                 "sweep_shape": tuple((self.sweep_nslots[i], self.sweep_ntiles[i]) for i in range(2)),
                 "post": POST_ROUTES[self.post], "paths_chains": self.paths_chains,
-                "south_chains": self.south_chains, "cus": self.cus}
+                "south_chains": self.south_chains, "cus": self.cus, "cost_rows": self.cost_rows,
+                "cost_bands": self.cost_bands}
 
 
 def sgbm_plan(params, w, h, nframes=1, channels=1, cost=0, cus=0):

@@ -340,7 +340,7 @@ __global__ __launch_bounds__((CensusCfg<NR, K>::NT)) void k_cost_census(Geometry
 }
 
 template <int NR, int K>
-static void launch_census_t(const Geometry& g, CostArgs a, int F, hipStream_t st) {
+static CostBands launch_census_t(const Geometry& g, CostArgs a, int F, hipStream_t st) {
     using Cfg = CensusCfg<NR, K>;
     const int rows = max(a.row_end - a.row_begin, 0);
     const size_t lds = Cfg::lds_bytes(g.D);
@@ -363,21 +363,19 @@ static void launch_census_t(const Geometry& g, CostArgs a, int F, hipStream_t st
     if (rows == 0) a.TY = 1;
     dim3 grid(colblocks, (rows + a.TY - 1) / a.TY + a.naux, F);
     hipLaunchKernelGGL((k_cost_census<NR, K>), grid, dim3(Cfg::NT), lds, st, g, a);
+    return {a.TY, (rows + a.TY - 1) / a.TY};
 }
 
 // SH2 <= 5 and D <= 256 (check_frame refuses the rest under the census cost)
-void launch_cost_census(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st) {
-    if (a.row_end <= a.row_begin && a.naux == 0) return;
+CostBands launch_cost_census(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st) {
+    if (a.row_end <= a.row_begin && a.naux == 0) return {0, 0};
     const int NR = c.nr;
     const bool k2 = c.k == 2;
-#define SDR_CENSUS(NRV)                                              \
-    case NRV:                                                        \
-        if (k2) launch_census_t<NRV, 2>(g, a, F, st);                \
-        else launch_census_t<NRV, 1>(g, a, F, st);                   \
-        break;
+#define SDR_CENSUS(NRV) \
+    case NRV: return k2 ? launch_census_t<NRV, 2>(g, a, F, st) : launch_census_t<NRV, 1>(g, a, F, st);
     switch (NR) {
         SDR_CENSUS(1) SDR_CENSUS(3) SDR_CENSUS(5) SDR_CENSUS(7) SDR_CENSUS(9) SDR_CENSUS(11)
-        default: break;
+        default: return kNoCostKernel;
     }
 #undef SDR_CENSUS
 }

@@ -174,19 +174,16 @@ CostChoice cost_choice(const Geometry& g, int cn, bool census) {
     return {census ? SDR_SGBM_COST_CENSUS : SDR_SGBM_COST_ONE_PASS, 2 * g.SH2 + 1, g.D > 128 ? 2 : 1, cn};
 }
 
-void launch_cost(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st) {
-    if (a.row_end <= a.row_begin && a.naux == 0) return;
+CostBands launch_cost(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st) {
+    if (a.row_end <= a.row_begin && a.naux == 0) return {0, 0};
     if (c.cn == 3) return launch_cost_cn3(g, a, c, F, st);
     const int NR = c.nr;
     const bool k2 = c.k == 2;
-#define SDR_COST(NRV)                                                 \
-    case NRV:                                                         \
-        if (k2) launch_cost_t<NRV, 2, 1>(g, a, F, st);                \
-        else launch_cost_t<NRV, 1, 1>(g, a, F, st);                   \
-        break;
+#define SDR_COST(NRV) \
+    case NRV: return k2 ? launch_cost_t<NRV, 2, 1>(g, a, F, st) : launch_cost_t<NRV, 1, 1>(g, a, F, st);
     switch (NR) {
         SDR_COST(1) SDR_COST(3) SDR_COST(5) SDR_COST(7) SDR_COST(9) SDR_COST(11)
-        default: break;
+        default: return kNoCostKernel;
     }
 #undef SDR_COST
 }

@@ -6,18 +6,19 @@
 
 namespace sdr {
 
-void launch_cost_cn3_k2(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st);
+CostBands launch_cost_cn3_k2(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st);
 
-void launch_cost_cn3(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st) {
+// No blockSize 11: check_channels refuses it for three channels at every preFilterCap and P2 (the
+// block term alone, 3 * 93 * 121, passes the int16 cost range), so the plan never names it.
+CostBands launch_cost_cn3(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st) {
     if (c.k == 2) return launch_cost_cn3_k2(g, a, c, F, st);
     switch (c.nr) {
-        case 1: launch_cost_t<1, 1, 3>(g, a, F, st); break;
-        case 3: launch_cost_t<3, 1, 3>(g, a, F, st); break;
-        case 5: launch_cost_t<5, 1, 3>(g, a, F, st); break;
-        case 7: launch_cost_t<7, 1, 3>(g, a, F, st); break;
-        case 9: launch_cost_t<9, 1, 3>(g, a, F, st); break;
-        case 11: launch_cost_t<11, 1, 3>(g, a, F, st); break;
-        default: break;
+        case 1: return launch_cost_t<1, 1, 3>(g, a, F, st);
+        case 3: return launch_cost_t<3, 1, 3>(g, a, F, st);
+        case 5: return launch_cost_t<5, 1, 3>(g, a, F, st);
+        case 7: return launch_cost_t<7, 1, 3>(g, a, F, st);
+        case 9: return launch_cost_t<9, 1, 3>(g, a, F, st);
+        default: return kNoCostKernel;
     }
 }
 

@@ -4,15 +4,14 @@
 
 namespace sdr {
 
-void launch_cost_cn3_k2(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st) {
+CostBands launch_cost_cn3_k2(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st) {
     switch (c.nr) {
-        case 1: launch_cost_t<1, 2, 3>(g, a, F, st); break;
-        case 3: launch_cost_t<3, 2, 3>(g, a, F, st); break;
-        case 5: launch_cost_t<5, 2, 3>(g, a, F, st); break;
-        case 7: launch_cost_t<7, 2, 3>(g, a, F, st); break;
-        case 9: launch_cost_t<9, 2, 3>(g, a, F, st); break;
-        case 11: launch_cost_t<11, 2, 3>(g, a, F, st); break;
-        default: break;
+        case 1: return launch_cost_t<1, 2, 3>(g, a, F, st);
+        case 3: return launch_cost_t<3, 2, 3>(g, a, F, st);
+        case 5: return launch_cost_t<5, 2, 3>(g, a, F, st);
+        case 7: return launch_cost_t<7, 2, 3>(g, a, F, st);
+        case 9: return launch_cost_t<9, 2, 3>(g, a, F, st);
+        default: return kNoCostKernel;  // blockSize 11: refused by the plan (sdr_cost3.hip)
     }
 }
 

@@ -357,7 +357,7 @@ __global__ __launch_bounds__((CostCfg<NR, K, CN>::NT)) void k_cost(Geometry g, C
 }
 
 template <int NR, int K, int CN>
-static void launch_cost_t(const Geometry& g, CostArgs a, int F, hipStream_t st) {
+static CostBands launch_cost_t(const Geometry& g, CostArgs a, int F, hipStream_t st) {
     using Cfg = CostCfg<NR, K, CN>;
     const int rows = max(a.row_end - a.row_begin, 0);
     const size_t lds = Cfg::lds_bytes(g.D);
@@ -385,6 +385,7 @@ static void launch_cost_t(const Geometry& g, CostArgs a, int F, hipStream_t st) 
     if (rows == 0) a.TY = 1;
     dim3 grid(colblocks, (rows + a.TY - 1) / a.TY + a.naux, F);
     hipLaunchKernelGGL((k_cost<NR, K, CN>), grid, dim3(Cfg::NT), lds, st, g, a);
+    return {a.TY, (rows + a.TY - 1) / a.TY};
 }
 
 }  // namespace sdr

@@ -122,8 +122,9 @@ sdr::Planes stage_planes(sdr_sgbm* h, const Plan& p, const Io& io) {
     return pl;
 }
 
-// The cost volume, with the 3WAY stripe-start rows as extra row bands of the same launch.
-void stage_cost(sdr_sgbm* h, const Plan& p, const sdr::Planes& planes) {
+// The cost volume, with the 3WAY stripe-start rows as extra row bands of the same launch.  Returns
+// the rows a band and the main bands of a one-pass launch ({0, 0}: the generic cost, or no launch).
+sdr::CostBands stage_cost(sdr_sgbm* h, const Plan& p, const sdr::Planes& planes) {
     const sdr::Geometry& g = p.e.g;
     sdr::CostArgs ca{};
     ca.pl = planes;
@@ -136,7 +137,8 @@ void stage_cost(sdr_sgbm* h, const Plan& p, const sdr::Planes& planes) {
     ca.ylim = std::max(g.H - 1 - g.SH2, 0);
     // the full-DP cost buffers of MODE_HH and MODE_HH4 keep P2 on the rows the running sum never reaches
     ca.hh_bottom = p.e.mode == SDR_MODE_HH || p.e.mode == SDR_MODE_HH4;
-    ca.TY = 0;  // sized by launch_cost for one full pass of resident blocks
+    // 0: sized by the launcher for one full pass of resident blocks (SDR_DEBUG_COST_ROWS: a test's own)
+    ca.TY = h->cost_rows;
     ca.sink = (int16_t*)h->sink.p;
     ca.naux = 0;
     ca.aux_fstride = p.aux_fstride;
@@ -154,9 +156,12 @@ void stage_cost(sdr_sgbm* h, const Plan& p, const sdr::Planes& planes) {
     // blockSize 13..17 (within the int16 domain) or D > 256: the two-pass cost through the
     // idle L records
     const sdr::CostChoice cc = sdr::cost_choice(g, p.cn, p.census());
-    if (cc.kernel == SDR_SGBM_COST_CENSUS) sdr::launch_cost_census(g, ca, cc, p.F, h->stream);
-    else if (cc.kernel == SDR_SGBM_COST_GENERIC) sdr::launch_cost_generic(g, ca, p.F, (uint32_t*)h->Lr.p, h->stream);
-    else sdr::launch_cost(g, ca, cc, p.F, h->stream);
+    if (cc.kernel == SDR_SGBM_COST_CENSUS) return sdr::launch_cost_census(g, ca, cc, p.F, h->stream);
+    if (cc.kernel == SDR_SGBM_COST_GENERIC) {
+        sdr::launch_cost_generic(g, ca, p.F, (uint32_t*)h->Lr.p, h->stream);
+        return {0, 0};
+    }
+    return sdr::launch_cost(g, ca, cc, p.F, h->stream);
 }
 
 void add_dir(sdr::PathLaunch& pl, int dir, int nch, int H, int16_t* out) {
@@ -420,13 +425,15 @@ int enqueue_compute(sdr_sgbm* h, Plan& planned, const Io& io, int16_t** final_di
     if (p.sweep && (rc = size_sweep(h, p))) return rc;
 
     const sdr::Planes planes = stage_planes(h, p, io);
-    stage_cost(h, p, planes);
+    const sdr::CostBands cb = stage_cost(h, p, planes);
+    if (cb.rows < 0) return fail(SDR_ERR_LIMIT, "no cost kernel is compiled for this plan's block size and channels");
     if (h->timing) SDR_HIP(hipEventRecord(h->ev[1], st));
 
     sdr::PathLaunch pls{}, plS{};
     // (the debug knob's compute units reach the two chain-count thresholds, nothing else)
     const int cus = h->plan_cus > 0 ? h->plan_cus : sdr::device_cus();
     const PathChoices ch = plan_launches({vol_C(h, p), vol_L(h, p), vol_Caux(h, p)}, p, pls, plS, h->rec16, cus);
+    p.launches.cost_rows = cb.rows, p.launches.cost_bands = cb.bands;
     { KTimer kt(h, SDR_KERNEL_PATHS); sdr::launch_paths(p.e.g, pls, ch.pc, p.F, st); }
     if (p.sweep && (rc = stage_sweep(h, p))) return rc;
     if (h->timing) SDR_HIP(hipEventRecord(h->ev[2], st));

@@ -273,6 +273,10 @@ int sdr_sgbm_debug_knob(sdr_sgbm* h, int knob, int value) {
         h->plan_cus = value > 0 ? value : 0;
         return SDR_OK;
     }
+    if (knob == SDR_DEBUG_COST_ROWS) {
+        h->cost_rows = value > 0 ? value : 0;
+        return SDR_OK;
+    }
     if (knob != SDR_DEBUG_SWEEP_SPIN) return set_error(SDR_ERR_ARG, "unknown knob");
     h->sweep_spin = value > 0 ? value : sdr::kSweepSpin;
     return SDR_OK;
@@ -282,9 +286,16 @@ int sdr_sgbm_debug_stage(const sdr_sgbm* h, int stage, void* dst, size_t bytes) 
     if (!h || !dst) return set_error(SDR_ERR_ARG, "null argument");
     const Buf* b = stage == 0 ? &h->C : stage == 1 ? &h->draw : stage == 2 ? &h->dlr
                  : stage == 3 ? &h->dfin : stage == 4 ? &h->Lr : stage == 5 ? &h->keys2
-                 : stage == 6 ? &h->Caux : stage == 7 ? &h->planesR : nullptr;
+                 : stage == 6 ? &h->Caux : stage == 7 ? &h->planesR : stage == 8 ? &h->planesL
+                 : stage == 9 ? &h->planesR : nullptr;
     if (!b) return set_error(SDR_ERR_ARG, "bad stage");
     const sdr::Plan& pl = h->last;
+    if (stage == 8 || stage == 9) {
+        // the prefilter's operands: the census cost keeps its descriptors in the same buffer
+        if (pl.census()) return set_error(SDR_ERR_ARG, "the last compute used the census cost");
+        const size_t have = (size_t)pl.F * 3 * pl.px * pl.cn * (stage == 8 ? 4 : 8);
+        if (bytes > have) return set_error(SDR_ERR_ARG, "stage buffer smaller than requested");
+    }
     if (stage == 7 && !pl.census_bytes()) return set_error(SDR_ERR_ARG, "the last compute did not use the census cost");
     if (stage == 7 && bytes > pl.census_bytes()) return set_error(SDR_ERR_ARG, "stage buffer smaller than requested");
     // front slack (the L records' is P-1 times C's)

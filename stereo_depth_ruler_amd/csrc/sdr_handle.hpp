@@ -30,6 +30,9 @@ struct sdr_sgbm {
     // with (0: the device's).  Read by enqueue_compute's plan_launches alone -- never by anything
     // that sizes a resident grid (the sweeps' tiling, the cost kernels' row bands)
     int plan_cus = 0;
+    // debug knob SDR_DEBUG_COST_ROWS: the rows of a row band of the one-pass cost kernels (0: the
+    // launcher's own rule).  The kernels take any band height; nothing here waits on a resident grid
+    int cost_rows = 0;
     // SDR_PATH_REC=16 in the environment when the handle was created: int16 path-cost records
     // always (A/B and tests; the default takes 12-bit records where enqueue_compute can)
     bool rec16 = false;

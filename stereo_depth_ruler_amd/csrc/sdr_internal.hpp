@@ -275,13 +275,21 @@ struct CostChoice {
     int kernel, nr, k, cn;
 };
 CostChoice cost_choice(const Geometry& g, int cn, bool census);
+// What a one-pass cost launcher chose: the rows of a main band (CostArgs::TY, the caller's when it
+// gave one > 0, else the tallest band that fills the chip in one pass of resident blocks) and the
+// number of main bands; {0, 0} when there was nothing to launch.  rows < 0: the choice names no
+// compiled instantiation and nothing was launched -- an engine error, which enqueue_compute reports.
+struct CostBands {
+    int rows, bands;
+};
+constexpr CostBands kNoCostKernel{-1, 0};
 // (kernel SDR_SGBM_COST_ONE_PASS)
-void launch_cost(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st);
+CostBands launch_cost(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st);
 // blockSize > 11 (SH2 > 5) or D > 256 (sdr_cost_generic.hip): two passes through a scratch volume h1 of
 // cost_generic_scratch_bytes (the L-record buffer, idle until the path kernels)
 size_t cost_generic_scratch_bytes(const Geometry& g, int F);
 void launch_cost_generic(const Geometry& g, const CostArgs& a, int F, uint32_t* h1, hipStream_t st);
-void launch_cost_cn3(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st);  // cn == 3
+CostBands launch_cost_cn3(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st);  // cn == 3
 // ---- census matching cost (sdr_census.hip; the definition: sdr.h SDR_COST_CENSUS_9X7) ----
 // 9x7 census descriptors of both images of F frames, desc u64 [F][2][H][W] (index 0: the frame's
 // left-role image, 1: its right-role image; frames >= split take the images swapped); d2fill as
@@ -291,7 +299,7 @@ void launch_census(const uint8_t* L, const uint8_t* R, size_t stride, size_t fst
 // launch_cost with the Hamming distance of the descriptors as the pixel cost (SH2 <= 5, D <= 256):
 // a.pl.L / a.pl.R are the left-role / right-role descriptor planes, u64 [H][W] a frame, frames
 // pl.fstrideL / pl.fstrideR u64 elements apart
-void launch_cost_census(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st);
+CostBands launch_cost_census(const Geometry& g, const CostArgs& a, const CostChoice& c, int F, hipStream_t st);
 void launch_paths(const Geometry& g, const PathLaunch& pl, const PathsChoice& c, int F, hipStream_t st);
 void launch_median3(const int16_t* src, int16_t* dst, int W, int H, int F, hipStream_t st);
 // median of the LR-checked map (computed per tile from the WTA map and the right-view keys)

@@ -36,7 +36,7 @@ COST_BT, COST_CENSUS = 0, 1
 (KERNEL_PREFILTER, KERNEL_COST, KERNEL_PATHS, KERNEL_WTA_LR, KERNEL_MEDIAN, KERNEL_SPECKLE,
  KERNEL_REPROJECT, KERNEL_LR_CHECK, KERNEL_SWEEP, KERNEL_WLS_PREP, KERNEL_FGS, KERNEL_WLS_FINAL,
  KERNEL_SWEEP_DOWN, KERNEL_FGS_COEF) = range(14)
-DEBUG_SWEEP_SPIN, DEBUG_PLAN_CUS = 1, 2  # sdr_sgbm_debug_knob
+DEBUG_SWEEP_SPIN, DEBUG_PLAN_CUS, DEBUG_COST_ROWS = 1, 2, 3  # sdr_sgbm_debug_knob
 
 
 def _is_cuda(x) -> bool:
@@ -280,7 +280,8 @@ class StereoSGBM:
 
     def debug_stage(self, stage: int, shape, dtype):
         """Copy an internal buffer of the last compute (0 C, 1 raw WTA, 2 LR, 3 final, 4 path costs,
-        5 disp2 keys, 6 3WAY stripe-start cost rows, 7 census descriptors)."""
+        5 disp2 keys, 6 3WAY stripe-start cost rows, 7 census descriptors, 8 / 9 the prefilter's
+        left pack / right pair planes)."""
         out = np.empty(shape, dtype)
         check(lib().sdr_sgbm_debug_stage(self._h, int(stage), out.ctypes.data, out.nbytes))
         return out
@@ -297,7 +298,8 @@ class StereoSGBM:
 
     def set_debug_knob(self, knob: int, value: int):
         """Test hook (sdr_sgbm_debug_knob): DEBUG_SWEEP_SPIN = polls before a sweep wait gives up;
-        DEBUG_PLAN_CUS = the compute units the path launches' chain-count thresholds count with."""
+        DEBUG_PLAN_CUS = the compute units the path launches' chain-count thresholds count with;
+        DEBUG_COST_ROWS = the rows of a row band of the one-pass cost kernels (0: the launcher's rule)."""
         check(lib().sdr_sgbm_debug_knob(self._h, int(knob), int(value)))
 
     def last_plan(self) -> dict:

@@ -308,6 +308,101 @@ def stripe_rows_ref(L, R, minD, D, bs, P2, nstripes):
     return out, (len(st), max(x[3] for x in st))
 
 
+# ---- row bands ----------------------------------------------------------------------------
+# k_cost_census and the BT cost's k_cost share one launch rule and one row loop: a block owns a band
+# of TY rows and walks n = tlast - tfirst + 1 + 2 SH2 virtual rows in a loop unrolled by U = 2 NR,
+# n // U full trips and a tail of n % U rows.  The launcher's own TY (the tallest band that fills the
+# device in one pass, at least 4) gives every small frame 4-row bands; the debug knob
+# SDR_DEBUG_COST_ROWS sets it instead.
+
+def is_hh(mode):
+    return mode in (SGM_HH, SGM_HH4)
+
+
+BAND_CLASSES = ("n<U", "n==U", "n==U+1", "n==3U-1", "n>=3U", "short_last", "straddles_ylim", "frozen",
+                "hh_straddles_yl", "hh_p2_only", "TY1", "one_band")
+# blockSize 1 has no frozen and no P2 rows (SH2 = 0: ylim = H - 1, yl = H)
+BAND_CLASSES_BS1 = tuple(c for c in BAND_CLASSES if c not in ("straddles_ylim", "frozen", "hh_straddles_yl",
+                                                              "hh_p2_only"))
+
+def band_shape(cls, nr):
+    """(TY, H, mode) of the entry built for a band class: a band clear of the frozen rows walks
+    n = TY + 2 SH2 = TY + NR - 1 virtual rows, and U = 2 NR."""
+    s = nr // 2
+    if cls == "n<U":
+        ty = nr if nr > 1 else 1
+        return ty, 3 * ty + s + 2, SGM_SGBM
+    if cls in ("n==U", "n==U+1", "n==3U-1", "n>=3U"):
+        ty = {"n==U": nr + 1, "n==U+1": nr + 2, "n==3U-1": 5 * nr, "n>=3U": 5 * nr + 3}[cls]
+        return ty, ty + s + 3, SGM_3WAY if cls == "n==U+1" else SGM_SGBM
+    if cls == "short_last":
+        return 4, 13, SGM_SGBM
+    if cls == "straddles_ylim":
+        return s + 3, 2 * (s + 3), SGM_SGBM
+    if cls == "frozen":
+        return (1 if s == 1 else 2), 2 * s + 6, SGM_3WAY
+    if cls == "hh_straddles_yl":
+        return s + 2, 2 * (s + 2), SGM_HH
+    if cls == "hh_p2_only":
+        return 1, 2 * s + 4, SGM_HH4
+    if cls == "TY1":
+        return 1, s + 4, SGM_SGBM
+    assert cls == "one_band"
+    return nr + 4, nr + 4, SGM_HH4
+
+
+def bands_of(c, mode=None, ty=None):
+    """The main row bands of a one-pass launch of c under band height ty, as the kernel derives
+    them: [(ty0, ty1, trips, tail, classes)] -- trips and tail of the row loop unrolled by U = 2 NR
+    (None for a block that returns before its first barrier)."""
+    mode = c.mode if mode is None else mode
+    ty = c.ty if ty is None else ty
+    H, s, nr = c.H, c.bs // 2, c.bs
+    U, ylim, hh = 2 * nr, max(H - 1 - s, 0), is_hh(mode)
+    nb = (H + ty - 1) // ty
+    out = []
+    for by in range(nb):
+        ty0, ty1 = by * ty, min(by * ty + ty, H)
+        yl = max(ty0, min(ty1, max(1, H - s))) if hh else ty1
+        cls = set()
+        if ty == 1:
+            cls.add("TY1")
+        if nb == 1:
+            cls.add("one_band")
+        if nb > 1 and by == nb - 1 and ty1 - ty0 < ty:
+            cls.add("short_last")
+        if yl <= ty0:
+            out.append((ty0, ty1, None, None, cls | {"hh_p2_only"}))
+            continue
+        if hh and ty0 < yl < ty1:
+            cls.add("hh_straddles_yl")
+        if not hh and ty0 > ylim:
+            cls.add("frozen")
+        if not hh and ty0 <= ylim < ty1 - 1:
+            cls.add("straddles_ylim")
+        tfirst, tlast = min(ty0, ylim), min(yl - 1, ylim)
+        n = tlast - tfirst + 1 + 2 * s
+        trips, tail = n // U, n % U
+        cls.add("n<U" if trips == 0 else "n>=3U" if trips >= 3 else
+                "n==U" if (trips, tail) == (1, 0) else "n==U+1" if (trips, tail) == (1, 1) else
+                "n==3U-1" if (trips, tail) == (2, U - 1) else "other")
+        out.append((ty0, ty1, trips, tail, cls))
+    return out
+
+
+BAND_KERNELS = [(5, 1), (5, 2), (7, 1), (7, 2), (11, 1), (11, 2)]
+
+
+def _band(cls, nr, k):
+    ty, H, mode = band_shape(cls, nr)
+    c = _cost(f"band_{cls}__k_{nr}_{k}", nr, 16 if k == 1 else 144, 37 if k == 1 else 21, H, mode)
+    c.ty, c.cls = ty, cls
+    return c
+
+
+BAND_CASES = [_band(cls, nr, k) for nr, k in BAND_KERNELS for cls in BAND_CLASSES]
+
+
 # ---- end to end ---------------------------------------------------------------------------
 
 def random_cases(n, seed):

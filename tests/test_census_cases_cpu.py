@@ -326,3 +326,31 @@ def test_stripe_window_clamped_at_row_0_and_ylim_show_on_the_stripe_rows():
     # every case with rows of its own tells the clamp
     assert with_rows >= 40 and len(set(clamp0)) == with_rows
     assert ylim
+
+
+# ---- the row bands ------------------------------------------------------------------------
+
+def test_band_cases_reach_their_trips_and_tails():
+    """Every band class at NR 5, 7 and 11 and both K: the entry's band height (set through
+    SDR_DEBUG_COST_ROWS on the GPU) puts a band in the class it is named for, by the kernel's own
+    row count n = tlast - tfirst + 1 + 2 SH2 and its unroll U = 2 NR."""
+    assert {(c.bs, C.kernel_of(c.bs, c.D)[1]) for c in C.BAND_CASES} == set(C.BAND_KERNELS)
+    assert {nr for nr, k in C.BAND_KERNELS} >= {5, 7, 11} and {k for nr, k in C.BAND_KERNELS} == {1, 2}
+    for nr, k in C.BAND_KERNELS:
+        assert [c.cls for c in C.BAND_CASES if (c.bs, C.kernel_of(c.bs, c.D)[1]) == (nr, k)] == list(C.BAND_CLASSES)
+    for c in C.BAND_CASES:
+        assert c.H <= 80 and plan_bytes(c) > 0 and plan_bytes(c, SGM_HH) > 0, c.id
+        s, U, ylim = c.bs // 2, 2 * c.bs, max(c.H - 1 - c.bs // 2, 0)
+        bands = C.bands_of(c)
+        assert [b[:2] for b in bands] == [(y, min(y + c.ty, c.H)) for y in range(0, c.H, c.ty)]
+        assert any(c.cls in b[4] for b in bands), (c.id, bands)
+        for ty0, ty1, trips, tail, _ in bands:
+            yl = max(ty0, min(ty1, max(1, c.H - s))) if C.is_hh(c.mode) else ty1
+            if yl <= ty0:
+                assert trips is None
+                continue
+            assert (trips, tail) == divmod(min(yl - 1, ylim) - min(ty0, ylim) + 1 + 2 * s, U)
+        # under the launcher's own 4-row bands no block completes a trip
+        assert all(b[2] in (0, None) for b in C.bands_of(c, ty=4)), c.id
+    for nr in (5, 7, 11):
+        assert any(b[2] >= 3 for c in C.BAND_CASES if c.bs == nr for b in C.bands_of(c))

@@ -192,3 +192,33 @@ def test_paired_class_path_roles_and_volume():
     vol = sd.matcher.debug_stage(0, (2, h, W1, 80), np.int16)
     assert np.array_equal(vol[0], CR.census_cost_volume(sl, sr, 0, 80, 5, 2400, C.SGM_3WAY))
     assert np.array_equal(vol[1], CR.census_cost_volume(sr, sl, -79, 80, 5, 2400, C.SGM_3WAY))
+
+
+# ---- the row bands ------------------------------------------------------------------------
+
+@pytest.mark.parametrize("nr,k", C.BAND_KERNELS, ids=[f"k_{nr}_{k}" for nr, k in C.BAND_KERNELS])
+def test_cost_volume_under_every_band_class(nr, k):
+    """k_cost_census<NR, K> with the band height of every class of census_cases.BAND_CLASSES, set
+    through SDR_DEBUG_COST_ROWS: the volume equals the pin and the one the launcher's own band
+    height computes, and sdr_sgbm_last_plan reports the bands that ran."""
+    for c in [c for c in C.BAND_CASES if (c.bs, C.kernel_of(c.bs, c.D)[1]) == (nr, k)]:
+        pairs = C.cost_pairs(c)
+        swapped = [(R, L) for L, R in pairs]
+        m = sdr.StereoSGBM.create(*C.create_args(c), cost=CENSUS)
+        for mode in (c.mode, C.SGM_3WAY if C.is_hh(c.mode) else C.SGM_HH):
+            m.setMode(mode)
+            vols = []
+            for ty in (c.ty, 0):
+                m.set_debug_knob(sdr.sgbm.DEBUG_COST_ROWS, ty)
+                compute_frames(m, swapped)
+                compute_frames(m, pairs)
+                plan = m.last_plan()
+                rows = plan["cost_rows"]
+                assert plan["cost"] == ("census", nr, k, 1) and (rows == ty if ty else rows >= 4), (c.id, plan)
+                assert plan["cost_bands"] == (c.H + rows - 1) // rows, (c.id, plan)
+                vols.append(m.debug_stage(0, (1, c.H, c.W1, c.D), np.int16)[0])
+            ref = CR.census_cost_volume(*pairs[0], c.minD, c.D, c.bs, c.P2, mode)
+            bad = vols[0] != ref
+            assert not bad.any(), f"{c.id} mode {mode}: {bad.sum()} cells differ, first {np.argwhere(bad)[0]}"
+            assert np.array_equal(vols[0], vols[1]), (c.id, mode)
+        m.close()
