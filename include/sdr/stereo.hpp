@@ -475,12 +475,7 @@ public:
     std::vector<Measurement> measure(const Mat& disparity, const std::vector<sdr_segment>& segs,
                                      const Mat* conf = nullptr, std::vector<float>* profile = nullptr,
                                      int cap = 0) const {
-        if (disparity.type != CV_32FC1 && disparity.type != CV_16SC1)
-            throw Exception(SDR_ERR_TYPE, "measure expects a CV_32F or CV_16S disparity");
-        const size_t es = elem_size(disparity.type);
-        if (conf && (conf->type != CV_32FC1 || conf->rows != disparity.rows || conf->cols != disparity.cols ||
-                     conf->step != (size_t)conf->cols * 4))
-            throw Exception(SDR_ERR_TYPE, "conf must be a continuous CV_32F map of the disparity's size");
+        check_maps(disparity, conf, "measure");
         std::vector<Measurement> out(segs.size());
         sdr_ruler_params p = p_;
         float* prof = nullptr;
@@ -489,11 +484,8 @@ public:
             profile->assign(segs.size() * (size_t)cap * 4, std::numeric_limits<float>::quiet_NaN());
             prof = profile->empty() ? nullptr : profile->data();
         }
-        check(sdr_measure_disp(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16,
-                               disparity.step / es, disparity.step / es * disparity.rows, disparity.cols,
-                               disparity.rows, 1, conf ? conf->ptr<float>(0) : nullptr, q_, &p,
-                               segs.empty() ? nullptr : segs.data(), (int)segs.size(),
-                               out.empty() ? nullptr : out.data(), prof));
+        on_maps(sdr_measure_disp, disparity, conf, q_, &p, segs.empty() ? nullptr : segs.data(), (int)segs.size(),
+                out.empty() ? nullptr : out.data(), prof);
         return out;
     }
     Measurement measure(const Mat& disparity, Point a, Point b, const Mat* conf = nullptr) const {
@@ -519,7 +511,6 @@ public:
                                  const Mat* conf = nullptr, int iterations = 3, float inlier_px = 1.0f,
                                  int min_inliers = 16) const {
         check_maps(disparity, conf, "fit_plane");
-        const size_t es = elem_size(disparity.type);
         sdr_plane_params pp;
         sdr_plane_params_default(&pp);
         pp.iterations = iterations;
@@ -528,11 +519,8 @@ public:
         pp.min_disp = p_.min_disp;
         pp.conf_min = p_.conf_min;
         std::vector<Plane> out(regions.size());
-        check(sdr_fit_planes(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16,
-                             disparity.step / es, disparity.step / es * disparity.rows, disparity.cols,
-                             disparity.rows, 1, conf ? conf->ptr<float>(0) : nullptr, q_, &pp,
-                             regions.empty() ? nullptr : regions.data(), (int)regions.size(),
-                             out.empty() ? nullptr : out.data()));
+        on_maps(sdr_fit_planes, disparity, conf, q_, &pp, regions.empty() ? nullptr : regions.data(),
+                (int)regions.size(), out.empty() ? nullptr : out.data());
         return out;
     }
     Plane fit_plane(const Mat& disparity, Point a, Point b, const Mat* conf = nullptr, int iterations = 3,
@@ -553,7 +541,6 @@ public:
                             int hypotheses = 256, uint32_t seed = 0, int iterations = 3, float inlier_px = 1.0f,
                             int min_inliers = 64, bool with_labels = false) const {
         check_maps(disparity, conf, "find_planes");
-        const size_t es = elem_size(disparity.type);
         sdr_plane_search_params sp;
         sdr_plane_search_params_default(&sp);
         sp.fit.iterations = iterations;
@@ -571,11 +558,8 @@ public:
         if (with_labels) out.labels = Mat::pageable(disparity.rows, disparity.cols, CV_8UC1);
         const sdr_segment reg{0, a.x, a.y, b.x, b.y};
         int32_t count = 0;
-        check(sdr_find_planes(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16,
-                              disparity.step / es, disparity.step / es * disparity.rows, disparity.cols,
-                              disparity.rows, 1, conf ? conf->ptr<float>(0) : nullptr, q_, &sp, &reg,
-                              n ? out.planes.data() : nullptr, &count, n ? out.rounds.data() : nullptr,
-                              with_labels ? out.labels.data : nullptr));
+        on_maps(sdr_find_planes, disparity, conf, q_, &sp, &reg, n ? out.planes.data() : nullptr, &count,
+                n ? out.rounds.data() : nullptr, with_labels ? out.labels.data : nullptr);
         out.planes.resize((size_t)count);
         return out;
     }
@@ -585,17 +569,13 @@ public:
                                               const std::vector<sdr_plane_query>& points,
                                               const Mat* conf = nullptr) const {
         check_maps(disparity, conf, "plane_distance");
-        const size_t es = elem_size(disparity.type);
         sdr_ruler_params p = p_;
         p.profile = 0;
         p.profile_cap = 0;
         std::vector<PlaneDistance> out(points.size());
-        check(sdr_plane_distance(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16,
-                                 disparity.step / es, disparity.step / es * disparity.rows, disparity.cols,
-                                 disparity.rows, 1, conf ? conf->ptr<float>(0) : nullptr, q_, &p,
-                                 planes.empty() ? nullptr : planes.data(), (int)planes.size(),
-                                 points.empty() ? nullptr : points.data(), (int)points.size(),
-                                 out.empty() ? nullptr : out.data()));
+        on_maps(sdr_plane_distance, disparity, conf, q_, &p, planes.empty() ? nullptr : planes.data(),
+                (int)planes.size(), points.empty() ? nullptr : points.data(), (int)points.size(),
+                out.empty() ? nullptr : out.data());
         return out;
     }
     PlaneDistance plane_distance(const Mat& disparity, const Plane& plane, Point at,
@@ -613,7 +593,6 @@ public:
         check_maps(disparity, conf, "relief");
         check_labels(disparity, labels);
         if (quantiles.size() > 8) throw Exception(SDR_ERR_ARG, "relief takes at most 8 quantiles");
-        const size_t es = elem_size(disparity.type);
         sdr_relief_params rp;
         sdr_relief_params_default(&rp);
         rp.min_disp = p_.min_disp;
@@ -622,12 +601,9 @@ public:
         rp.nq = (int)quantiles.size();
         for (size_t j = 0; j < 8; j++) rp.permille[j] = j < quantiles.size() ? quantiles[j] : 0;
         std::vector<Relief> out(regions.size());
-        check(sdr_plane_relief(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16,
-                               disparity.step / es, disparity.step / es * disparity.rows, disparity.cols,
-                               disparity.rows, 1, conf ? conf->ptr<float>(0) : nullptr,
-                               labels ? labels->data : nullptr, q_, &rp, planes.empty() ? nullptr : planes.data(),
-                               (int)planes.size(), regions.empty() ? nullptr : regions.data(), (int)regions.size(),
-                               out.empty() ? nullptr : out.data()));
+        on_maps(sdr_plane_relief, disparity, conf, labels ? labels->data : nullptr, q_, &rp,
+                planes.empty() ? nullptr : planes.data(), (int)planes.size(),
+                regions.empty() ? nullptr : regions.data(), (int)regions.size(), out.empty() ? nullptr : out.data());
         return out;
     }
     Relief relief(const Mat& disparity, const Plane& plane, Point a, Point b, const Mat* labels = nullptr,
@@ -646,7 +622,6 @@ public:
                                      float h_lo = -1048576.0f, float h_hi = 1048576.0f) const {
         check_maps(disparity, conf, "footprint");
         check_labels(disparity, labels);
-        const size_t es = elem_size(disparity.type);
         sdr_footprint_params fp;
         sdr_footprint_params_default(&fp);
         fp.min_disp = p_.min_disp;
@@ -657,12 +632,9 @@ public:
         fp.h_lo = h_lo;
         fp.h_hi = h_hi;
         std::vector<Footprint> out(regions.size());
-        check(sdr_plane_footprint(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16,
-                                  disparity.step / es, disparity.step / es * disparity.rows, disparity.cols,
-                                  disparity.rows, 1, conf ? conf->ptr<float>(0) : nullptr,
-                                  labels ? labels->data : nullptr, q_, &fp, planes.empty() ? nullptr : planes.data(),
-                                  (int)planes.size(), regions.empty() ? nullptr : regions.data(),
-                                  (int)regions.size(), out.empty() ? nullptr : out.data()));
+        on_maps(sdr_plane_footprint, disparity, conf, labels ? labels->data : nullptr, q_, &fp,
+                planes.empty() ? nullptr : planes.data(), (int)planes.size(),
+                regions.empty() ? nullptr : regions.data(), (int)regions.size(), out.empty() ? nullptr : out.data());
         return out;
     }
     Footprint footprint(const Mat& disparity, const Plane& plane, Point a, Point b, const Mat* labels = nullptr,
@@ -687,7 +659,6 @@ public:
                          int max_objects = 16, bool with_labels = true) const {
         check_maps(disparity, conf, "find_objects");
         check_labels(disparity, labels_in);
-        const size_t es = elem_size(disparity.type);
         sdr_object_params op;
         sdr_object_params_default(&op);
         op.min_disp = p_.min_disp;
@@ -702,12 +673,9 @@ public:
         out.objects.resize(max_objects > 0 && max_objects <= 64 ? (size_t)max_objects : 1);
         std::memset(&out.scan, 0, sizeof out.scan);
         if (with_labels) out.labels = Mat::pageable(disparity.rows, disparity.cols, CV_8UC1);
-        check(sdr_find_objects(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16,
-                               disparity.step / es, disparity.step / es * disparity.rows, disparity.cols,
-                               disparity.rows, 1, conf ? conf->ptr<float>(0) : nullptr,
-                               labels_in ? labels_in->data : nullptr, q_, &op, planes.empty() ? nullptr : planes.data(),
-                               (int)planes.size(), &region, out.objects.data(), &out.scan,
-                               with_labels ? out.labels.data : nullptr));
+        on_maps(sdr_find_objects, disparity, conf, labels_in ? labels_in->data : nullptr, q_, &op,
+                planes.empty() ? nullptr : planes.data(), (int)planes.size(), &region, out.objects.data(), &out.scan,
+                with_labels ? out.labels.data : nullptr);
         out.objects.resize((size_t)out.scan.count);
         return out;
     }
@@ -728,7 +696,6 @@ public:
                                      float h_hi = 1048576.0f) const {
         check_maps(disparity, conf, "clearance");
         check_labels(disparity, &labels);
-        const size_t es = elem_size(disparity.type);
         sdr_clearance_params cp;
         sdr_clearance_params_default(&cp);
         cp.min_disp = p_.min_disp;
@@ -738,12 +705,9 @@ public:
         cp.radius = p_.radius;
         cp.min_count = p_.min_count;
         std::vector<Clearance> out(pairs.size());
-        check(sdr_clearance(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16,
-                            disparity.step / es, disparity.step / es * disparity.rows, disparity.cols, disparity.rows,
-                            1, conf ? conf->ptr<float>(0) : nullptr, labels.data, q_, &cp,
-                            planes.empty() ? nullptr : planes.data(), (int)planes.size(),
-                            pairs.empty() ? nullptr : pairs.data(), (int)pairs.size(),
-                            out.empty() ? nullptr : out.data()));
+        on_maps(sdr_clearance, disparity, conf, labels.data, q_, &cp, planes.empty() ? nullptr : planes.data(),
+                (int)planes.size(), pairs.empty() ? nullptr : pairs.data(), (int)pairs.size(),
+                out.empty() ? nullptr : out.data());
         return out;
     }
     Clearance clearance(const Mat& disparity, const Plane& plane, Point a, Point b, const Mat& labels, int label_a,
@@ -764,6 +728,14 @@ private:
         if (conf && (conf->type != CV_32FC1 || conf->rows != disparity.rows || conf->cols != disparity.cols ||
                      conf->step != (size_t)conf->cols * 4))
             throw Exception(SDR_ERR_TYPE, "conf must be a continuous CV_32F map of the disparity's size");
+    }
+    // entry(the maps' run of a one-frame call: data, type, strides, size, conf; then rest...), checked
+    template <typename Entry, typename... Rest>
+    static void on_maps(Entry entry, const Mat& disparity, const Mat* conf, Rest... rest) {
+        const size_t es = elem_size(disparity.type);
+        check(entry(disparity.data, disparity.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16, disparity.step / es,
+                    disparity.step / es * disparity.rows, disparity.cols, disparity.rows, 1,
+                    conf ? conf->ptr<float>(0) : nullptr, rest...));
     }
     double q_[16];
     sdr_ruler_params p_;

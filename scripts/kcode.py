@@ -1,9 +1,11 @@
-"""Device code of a built object, per kernel: python scripts/kcode.py OBJ [OBJ2]
+"""Device code of a built object, per kernel: python scripts/kcode.py [--by-name] OBJ [OBJ2]
 
 One object: for every kernel its size, the sha256 of its bytes in .text and the resources from the
 code object's metadata (VGPRs, AGPRs, SGPRs, scratch and LDS bytes), then the unit's .text and
 .rodata hashes.  Two objects (parent, child): the kernels whose bytes differ, with both resource
-lines, and whether the unit's sections are the same.  The code object is taken out of the host
+lines, and whether the unit's sections are the same.  --by-name pairs the kernels of two objects by
+name and template arguments without the parameter list (a change of a kernel's parameters changes
+its mangled name) and prints both resource lines of every kernel.  The code object is taken out of the host
 object with llvm-objcopy --dump-section .hip_fatbin and clang-offload-bundler --unbundle
 (profiles/engine_plan_refactor.md).
 """
@@ -62,7 +64,8 @@ def unit(obj):
             g = lambda k: (re.search(r"\." + k + r":\s+(\d+)", blk) or [None, "?"])[1]
             if name:
                 meta[name.group(1)] = (f"vgpr={g('vgpr_count')} agpr={g('agpr_count')} sgpr={g('sgpr_count')} "
-                                       f"scratch={g('private_segment_fixed_size')} lds={g('group_segment_fixed_size')}")
+                                       f"scratch={g('private_segment_fixed_size')} lds={g('group_segment_fixed_size')} "
+                                       f"spills={g('vgpr_spill_count')}v/{g('sgpr_spill_count')}s")
         ti, taddr, toff, _ = secs[".text"]
         for m in re.finditer(r"^\s*\d+:\s+([0-9a-f]+)\s+(\d+)\s+FUNC\s+\S+\s+\S+\s+(\d+)\s+(\S+)$",
                              run(f"{LLVM}/llvm-readelf", "-s", "--wide", co), re.M):
@@ -78,7 +81,34 @@ def demangle(names):
     return dict(zip(names, run(filt, *names).splitlines() if filt and names else names))
 
 
+def bare(demangled):
+    """A demangled kernel name without its parameter list: `void ns::k<float, 1>(...)` -> `ns::k<float, 1>`."""
+    depth, end = 0, len(demangled)
+    for i in range(len(demangled) - 1, -1, -1):  # the parenthesis that matches the last one
+        depth += {")": 1, "(": -1}.get(demangled[i], 0)
+        if depth == 0 and demangled[i] == "(":
+            end = i
+            break
+    return demangled[:end].split(" ", 1)[-1] if demangled.startswith("void ") else demangled[:end]
+
+
+def by_name(a, b):
+    dm = demangle(sorted(set(a["kernels"]) | set(b["kernels"])))
+    ka = {bare(dm[n]): v for n, v in a["kernels"].items()}
+    kb = {bare(dm[n]): v for n, v in b["kernels"].items()}
+    same = 0
+    for n in sorted(set(ka) | set(kb)):
+        x, y = ka.get(n), kb.get(n)
+        same += bool(x and y and x[:2] == y[:2])
+        print(n + ("  (identical)" if x and y and x[:2] == y[:2] else ""))
+        for tag, k in (("parent", x), ("child", y)):
+            print(f"    {tag:6s} " + (f"{k[0]:7d} bytes {k[1]} {k[2]}" if k else "absent"))
+    print(f"{same} of {len(set(ka) | set(kb))} kernels identical; code object {a['size']} -> {b['size']} bytes")
+
+
 def main():
+    if sys.argv[1] == "--by-name":
+        return by_name(unit(sys.argv[2]), unit(sys.argv[3]))
     a = unit(sys.argv[1])
     if len(sys.argv) == 2:
         dm = demangle(list(a["kernels"]))

@@ -69,39 +69,24 @@ __device__ __forceinline__ bool clr_before(unsigned long long s, int ip, int iq,
     return s < t || (s == t && (ip < jp || (ip == jp && iq < jq)));
 }
 
-// 0, or the flag that refuses the query without a read of the maps; the plane of one that runs
-__device__ __forceinline__ uint32_t clearance_refusal(const sdr_clearance_query& q, int W, int H, int F,
-                                                      const sdr_plane* __restrict__ planes, int NP, RegionPlane* pl) {
-    if (q.label_a < 0 || q.label_a > 255 || q.label_b < 0 || q.label_b > 255 || q.label_a == q.label_b)
-        return kRegionOutOfRange;
-    const sdr_relief_query r = {q.frame, q.x0, q.y0, q.x1, q.y1, q.plane, q.label_a, 0};
-    return region_refusal(r, W, H, F, true, planes, NP, pl);
-}
-__device__ __forceinline__ sdr_segment clearance_segment(const sdr_clearance_query& q) {
-    return sdr_segment{q.frame, q.x0, q.y0, q.x1, q.y1};
-}
-
 // Sweep 1, a workgroup a slice: mark[v * rw + u] = 1 for a member of A, 2 for a member of B, 0 for
 // the rest; the members' counts.  A refused query and a slice past the area leave at once.
 template <typename T>
 __global__ __launch_bounds__(kRegionThreads) void k_clr_mark(
-    const T* __restrict__ disp, size_t stride, size_t fstride, int W, int H, int F, const float* __restrict__ conf,
-    const uint8_t* __restrict__ labels, Q16 Q, sdr_clearance_params P, const sdr_plane* __restrict__ planes, int NP,
+    RegionMaps<T> maps, Q16 Q, sdr_clearance_params P, const sdr_plane* __restrict__ planes, int NP,
     const sdr_clearance_query* __restrict__ query, ClrState* __restrict__ S, uint8_t* __restrict__ mark) {
 #pragma clang fp contract(off)
     const sdr_clearance_query q = *query;
     RegionPlane pl;
-    if (clearance_refusal(q, W, H, F, planes, NP, &pl)) return;  // block-uniform
-    RegionSlice<T, const uint8_t> sl;
-    if (!region_slice(clearance_segment(q), disp, stride, fstride, W, H, conf, labels + (size_t)q.frame * H * W, &sl))
-        return;
+    RegionSlice<T> sl;
+    if (!query_slice(maps, planes, NP, q, &pl, &sl)) return;  // block-uniform
+    const int W = maps.W;
     int na = 0, nb = 0;
     sl.each([&](unsigned u, unsigned v) __attribute__((always_inline)) {
         const int l = sl.fl[(size_t)v * W + u];
         uint8_t m = 0;
         if (l == q.label_a || l == q.label_b) {
-            const RegionPix px = region_pixel(sl.fd, stride, sl.fc, sl.fl, W, Q, pl, P.min_disp, P.conf_min, l, sl.R.xs,
-                                              sl.R.ys, u, v);
+            const RegionPix px = region_pixel(sl, Q, pl, P.min_disp, P.conf_min, l, u, v);
             if (px.member && P.h_lo <= px.hf && px.hf <= P.h_hi) m = l == q.label_a ? 1 : 2;
         }
         mark[(size_t)v * sl.R.rw + u] = m;
@@ -122,8 +107,8 @@ __global__ __launch_bounds__(kRegionThreads) void k_clr_mark(
 // finish in; that order shows in no output.  dmed[v * rw + u]: a point's median.
 template <typename T>
 __global__ __launch_bounds__(kRegionThreads) void k_clr_sample(
-    const T* __restrict__ disp, size_t stride, size_t fstride, int W, int H, int F, Q16 Q, sdr_clearance_params P,
-    const sdr_plane* __restrict__ planes, int NP, const sdr_clearance_query* __restrict__ query,
+    RegionMaps<T> maps, Q16 Q, sdr_clearance_params P, const sdr_plane* __restrict__ planes, int NP,
+    const sdr_clearance_query* __restrict__ query,
     ClrState* __restrict__ S, const uint8_t* __restrict__ mark, float* __restrict__ dmed, ClrPoint* __restrict__ pts,
     int cap) {
 #pragma clang fp contract(off)
@@ -131,11 +116,9 @@ __global__ __launch_bounds__(kRegionThreads) void k_clr_sample(
     __shared__ int cnt[2], base[2];
     const sdr_clearance_query q = *query;
     RegionPlane pl;
-    if (clearance_refusal(q, W, H, F, planes, NP, &pl)) return;  // block-uniform
-    RegionSlice<T, const uint8_t> sl;
-    if (!region_slice(clearance_segment(q), disp, stride, fstride, W, H, (const float*)nullptr,
-                      (const uint8_t*)nullptr, &sl))
-        return;
+    RegionSlice<T> sl;
+    if (!query_slice(maps, planes, NP, q, &pl, &sl)) return;  // block-uniform
+    const size_t stride = maps.stride;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid < 2) cnt[tid] = 0;
     __syncthreads();
@@ -351,7 +334,7 @@ __global__ __launch_bounds__(kClrWave) void k_clr_pairs(ClrState* __restrict__ S
 
 // The record, one workgroup: the smallest of the workgroups' pairs in the result's order, its two
 // points again from their medians, the distance and its two parts.
-__global__ __launch_bounds__(kRegionThreads) void k_clr_finish(int W, int H, int F, Q16 Q,
+__global__ __launch_bounds__(kRegionThreads) void k_clr_finish(RegionDims dims, Q16 Q,
                                                                const sdr_plane* __restrict__ planes, int NP,
                                                                const sdr_clearance_query* __restrict__ query,
                                                                const ClrState* __restrict__ S,
@@ -363,7 +346,7 @@ __global__ __launch_bounds__(kRegionThreads) void k_clr_finish(int W, int H, int
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const sdr_clearance_query q = *query;
     RegionPlane pl;
-    uint32_t flags = clearance_refusal(q, W, H, F, planes, NP, &pl);
+    uint32_t flags = query_refusal(dims, planes, NP, q, &pl);
     const int ma = flags ? 0 : S->m[0], mb = flags ? 0 : S->m[1];
     if (!flags) flags = (ma == 0 || mb == 0) ? SDR_CLEARANCE_EMPTY : SDR_CLEARANCE_VALID;
     unsigned long long s = ~0ull;
@@ -395,7 +378,7 @@ __global__ __launch_bounds__(kRegionThreads) void k_clr_finish(int W, int H, int
     r.xa = r.ya = r.xb = r.yb = -1;
     r.area = r.n_a = r.n_b = r.m_a = r.m_b = 0;
     if (flags != SDR_CLEARANCE_OUT_OF_RANGE) {
-        const PlaneRect R = plane_rect(clearance_segment(q));
+        const PlaneRect R = plane_rect(region_segment(q));
         r.area = R.rw * R.rh;
         if (flags != SDR_CLEARANCE_NO_PLANE) {
             r.n_a = S->n[0], r.n_b = S->n[1];
@@ -505,24 +488,24 @@ int sdr_clearance_device(const void* d_disp, int disp_type, size_t stride, size_
     const unsigned slices = sdr::region_slices(W, H);
     const dim3 block(sdr::kRegionThreads), wave(sdr::kClrWave);
     hipError_t e = hipSuccess;
-    auto one = [&](auto* disp, int k) {
-        using T = disp_elem_t<decltype(disp)>;
+    auto one = [&](auto maps, int k) {
+        using T = disp_elem_t<decltype(maps)>;
         const sdr_clearance_query* qk = d_queries + k;
         // the state's first 16 bytes are the counts (0), the next 8 the bits of +inf
         if ((e = hipMemsetAsync(state, 0, sizeof(sdr::ClrState), st)) != hipSuccess) return;
         if ((e = hipMemsetD32Async((hipDeviceptr_t)((char*)state + 20), 0x7ff00000, 1, st)) != hipSuccess) return;
-        hipLaunchKernelGGL((sdr::k_clr_mark<T>), dim3(slices), block, 0, st, disp, stride, frame_stride, W, H, F, d_conf,
-                           d_labels, q, CP, d_planes, P, qk, state, mark);
-        hipLaunchKernelGGL((sdr::k_clr_sample<T>), dim3(slices), block, 0, st, disp, stride, frame_stride, W, H, F, q,
-                           CP, d_planes, P, qk, state, (const uint8_t*)mark, dmed, pts, cap);
+        hipLaunchKernelGGL((sdr::k_clr_mark<T>), dim3(slices), block, 0, st, maps, q, CP, d_planes, P, qk, state, mark);
+        hipLaunchKernelGGL((sdr::k_clr_sample<T>), dim3(slices), block, 0, st, maps, q, CP, d_planes, P, qk, state,
+                           (const uint8_t*)mark, dmed, pts, cap);
         hipLaunchKernelGGL(sdr::k_clr_bounds, dim3((unsigned)maxblocks, 2), wave, 0, st, (const sdr::ClrState*)state,
                            (const sdr::ClrPoint*)pts, cap, bounds, maxblocks);
         hipLaunchKernelGGL(sdr::k_clr_pairs, dim3((unsigned)maxblocks, sdr::kClrGroups), wave, 0, st, state, (const sdr::ClrPoint*)pts,
                            cap, (const sdr::ClrBounds*)bounds, maxblocks, prune, cand);
-        hipLaunchKernelGGL(sdr::k_clr_finish, dim3(1), block, 0, st, W, H, F, q, d_planes, P, qk,
+        hipLaunchKernelGGL(sdr::k_clr_finish, dim3(1), block, 0, st, maps.dims(), q, d_planes, P, qk,
                            (const sdr::ClrState*)state, (const float*)dmed, (const sdr::ClrCand*)cand, d_out + k);
     };
-    for (int k = 0; k < K && e == hipSuccess; k++) with_disp(disp_type, d_disp, [&](auto* disp) { one(disp, k); });
+    for (int k = 0; k < K && e == hipSuccess; k++)
+        with_maps(d_disp, disp_type, stride, frame_stride, W, H, F, d_conf, d_labels, [&](auto maps) { one(maps, k); });
     return sc.finish(e);
 }
 

@@ -69,8 +69,7 @@ struct FootState {
 static_assert(sizeof(FootState) == 128 + kFootDirs * 16, "FootState's layout");
 
 // Setup, a workgroup a query: the checks, the basis, the accumulators at their start values.
-__global__ __launch_bounds__(kFootFinish) void k_foot_setup(int W, int H, int F, int has_labels,
-                                                            const sdr_plane* __restrict__ planes, int NP,
+__global__ __launch_bounds__(kFootFinish) void k_foot_setup(RegionDims dims, const sdr_plane* __restrict__ planes, int NP,
                                                             const sdr_relief_query* __restrict__ queries,
                                                             FootState* __restrict__ states) {
 #pragma clang fp contract(off)
@@ -86,7 +85,7 @@ __global__ __launch_bounds__(kFootFinish) void k_foot_setup(int W, int H, int F,
     const sdr_relief_query q = queries[k];
     double es[3] = {0, 0, 0}, et[3] = {0, 0, 0};
     RegionPlane pl = {{0, 0, 0}, 0};
-    unsigned flags = region_refusal(q, W, H, F, has_labels != 0, planes, NP, &pl);
+    unsigned flags = query_refusal(dims, planes, NP, q, &pl);
     if (!flags) {
         const double* n = pl.n;
         double a, b, c;
@@ -129,12 +128,10 @@ struct FootPix {
 // Pixel (u, v) of the slice's region: the region rule's member, the band of heights, the cell.
 // Both sweeps repeat it: the same bits in each.
 template <typename T>
-__device__ __forceinline__ FootPix foot_pixel(const RegionSlice<T, const uint8_t>& sl, size_t stride, int W,
-                                              const Q16& Q, const FootBasis& B, const sdr_footprint_params& P,
-                                              int label, unsigned u, unsigned v) {
+__device__ __forceinline__ FootPix foot_pixel(const RegionSlice<T>& sl, const Q16& Q, const FootBasis& B,
+                                              const sdr_footprint_params& P, int label, unsigned u, unsigned v) {
 #pragma clang fp contract(off)
-    const RegionPix px = region_pixel(sl.fd, stride, sl.fc, sl.fl, W, Q, B.pl, P.min_disp, P.conf_min, label,
-                                      sl.R.xs, sl.R.ys, u, v);
+    const RegionPix px = region_pixel(sl, Q, B.pl, P.min_disp, P.conf_min, label, u, v);
     FootPix r = {px.masked, px.valid, false, 0, 0};
     if (!px.member) return r;
     if (!(P.h_lo <= px.hf && px.hf <= P.h_hi)) return r;
@@ -155,8 +152,7 @@ __device__ __forceinline__ FootPix foot_pixel(const RegionSlice<T, const uint8_t
 // A refused query and a slice past the area leave at once (block-uniform).
 template <typename T, int PASS>
 __global__ __launch_bounds__(kRegionThreads) void k_foot_sweep(
-    const T* __restrict__ disp, size_t stride, size_t fstride, int W, int H, int F, const float* __restrict__ conf,
-    const uint8_t* __restrict__ labels, Q16 Q, sdr_footprint_params P, const sdr_relief_query* __restrict__ queries,
+    RegionMaps<T> maps, Q16 Q, sdr_footprint_params P, const sdr_relief_query* __restrict__ queries,
     FootState* __restrict__ states, unsigned* __restrict__ grids) {
     __shared__ int red[kRegionWaves][8];
     const int k = blockIdx.y;
@@ -165,10 +161,8 @@ __global__ __launch_bounds__(kRegionThreads) void k_foot_sweep(
     if (S->flags) return;                    // block-uniform
     if (PASS == 2 && S->cnt[2] == 0) return;  // no member
     const sdr_relief_query q = queries[k];
-    RegionSlice<T, const uint8_t> sl;
-    if (!region_slice(region_segment(q), disp, stride, fstride, W, H, conf,
-                      labels ? labels + (size_t)q.frame * H * W : nullptr, &sl))
-        return;
+    RegionSlice<T> sl;
+    if (!region_cut(query_view(maps, q), &sl)) return;  // in range: S->flags
     const FootBasis B = S->b;
     const int si0 = PASS == 2 ? S->smin : 0, ti0 = PASS == 2 ? S->tmin : 0;  // pass 1 is complete
     const unsigned G = (unsigned)P.grid;
@@ -178,7 +172,7 @@ __global__ __launch_bounds__(kRegionThreads) void k_foot_sweep(
     int smin = INT_MAX, smax = INT_MIN, tmin = INT_MAX, tmax = INT_MIN;
     int outside = 0;
     sl.each([&](unsigned u, unsigned v) __attribute__((always_inline)) {
-        const FootPix px = foot_pixel(sl, stride, W, Q, B, P, q.label, u, v);
+        const FootPix px = foot_pixel(sl, Q, B, P, q.label, u, v);
         if (PASS == 1) {
             m[0] += px.masked ? 1 : 0;
             m[1] += px.valid ? 1 : 0;
@@ -479,22 +473,21 @@ int sdr_plane_footprint_device(const void* d_disp, int disp_type, size_t stride,
     const unsigned tiles = (unsigned)((G + sdr::kFootTile - 1) / sdr::kFootTile);
     const dim3 block(sdr::kRegionThreads), small(sdr::kFootFinish);
     hipError_t e = hipSuccess;
-    auto batch = [&](auto* disp, int k0, int kb) {
-        using T = disp_elem_t<decltype(disp)>;
+    auto batch = [&](auto maps, int k0, int kb) {
+        using T = disp_elem_t<decltype(maps)>;
         const sdr_relief_query* qs = d_queries + k0;
         const dim3 sgrid(slices, (unsigned)kb), cgrid(tiles, tiles, (unsigned)kb), pgrid((unsigned)kb);
         if ((e = hipMemsetAsync(grids, 0, (size_t)kb * gbytes, st)) != hipSuccess) return;
-        hipLaunchKernelGGL(sdr::k_foot_setup, pgrid, small, 0, st, W, H, F, d_labels ? 1 : 0, d_planes, P, qs, states);
-        hipLaunchKernelGGL((sdr::k_foot_sweep<T, 1>), sgrid, block, 0, st, disp, stride, frame_stride, W, H, F, d_conf,
-                           d_labels, q, FP, qs, states, grids);
-        hipLaunchKernelGGL((sdr::k_foot_sweep<T, 2>), sgrid, block, 0, st, disp, stride, frame_stride, W, H, F, d_conf,
-                           d_labels, q, FP, qs, states, grids);
+        hipLaunchKernelGGL(sdr::k_foot_setup, pgrid, small, 0, st, maps.dims(), d_planes, P, qs, states);
+        hipLaunchKernelGGL((sdr::k_foot_sweep<T, 1>), sgrid, block, 0, st, maps, q, FP, qs, states, grids);
+        hipLaunchKernelGGL((sdr::k_foot_sweep<T, 2>), sgrid, block, 0, st, maps, q, FP, qs, states, grids);
         hipLaunchKernelGGL(sdr::k_foot_cells, cgrid, block, 0, st, FP, states, (const unsigned*)grids);
         hipLaunchKernelGGL(sdr::k_foot_finish, pgrid, small, 0, st, FP, qs, (const sdr::FootState*)states,
                            d_out + k0);
     };
     for (int k0 = 0; k0 < K && e == hipSuccess; k0 += KB)
-        with_disp(disp_type, d_disp, [&](auto* disp) { batch(disp, k0, std::min(K - k0, KB)); });
+        with_maps(d_disp, disp_type, stride, frame_stride, W, H, F, d_conf, d_labels,
+                  [&](auto maps) { batch(maps, k0, std::min(K - k0, KB)); });
     return sc.finish(e);
 }
 

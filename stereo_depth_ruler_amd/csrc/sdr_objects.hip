@@ -71,39 +71,10 @@ struct ObjSliceCount {
 };
 static_assert(sizeof(ObjState) == 3616, "ObjState is 3616 bytes");
 
-// float -> key with the floats' order (no NaN among the members); and back
-__device__ __forceinline__ unsigned obj_key(float hf) {
-    const unsigned b = __float_as_uint(hf);
-    return b ^ ((b & 0x80000000u) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float obj_unkey(unsigned k) {
-    return __uint_as_float(k ^ ((k & 0x80000000u) ? 0x80000000u : 0xffffffffu));
-}
-
-// the maps at the rectangle's origin
-template <typename T>
-struct ObjMaps {
-    const T* fd;
-    const float* fc;
-    const uint8_t* fl;
-};
-template <typename T>
-__device__ __forceinline__ ObjMaps<T> obj_maps(const sdr_relief_query& q, const PlaneRect& R, const T* disp,
-                                               size_t stride, size_t fstride, int W, int H, const float* conf,
-                                               const uint8_t* labels) {
-    const size_t org = (size_t)R.ys * W + (size_t)R.xs, fo = (size_t)q.frame * H * W;
-    ObjMaps<T> m;
-    m.fd = disp + (size_t)q.frame * fstride + (size_t)R.ys * stride + (size_t)R.xs;
-    m.fc = conf ? conf + fo + org : nullptr;
-    m.fl = labels ? labels + fo + org : nullptr;
-    return m;
-}
-
 // 1024 threads = 16 waves, a thread a pixel of the tile: a wave covers two tile rows.
 template <typename T>
 __global__ __launch_bounds__(kObjLocalThreads) void k_obj_local(
-    const T* __restrict__ disp, size_t stride, size_t fstride, int W, int H, int F, const float* __restrict__ conf,
-    const uint8_t* __restrict__ labels, Q16 Q, sdr_object_params P, const sdr_plane* __restrict__ planes, int NP,
+    RegionMaps<T> maps, Q16 Q, sdr_object_params P, const sdr_plane* __restrict__ planes, int NP,
     const sdr_relief_query* __restrict__ query, ObjTileCount* __restrict__ tiles, int* __restrict__ Pa,
     int* __restrict__ Sz) {
 #pragma clang fp contract(off)
@@ -113,11 +84,12 @@ __global__ __launch_bounds__(kObjLocalThreads) void k_obj_local(
     __shared__ int red[kObjLocalThreads / 64][3];
     const sdr_relief_query q = *query;
     RegionPlane pl;
-    if (region_refusal(q, W, H, F, labels != nullptr, planes, NP, &pl)) return;
-    const PlaneRect R = plane_rect(region_segment(q));
+    RegionView<T> M;
+    if (query_view(maps, planes, NP, q, &pl, &M)) return;
+    const PlaneRect R = M.R;
+    const size_t stride = maps.stride;
     const int tx0 = blockIdx.x * kObjTile, ty0 = blockIdx.y * kObjTile;
     if (tx0 >= R.rw || ty0 >= R.rh) return;  // block-uniform
-    const ObjMaps<T> M = obj_maps(q, R, disp, stride, fstride, W, H, conf, labels);
     const int i = threadIdx.x, lane = i & 63, wave = i >> 6, lx = i & (kObjTile - 1);
     const int u = tx0 + lx, v = ty0 + (i >> 5);
     const float md = P.max_diff;
@@ -126,8 +98,7 @@ __global__ __launch_bounds__(kObjLocalThreads) void k_obj_local(
     bool mem = false, masked = false, valid = false;
     float d = ruler_nan();
     if (u < R.rw && v < R.rh) {
-        const RegionPix px = region_pixel(M.fd, stride, M.fc, M.fl, W, Q, pl, P.min_disp, P.conf_min, q.label, R.xs,
-                                          R.ys, (unsigned)u, (unsigned)v);
+        const RegionPix px = region_pixel(M, Q, pl, P.min_disp, P.conf_min, q.label, (unsigned)u, (unsigned)v);
         masked = px.masked;
         valid = px.valid;
         mem = px.member && P.h_lo <= px.hf && px.hf <= P.h_hi;
@@ -192,20 +163,21 @@ __global__ __launch_bounds__(kObjLocalThreads) void k_obj_local(
 // against the row below, each with its one (4) or three (8) neighbours across; the diagonal pairs
 // at a tile corner are among them.
 template <typename T>
-__global__ __launch_bounds__(256) void k_obj_merge(const T* __restrict__ disp, size_t stride, size_t fstride, int W,
-                                                   int H, int F, int has_labels, sdr_object_params P,
+__global__ __launch_bounds__(256) void k_obj_merge(RegionMaps<T> maps, sdr_object_params P,
                                                    const sdr_plane* __restrict__ planes, int NP,
                                                    const sdr_relief_query* __restrict__ query, int* Pa) {
 #pragma clang fp contract(off)
     const sdr_relief_query q = *query;
     RegionPlane pl;
-    if (region_refusal(q, W, H, F, has_labels != 0, planes, NP, &pl)) return;
-    const PlaneRect R = plane_rect(region_segment(q));
+    RegionView<T> M;
+    if (query_view(maps, planes, NP, q, &pl, &M)) return;
+    const PlaneRect R = M.R;
+    const T* fd = M.fd;
+    const size_t stride = maps.stride;
     const int nvx = (R.rw - 1) / kObjTile, nhy = (R.rh - 1) / kObjTile;
     const int nv = nvx * R.rh, nh = nhy * R.rw;
     const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (t >= nv + nh) return;
-    const T* fd = disp + (size_t)q.frame * fstride + (size_t)R.ys * stride + (size_t)R.xs;
     int ax, ay, bx[3], by[3];
     if (t < nv) {
         ay = t / nvx;
@@ -248,13 +220,12 @@ __global__ __launch_bounds__(256) void k_obj_merge(const T* __restrict__ disp, s
 
 // tile roots (S > 0): the global root, the size accumulated there, a one-hop pointer for the
 // sweeps behind.  Only a global root's size is added to, and a global root adds nothing.
-__global__ __launch_bounds__(kRegionThreads) void k_obj_sizes(int W, int H, int F, int has_labels,
-                                                              const sdr_plane* __restrict__ planes, int NP,
+__global__ __launch_bounds__(kRegionThreads) void k_obj_sizes(RegionDims dims, const sdr_plane* __restrict__ planes, int NP,
                                                               const sdr_relief_query* __restrict__ query, int* Pa,
                                                               int* Sz) {
     const sdr_relief_query q = *query;
     RegionPlane pl;
-    if (region_refusal(q, W, H, F, has_labels != 0, planes, NP, &pl)) return;
+    if (query_refusal(dims, planes, NP, q, &pl)) return;
     const PlaneRect R = plane_rect(region_segment(q));
     const unsigned area = (unsigned)R.rw * (unsigned)R.rh, base = blockIdx.x * (unsigned)kRegionSlice;
 #pragma unroll
@@ -287,8 +258,7 @@ __device__ __forceinline__ unsigned long long block_max(unsigned long long m, un
 
 // A slice of the rectangle's order a workgroup: its global roots counted (slices[slice]), and the
 // slice's max_objects largest keys of kept roots into cand[slice][max_objects], zeros behind them.
-__global__ __launch_bounds__(kRegionThreads) void k_obj_select(int W, int H, int F, int has_labels,
-                                                               sdr_object_params P,
+__global__ __launch_bounds__(kRegionThreads) void k_obj_select(RegionDims dims, sdr_object_params P,
                                                                const sdr_plane* __restrict__ planes, int NP,
                                                                const sdr_relief_query* __restrict__ query,
                                                                ObjSliceCount* __restrict__ slices,
@@ -299,7 +269,7 @@ __global__ __launch_bounds__(kRegionThreads) void k_obj_select(int W, int H, int
     __shared__ int red[kRegionWaves][3];
     const sdr_relief_query q = *query;
     RegionPlane pl;
-    if (region_refusal(q, W, H, F, has_labels != 0, planes, NP, &pl)) return;
+    if (query_refusal(dims, planes, NP, q, &pl)) return;
     const PlaneRect R = plane_rect(region_segment(q));
     const unsigned area = (unsigned)R.rw * (unsigned)R.rh, base = blockIdx.x * (unsigned)kRegionSlice;
     if (base >= area) return;  // block-uniform
@@ -358,8 +328,7 @@ __global__ __launch_bounds__(kRegionThreads) void k_obj_select(int W, int H, int
 // One workgroup.  First the scan record's counts: the sums of what the rectangle's tiles and slices
 // wrote.  Then max_objects rounds of the largest key left in the slices' lists; a thread reads the
 // same entries every round, so the zero it writes over a winner is its own to see.
-__global__ __launch_bounds__(kObjRankThreads) void k_obj_rank(int W, int H, int F, int has_labels,
-                                                              sdr_object_params P,
+__global__ __launch_bounds__(kObjRankThreads) void k_obj_rank(RegionDims dims, sdr_object_params P,
                                                               const sdr_plane* __restrict__ planes, int NP,
                                                               const sdr_relief_query* __restrict__ query,
                                                               ObjState* __restrict__ S,
@@ -370,7 +339,8 @@ __global__ __launch_bounds__(kObjRankThreads) void k_obj_rank(int W, int H, int 
     __shared__ int sh[kObjRankThreads / 64][6];
     const sdr_relief_query q = *query;
     RegionPlane pl;
-    if (region_refusal(q, W, H, F, has_labels != 0, planes, NP, &pl)) return;
+    if (query_refusal(dims, planes, NP, q, &pl)) return;
+    const int W = dims.W;
     const PlaneRect R = plane_rect(region_segment(q));
     const size_t area = (size_t)R.rw * (size_t)R.rh;
     const int nslices = (int)((area + kRegionSlice - 1) / kRegionSlice);
@@ -437,11 +407,7 @@ __global__ __launch_bounds__(kObjRankThreads) void k_obj_rank(int W, int H, int 
 // The labels and the ranked objects' records: every lane takes part in the wave reductions, a
 // lane without a ranked pixel with neutral values.
 template <typename T>
-__global__ __launch_bounds__(kRegionThreads) void k_obj_stats(const T* __restrict__ disp, size_t stride,
-                                                              size_t fstride, int W, int H, int F,
-                                                              const float* __restrict__ conf,
-                                                              const uint8_t* __restrict__ labels, Q16 Q,
-                                                              sdr_object_params P,
+__global__ __launch_bounds__(kRegionThreads) void k_obj_stats(RegionMaps<T> maps, Q16 Q, sdr_object_params P,
                                                               const sdr_plane* __restrict__ planes, int NP,
                                                               const sdr_relief_query* __restrict__ query,
                                                               ObjState* __restrict__ S, const int* __restrict__ Pa,
@@ -451,13 +417,14 @@ __global__ __launch_bounds__(kRegionThreads) void k_obj_stats(const T* __restric
     __shared__ ObjAcc la[kObjMax];
     const sdr_relief_query q = *query;
     RegionPlane pl;
-    if (region_refusal(q, W, H, F, labels != nullptr, planes, NP, &pl)) return;
+    RegionView<T> M;
+    if (query_view(maps, planes, NP, q, &pl, &M)) return;
     if (S->count == 0) return;  // block-uniform: every label stays 255
-    const PlaneRect R = plane_rect(region_segment(q));
+    const PlaneRect R = M.R;
+    const int W = maps.W;
     const unsigned area = (unsigned)R.rw * (unsigned)R.rh, base = blockIdx.x * (unsigned)kRegionSlice;
     if (base >= area) return;  // block-uniform
-    const ObjMaps<T> M = obj_maps(q, R, disp, stride, fstride, W, H, conf, labels);
-    uint8_t* lo = labels_out ? labels_out + (size_t)R.ys * W + (size_t)R.xs : nullptr;
+    uint8_t* lo = maps.view(region_segment(q), labels_out).fl;  // the frame's label map that goes out
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid < kObjMax) la[tid] = ObjAcc{0, 0, 0, 0u, 0u, 0u, 0u, 0u, 0u};
     __syncthreads();
@@ -485,10 +452,9 @@ __global__ __launch_bounds__(kRegionThreads) void k_obj_stats(const T* __restric
         long long e = 0;
         unsigned key = 0;
         if (k >= 0) {
-            const RegionPix px = region_pixel(M.fd, stride, M.fc, M.fl, W, Q, pl, P.min_disp, P.conf_min, q.label,
-                                              R.xs, R.ys, u, v);
+            const RegionPix px = region_pixel(M, Q, pl, P.min_disp, P.conf_min, q.label, u, v);
             e = llrint((double)px.hf * 256.0);
-            key = obj_key(px.hf);
+            key = ordered_key(px.hf);
         }
         const int x = R.xs + (int)u, y = R.ys + (int)v;
         unsigned long long pend = __ballot(k >= 0);
@@ -534,7 +500,7 @@ __global__ __launch_bounds__(kRegionThreads) void k_obj_stats(const T* __restric
 }
 
 // the max_objects records (a thread each) and the scan record
-__global__ __launch_bounds__(kObjMax) void k_obj_finish(int W, int H, int F, int has_labels, sdr_object_params P,
+__global__ __launch_bounds__(kObjMax) void k_obj_finish(RegionDims dims, sdr_object_params P,
                                                         const sdr_plane* __restrict__ planes, int NP,
                                                         const sdr_relief_query* __restrict__ query,
                                                         const ObjState* __restrict__ S,
@@ -542,7 +508,7 @@ __global__ __launch_bounds__(kObjMax) void k_obj_finish(int W, int H, int F, int
                                                         sdr_object_scan* __restrict__ scan) {
     const sdr_relief_query q = *query;
     RegionPlane pl;
-    const uint32_t refused = region_refusal(q, W, H, F, has_labels != 0, planes, NP, &pl);
+    const uint32_t refused = query_refusal(dims, planes, NP, q, &pl);
     const PlaneRect R = plane_rect(region_segment(q));
     const int tid = threadIdx.x, count = refused ? 0 : S->count;
     if (tid < P.max_objects) {
@@ -565,8 +531,8 @@ __global__ __launch_bounds__(kObjMax) void k_obj_finish(int W, int H, int F, int
             o.sum_x = a.sum_x;
             o.sum_y = a.sum_y;
             o.sum256 = a.sum256;
-            o.h_max = obj_unkey(a.kmax);
-            o.h_min = obj_unkey(~a.kmin_inv);
+            o.h_max = ordered_unkey(a.kmax);
+            o.h_min = ordered_unkey(~a.kmin_inv);
             const bool cut = o.x0 == R.xs || o.x1 == R.xs + R.rw - 1 || o.y0 == R.ys || o.y1 == R.ys + R.rh - 1;
             o.flags = SDR_OBJECT_VALID | (cut ? SDR_OBJECT_CUT : 0);
         }
@@ -676,32 +642,28 @@ int sdr_find_objects_device(const void* d_disp, int disp_type, size_t stride, si
     sdr::ObjTileCount* tcnt = sc.at(s_tiles);
     sdr::ObjSliceCount* scnt = sc.at(s_slices);
     sdr::ObjState* S = sc.at(s_state);
-    const int has_labels = d_labels_in ? 1 : 0;
     // border pixels of the largest rectangle: ((W - 1) / 32) * H + ((H - 1) / 32) * W <= 2^20
     const size_t borders = (size_t)((W - 1) / sdr::kObjTile) * H + (size_t)((H - 1) / sdr::kObjTile) * W;
     const dim3 block(sdr::kRegionThreads), sgrid(slices), mgrid((unsigned)((borders + 255) / 256));
     hipError_t e = hipMemsetAsync(S, 0, sizeof(sdr::ObjState), st);
     if (e == hipSuccess && d_labels_out) e = hipMemsetAsync(d_labels_out, 255, px, st);
     if (e == hipSuccess)
-        with_disp(disp_type, d_disp, [&](auto* disp) {
-            using T = disp_elem_t<decltype(disp)>;
-            hipLaunchKernelGGL((sdr::k_obj_local<T>), tiles, dim3(sdr::kObjLocalThreads), 0, st, disp, stride,
-                               frame_stride, W, H, F, d_conf, d_labels_in, q, OP, d_planes, P, d_query, tcnt, Pa, Sz);
+        with_maps(d_disp, disp_type, stride, frame_stride, W, H, F, d_conf, d_labels_in, [&](auto maps) {
+            using T = disp_elem_t<decltype(maps)>;
+            const sdr::RegionDims dims = maps.dims();
+            hipLaunchKernelGGL((sdr::k_obj_local<T>), tiles, dim3(sdr::kObjLocalThreads), 0, st, maps, q, OP, d_planes, P,
+                               d_query, tcnt, Pa, Sz);
             if (borders)
-                hipLaunchKernelGGL((sdr::k_obj_merge<T>), mgrid, dim3(256), 0, st, disp, stride, frame_stride, W, H, F,
-                                   has_labels, OP, d_planes, P, d_query, Pa);
-            hipLaunchKernelGGL(sdr::k_obj_sizes, sgrid, block, 0, st, W, H, F, has_labels, d_planes, P, d_query, Pa,
-                               Sz);
-            hipLaunchKernelGGL(sdr::k_obj_select, sgrid, block, 0, st, W, H, F, has_labels, OP, d_planes, P, d_query,
-                               scnt, (const int*)Pa, (const int*)Sz, cand);
-            hipLaunchKernelGGL(sdr::k_obj_rank, dim3(1), dim3(sdr::kObjRankThreads), 0, st, W, H, F, has_labels, OP,
-                               d_planes, P, d_query, S, (const sdr::ObjTileCount*)tcnt,
-                               (const sdr::ObjSliceCount*)scnt, Sz, cand);
-            hipLaunchKernelGGL((sdr::k_obj_stats<T>), sgrid, block, 0, st, disp, stride, frame_stride, W, H, F, d_conf,
-                               d_labels_in, q, OP, d_planes, P, d_query, S, (const int*)Pa, (const int*)Sz,
-                               d_labels_out);
-            hipLaunchKernelGGL(sdr::k_obj_finish, dim3(1), dim3(sdr::kObjMax), 0, st, W, H, F, has_labels, OP, d_planes,
-                               P, d_query, (const sdr::ObjState*)S, d_objects, d_scan);
+                hipLaunchKernelGGL((sdr::k_obj_merge<T>), mgrid, dim3(256), 0, st, maps, OP, d_planes, P, d_query, Pa);
+            hipLaunchKernelGGL(sdr::k_obj_sizes, sgrid, block, 0, st, dims, d_planes, P, d_query, Pa, Sz);
+            hipLaunchKernelGGL(sdr::k_obj_select, sgrid, block, 0, st, dims, OP, d_planes, P, d_query, scnt,
+                               (const int*)Pa, (const int*)Sz, cand);
+            hipLaunchKernelGGL(sdr::k_obj_rank, dim3(1), dim3(sdr::kObjRankThreads), 0, st, dims, OP, d_planes, P,
+                               d_query, S, (const sdr::ObjTileCount*)tcnt, (const sdr::ObjSliceCount*)scnt, Sz, cand);
+            hipLaunchKernelGGL((sdr::k_obj_stats<T>), sgrid, block, 0, st, maps, q, OP, d_planes, P, d_query, S,
+                               (const int*)Pa, (const int*)Sz, d_labels_out);
+            hipLaunchKernelGGL(sdr::k_obj_finish, dim3(1), dim3(sdr::kObjMax), 0, st, dims, OP, d_planes, P, d_query,
+                               (const sdr::ObjState*)S, d_objects, d_scan);
         });
     return sc.finish(e);
 }

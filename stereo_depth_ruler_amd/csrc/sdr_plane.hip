@@ -82,11 +82,11 @@ constexpr uint8_t kFreeLabel = 255;
 // Pixel (u, v) of the slice's region on the 1/16 px grid; true when it counts: valid, confident
 // and, in the search (kFree), not yet claimed by a plane.
 template <bool kFree, typename T, typename L>
-__device__ __forceinline__ bool plane_pixel(const RegionSlice<T, L>& sl, size_t stride, int W,
-                                            const sdr_plane_params& P, unsigned u, unsigned v, int* q) {
-    bool ok = plane_q(sl.fd + (size_t)v * stride + u, P.min_disp, q);
-    if (sl.fc) ok = ok && sl.fc[(size_t)v * W + u] >= P.conf_min;
-    if (kFree) ok = ok && sl.fl[(size_t)v * W + u] == kFreeLabel;
+__device__ __forceinline__ bool plane_pixel(const RegionView<T, L>& sl, const sdr_plane_params& P, unsigned u,
+                                            unsigned v, int* q) {
+    bool ok = plane_q(sl.fd + (size_t)v * sl.stride + u, P.min_disp, q);
+    if (sl.fc) ok = ok && sl.fc[(size_t)v * sl.W + u] >= P.conf_min;
+    if (kFree) ok = ok && sl.fl[(size_t)v * sl.W + u] == kFreeLabel;
     return ok;
 }
 
@@ -101,10 +101,7 @@ __device__ __forceinline__ bool plane_pixel(const RegionSlice<T, L>& sl, size_t 
 // round's seed plane, and a stopped search leaves at once.  The sums and the residual are the
 // same code either way.
 template <typename T, bool kSearch>
-__global__ __launch_bounds__(kRegionThreads) void k_plane_sweep(const T* __restrict__ disp, size_t stride,
-                                                               size_t fstride, int W, int H, int F,
-                                                               const float* __restrict__ conf,
-                                                               sdr_plane_params P,
+__global__ __launch_bounds__(kRegionThreads) void k_plane_sweep(RegionMaps<T> maps, sdr_plane_params P,
                                                                const sdr_segment* __restrict__ regs,
                                                                long long* __restrict__ acc, int sweep,
                                                                const uint8_t* __restrict__ labels,
@@ -115,9 +112,9 @@ __global__ __launch_bounds__(kRegionThreads) void k_plane_sweep(const T* __restr
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (kSearch && state->stopped) return;  // block-uniform
     const sdr_segment sg = regs[k];
-    if (!segment_in_range(sg, W, H, F)) return;
-    RegionSlice<T, const uint8_t> sl;
-    if (!region_slice(sg, disp, stride, fstride, W, H, conf, kSearch ? labels : nullptr, &sl)) return;
+    if (!maps.holds(sg)) return;
+    RegionSlice<T> sl;
+    if (!region_cut(maps.view(sg, kSearch ? labels : nullptr), &sl)) return;
     long long* A = acc + (size_t)k * (size_t)(P.iterations + 2) * kPlaneSlots;
     const bool last = sweep == P.iterations + 1;
     PlaneFit fit = {0.0, 0.0, 0.0, true};
@@ -137,7 +134,7 @@ __global__ __launch_bounds__(kRegionThreads) void k_plane_sweep(const T* __restr
     double rmax = 0.0;
     sl.each([&](unsigned u, unsigned v) __attribute__((always_inline)) {
         int q;
-        bool ok = plane_pixel<kSearch>(sl, stride, W, P, u, v, &q);
+        bool ok = plane_pixel<kSearch>(sl, P, u, v, &q);
         double r = 0.0;
         if (sweep > 0) {
             r = (double)q - plane_at(fit, (double)u, (double)v);
@@ -261,8 +258,8 @@ __device__ __forceinline__ void plane_record(sdr_plane& o, const PlaneRect& R, c
 }
 
 // The records, one lane a region, from the accumulators the sweeps have left.
-__global__ __launch_bounds__(64) void k_plane_finish(const sdr_segment* __restrict__ regs, int K, int W,
-                                                     int H, int F, Q16 Q, sdr_plane_params P,
+__global__ __launch_bounds__(64) void k_plane_finish(const sdr_segment* __restrict__ regs, int K,
+                                                     RegionDims dims, Q16 Q, sdr_plane_params P,
                                                      const long long* __restrict__ acc,
                                                      sdr_plane* __restrict__ out) {
 #pragma clang fp contract(off)
@@ -280,7 +277,7 @@ __global__ __launch_bounds__(64) void k_plane_finish(const sdr_segment* __restri
     o.area = o.n_valid = o.n_inliers = o.fits = 0;
     o.flags = SDR_PLANE_OUT_OF_RANGE;
     o.reserved = 0;
-    if (!segment_in_range(sg, W, H, F)) {
+    if (!dims.holds(sg)) {
         out[k] = o;
         return;
     }
@@ -370,23 +367,21 @@ __device__ __forceinline__ void search_stop(SearchState* st, const sdr_segment& 
 }
 
 // Before round 0: a region out of range stops the search with its records.
-__global__ __launch_bounds__(64) void k_search_init(const sdr_segment* __restrict__ reg, int W, int H, int F,
+__global__ __launch_bounds__(64) void k_search_init(const sdr_segment* __restrict__ reg, RegionDims dims,
                                                     int max_planes, SearchState* __restrict__ st,
                                                     sdr_plane* __restrict__ planes, int32_t* __restrict__ count,
                                                     sdr_plane_search_round* __restrict__ rounds) {
     if (threadIdx.x != 0) return;
     const sdr_segment sg = reg[0];
     *count = 0;
-    if (!segment_in_range(sg, W, H, F))
+    if (!dims.holds(sg))
         search_stop(st, sg, 0, 0, max_planes, -1, 0, 0, SDR_SEARCH_NOT_RUN, SDR_PLANE_OUT_OF_RANGE, planes, count,
                     rounds);
 }
 
 // The draws of round r, a thread a hypothesis.
 template <typename T>
-__global__ __launch_bounds__(64) void k_search_draw(const T* __restrict__ disp, size_t stride, size_t fstride, int W,
-                                                    int H, int F, const float* __restrict__ conf,
-                                                    sdr_plane_params P, const sdr_segment* __restrict__ reg,
+__global__ __launch_bounds__(64) void k_search_draw(RegionMaps<T> maps, sdr_plane_params P, const sdr_segment* __restrict__ reg,
                                                     const uint8_t* __restrict__ labels, int r, int M, uint32_t seed,
                                                     const SearchState* __restrict__ st,
                                                     SearchHyp* __restrict__ hyp) {
@@ -394,11 +389,9 @@ __global__ __launch_bounds__(64) void k_search_draw(const T* __restrict__ disp, 
     const int h = blockIdx.x * 64 + threadIdx.x;
     if (h >= M) return;
     const sdr_segment sg = reg[0];
-    const PlaneRect R = plane_rect(sg);  // in range: k_search_init
+    const RegionView<T> vw = maps.view(sg, labels);  // in range: k_search_init
+    const PlaneRect R = vw.R;
     const unsigned area = (unsigned)R.rw * (unsigned)R.rh;
-    const T* fd = disp + (size_t)sg.frame * fstride + (size_t)R.ys * stride + (size_t)R.xs;
-    const float* fc = conf ? conf + ((size_t)sg.frame * H + (size_t)R.ys) * W + (size_t)R.xs : nullptr;
-    const uint8_t* fl = labels + (size_t)R.ys * W + (size_t)R.xs;
     const uint32_t key = search_mix(search_mix(seed ^ (0x9E3779B9u * (uint32_t)(r + 1))) ^ (uint32_t)h);
     int pu[3], pv[3], pq[3];
     bool found = true;
@@ -409,9 +402,7 @@ __global__ __launch_bounds__(64) void k_search_draw(const T* __restrict__ disp, 
             const unsigned p = (unsigned)(((unsigned long long)x * area) >> 32);  // < area
             const unsigned v = p / (unsigned)R.rw, u = p - v * (unsigned)R.rw;
             int q;
-            bool ok = plane_q(fd + (size_t)v * stride + u, P.min_disp, &q);
-            if (fc) ok = ok && fc[(size_t)v * W + u] >= P.conf_min;
-            ok = ok && fl[(size_t)v * W + u] == kFreeLabel;
+            const bool ok = plane_pixel<true>(vw, P, u, v, &q);
             if (ok) {
                 pu[j] = (int)u;
                 pv[j] = (int)v;
@@ -444,10 +435,7 @@ __global__ __launch_bounds__(64) void k_search_draw(const T* __restrict__ disp, 
 // count) goes to the score array: neither the slices' order nor the grid shows in the result.  It
 // also counts the round's free pixels (the record's n_valid) into acc[0].
 template <typename T>
-__global__ __launch_bounds__(kRegionThreads) void k_search_score(const T* __restrict__ disp, size_t stride,
-                                                                size_t fstride, int W, int H, int F,
-                                                                const float* __restrict__ conf,
-                                                                sdr_plane_params P,
+__global__ __launch_bounds__(kRegionThreads) void k_search_score(RegionMaps<T> maps, sdr_plane_params P,
                                                                 const sdr_segment* __restrict__ reg,
                                                                 const uint8_t* __restrict__ labels, int M,
                                                                 const SearchState* __restrict__ st,
@@ -458,8 +446,8 @@ __global__ __launch_bounds__(kRegionThreads) void k_search_score(const T* __rest
     if (st->stopped) return;  // block-uniform
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    RegionSlice<T, const uint8_t> sl;
-    if (!region_slice(reg[0], disp, stride, fstride, W, H, conf, labels, &sl)) return;
+    RegionSlice<T> sl;
+    if (!region_cut(maps.view(reg[0], labels), &sl)) return;
     const long long Tq = (long long)floor((double)P.inlier_px * 16.0);
 
     // the loop is written out: every lane takes part in a step's ballot, past the area too
@@ -474,7 +462,7 @@ __global__ __launch_bounds__(kRegionThreads) void k_search_score(const T* __rest
         if (p < sl.area) {
             const unsigned v = p / (unsigned)sl.R.rw, u = p - v * (unsigned)sl.R.rw;
             int q;
-            const bool ok = plane_pixel<true>(sl, stride, W, P, u, v, &q);
+            const bool ok = plane_pixel<true>(sl, P, u, v, &q);
             pu[j] = (int)u;
             pv[j] = (int)v;
             pq[j] = ok ? q : 0;
@@ -617,10 +605,7 @@ __global__ __launch_bounds__(64) void k_search_finish(const sdr_segment* __restr
 // get the round's label.  A pass of its own behind k_search_finish: a round that stops claims
 // nothing, and no sweep can see a partly claimed map.
 template <typename T>
-__global__ __launch_bounds__(kRegionThreads) void k_search_claim(const T* __restrict__ disp, size_t stride,
-                                                                size_t fstride, int W, int H, int F,
-                                                                const float* __restrict__ conf,
-                                                                sdr_plane_params P,
+__global__ __launch_bounds__(kRegionThreads) void k_search_claim(RegionMaps<T> maps, sdr_plane_params P,
                                                                 const sdr_segment* __restrict__ reg,
                                                                 uint8_t* __restrict__ labels, int r,
                                                                 const SearchState* __restrict__ st,
@@ -628,12 +613,13 @@ __global__ __launch_bounds__(kRegionThreads) void k_search_claim(const T* __rest
 #pragma clang fp contract(off)
     if (st->stopped) return;  // block-uniform
     RegionSlice<T, uint8_t> sl;
-    if (!region_slice(reg[0], disp, stride, fstride, W, H, conf, labels, &sl)) return;
+    if (!region_cut(maps.view(reg[0], labels), &sl)) return;
+    const int W = maps.W;
     const PlaneFit fit = plane_solve(A + (size_t)P.iterations * kPlaneSlots, P.min_inliers);  // ok: not stopped
     const double band = (double)P.inlier_px * 16.0;
     sl.each([&](unsigned u, unsigned v) __attribute__((always_inline)) {
         int q;
-        const bool ok = plane_pixel<true>(sl, stride, W, P, u, v, &q);
+        const bool ok = plane_pixel<true>(sl, P, u, v, &q);
         const double res = (double)q - plane_at(fit, (double)u, (double)v);
         if (ok && fabs(res) <= band) sl.fl[(size_t)v * W + u] = (uint8_t)r;
     });
@@ -641,10 +627,7 @@ __global__ __launch_bounds__(kRegionThreads) void k_search_claim(const T* __rest
 
 // Point queries, one wave a query: the ruler's sample and its distance to a fitted plane.
 template <typename T>
-__global__ __launch_bounds__(kRegionThreads) void k_plane_distance(const T* __restrict__ disp, size_t stride,
-                                                                  size_t fstride, int W, int H, int F,
-                                                                  const float* __restrict__ conf, Q16 Q,
-                                                                  sdr_ruler_params P,
+__global__ __launch_bounds__(kRegionThreads) void k_plane_distance(RegionMaps<T> maps, Q16 Q, sdr_ruler_params P,
                                                                   const sdr_plane* __restrict__ planes, int NP,
                                                                   const sdr_plane_query* __restrict__ qs, int K,
                                                                   struct sdr_plane_distance* __restrict__ out) {
@@ -653,7 +636,7 @@ __global__ __launch_bounds__(kRegionThreads) void k_plane_distance(const T* __re
     const int k = (int)blockIdx.x * kRegionWaves + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     if (k >= K) return;  // wave-uniform
     const sdr_plane_query q = qs[k];
-    const bool inside = q.frame >= 0 && q.frame < F && q.x >= 0 && q.x < W && q.y >= 0 && q.y < H;
+    const bool inside = maps.holds(q.frame, q.x, q.y);
     uint32_t flags = inside ? 0 : SDR_PDIST_OUT_OF_RANGE;
     RegionPlane pl = {{0.0, 0.0, 0.0}, 0.0};
     const bool plane_ok = query_plane(planes, NP, q.plane, &pl);
@@ -662,9 +645,7 @@ __global__ __launch_bounds__(kRegionThreads) void k_plane_distance(const T* __re
     s.d = s.xyz[0] = s.xyz[1] = s.xyz[2] = ruler_nan();
     s.n = 0;
     s.valid = false;
-    if (inside)
-        s = ruler_sample(disp + (size_t)q.frame * fstride, stride,
-                         conf ? conf + (size_t)q.frame * W * H : nullptr, W, H, Q, P, q.x, q.y, lane);
+    if (inside) s = ruler_sample(maps.frame(q.frame), Q, P, q.x, q.y, lane);
     if (lane != 0) return;
     double dist = __builtin_nan("");
     if (s.valid && plane_ok) {
@@ -744,14 +725,14 @@ int sdr_fit_planes_device(const void* d_disp, int disp_type, size_t stride, size
     for (int s = 0; s < sweeps; s++)
         for (int k0 = 0; k0 < K; k0 += 65535) {  // the grid's y extent
             const dim3 grid(slices, (unsigned)std::min(K - k0, 65535)), block(sdr::kRegionThreads);
-            with_disp(disp_type, d_disp, [&](auto* disp) {
-                hipLaunchKernelGGL((sdr::k_plane_sweep<disp_elem_t<decltype(disp)>, false>), grid, block, 0, st, disp,
-                                   stride, frame_stride, W, H, F, d_conf, *params, d_regions + k0, acc + k0 * per, s,
-                                   (const uint8_t*)nullptr, (const sdr::SearchState*)nullptr);
+            with_maps(d_disp, disp_type, stride, frame_stride, W, H, F, d_conf, nullptr, [&](auto maps) {
+                hipLaunchKernelGGL((sdr::k_plane_sweep<disp_elem_t<decltype(maps)>, false>), grid, block, 0, st, maps,
+                                   *params, d_regions + k0, acc + k0 * per, s, (const uint8_t*)nullptr,
+                                   (const sdr::SearchState*)nullptr);
             });
         }
-    hipLaunchKernelGGL(sdr::k_plane_finish, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, st, d_regions, K, W, H,
-                       F, q, *params, (const long long*)acc, d_planes);
+    hipLaunchKernelGGL(sdr::k_plane_finish, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, st, d_regions, K,
+                       sdr::RegionDims{W, H, F, 0}, q, *params, (const long long*)acc, d_planes);
     return sc.finish();
 }
 
@@ -799,28 +780,29 @@ int sdr_find_planes_device(const void* d_disp, int disp_type, size_t stride, siz
     const unsigned slices = sdr::region_slices(W, H);
     const dim3 sgrid(slices), sblock(sdr::kRegionThreads), dgrid((unsigned)((M + 63) / 64)), one(1), wave(64);
     const dim3 cgrid(slices, (unsigned)((M + sdr::kSearchChunk - 1) / sdr::kSearchChunk));
-    hipLaunchKernelGGL(sdr::k_search_init, one, wave, 0, st, d_region, W, H, F, NP, state, d_planes, d_count,
-                       d_rounds);
-    auto round = [&](auto* disp, int r) {
-        using T = disp_elem_t<decltype(disp)>;
+    hipLaunchKernelGGL(sdr::k_search_init, one, wave, 0, st, d_region, sdr::RegionDims{W, H, F, 0}, NP, state, d_planes,
+                       d_count, d_rounds);
+    // the maps carry no label map: the search's claim map is one frame's and goes beside them
+    auto round = [&](auto maps, int r) {
+        using T = disp_elem_t<decltype(maps)>;
         long long* A = acc + (size_t)r * per;
         unsigned* S = scores + (size_t)r * M;
-        hipLaunchKernelGGL(sdr::k_search_draw<T>, dgrid, wave, 0, st, disp, stride, frame_stride, W, H, F, d_conf, P,
-                           d_region, (const uint8_t*)labels, r, M, params->seed, (const sdr::SearchState*)state, hyp);
-        hipLaunchKernelGGL(sdr::k_search_score<T>, cgrid, sblock, 0, st, disp, stride, frame_stride, W, H, F, d_conf,
-                           P, d_region, (const uint8_t*)labels, M, (const sdr::SearchState*)state,
-                           (const sdr::SearchHyp*)hyp, S, A);
+        hipLaunchKernelGGL(sdr::k_search_draw<T>, dgrid, wave, 0, st, maps, P, d_region, (const uint8_t*)labels, r, M,
+                           params->seed, (const sdr::SearchState*)state, hyp);
+        hipLaunchKernelGGL(sdr::k_search_score<T>, cgrid, sblock, 0, st, maps, P, d_region, (const uint8_t*)labels, M,
+                           (const sdr::SearchState*)state, (const sdr::SearchHyp*)hyp, S, A);
         hipLaunchKernelGGL(sdr::k_search_pick, one, sblock, 0, st, d_region, r, NP, M, P.min_inliers,
                            (const sdr::SearchHyp*)hyp, (const unsigned*)S, state, d_planes, d_count, d_rounds);
         for (int s = 1; s <= P.iterations + 1; s++)
-            hipLaunchKernelGGL((sdr::k_plane_sweep<T, true>), sgrid, sblock, 0, st, disp, stride, frame_stride, W, H,
-                               F, d_conf, P, d_region, A, s, (const uint8_t*)labels, (const sdr::SearchState*)state);
+            hipLaunchKernelGGL((sdr::k_plane_sweep<T, true>), sgrid, sblock, 0, st, maps, P, d_region, A, s,
+                               (const uint8_t*)labels, (const sdr::SearchState*)state);
         hipLaunchKernelGGL(sdr::k_search_finish, one, wave, 0, st, d_region, r, NP, q, P, (const long long*)A, state,
                            d_planes, d_count, d_rounds);
-        hipLaunchKernelGGL(sdr::k_search_claim<T>, sgrid, sblock, 0, st, disp, stride, frame_stride, W, H, F, d_conf,
-                           P, d_region, labels, r, (const sdr::SearchState*)state, (const long long*)A);
+        hipLaunchKernelGGL(sdr::k_search_claim<T>, sgrid, sblock, 0, st, maps, P, d_region, labels, r,
+                           (const sdr::SearchState*)state, (const long long*)A);
     };
-    for (int r = 0; r < NP; r++) with_disp(disp_type, d_disp, [&](auto* disp) { round(disp, r); });
+    for (int r = 0; r < NP; r++)
+        with_maps(d_disp, disp_type, stride, frame_stride, W, H, F, d_conf, nullptr, [&](auto maps) { round(maps, r); });
     return sc.finish();
 }
 
@@ -858,9 +840,9 @@ int sdr_plane_distance_device(const void* d_disp, int disp_type, size_t stride, 
     if (K == 0) return SDR_OK;
     const sdr::Q16 q = make_q16(Q);
     const dim3 grid((unsigned)((K + sdr::kRegionWaves - 1) / sdr::kRegionWaves)), block(sdr::kRegionThreads);
-    with_disp(disp_type, d_disp, [&](auto* disp) {
-        hipLaunchKernelGGL(sdr::k_plane_distance<disp_elem_t<decltype(disp)>>, grid, block, 0, (hipStream_t)stream, disp,
-                           stride, frame_stride, W, H, F, d_conf, q, *params, d_planes, P, d_queries, K, d_out);
+    with_maps(d_disp, disp_type, stride, frame_stride, W, H, F, d_conf, nullptr, [&](auto maps) {
+        hipLaunchKernelGGL(sdr::k_plane_distance<disp_elem_t<decltype(maps)>>, grid, block, 0, (hipStream_t)stream, maps,
+                           q, *params, d_planes, P, d_queries, K, d_out);
     });
     SDR_HIP(hipGetLastError());
     return SDR_OK;

@@ -1,8 +1,11 @@
 // sdr_region.hpp -- the region rule, once: which queries run, which pixels of a rectangle count and
 // how high each lies above the query's plane (steps 1 to 5 of "the relief of a region" in
 // include/sdr/sdr.h, which the footprint takes over), and the frame of a sweep that gives a
-// workgroup a slice of a rectangle's row-major order.  The relief, the footprint, the objects, the
-// clearance, the plane fit and the plane search are written on it.
+// workgroup a slice of a rectangle's row-major order.  A kernel takes the call's maps as one
+// RegionMaps (sdr_ruler_shared.hpp) and opens its query with one call: query_refusal (no map read),
+// query_view (the rectangle and the maps at its origin) or query_slice (the workgroup's slice of
+// it); region_pixel is the rule on a view.  The relief, the footprint, the objects, the clearance,
+// the plane fit and the plane search are written on it.
 #pragma once
 #include "sdr_ruler_shared.hpp"
 
@@ -20,8 +23,18 @@ inline unsigned region_slices(int W, int H) {
     return (unsigned)(((size_t)W * H + kRegionSlice - 1) / kRegionSlice);
 }
 
-__device__ __forceinline__ sdr_segment region_segment(const sdr_relief_query& q) {
+// the rectangle of a query (sdr_relief_query, sdr_clearance_query)
+template <typename Query>
+__device__ __forceinline__ sdr_segment region_segment(const Query& q) {
     return sdr_segment{q.frame, q.x0, q.y0, q.x1, q.y1};
+}
+// a query's labels are in range and, where it needs a label map, the call has one
+__device__ __forceinline__ bool labels_in_range(const sdr_relief_query& q, bool has_labels) {
+    return q.label >= -1 && q.label <= 255 && (q.label < 0 || has_labels);
+}
+__device__ __forceinline__ bool labels_in_range(const sdr_clearance_query& q, bool has_labels) {
+    return q.label_a >= 0 && q.label_a <= 255 && q.label_b >= 0 && q.label_b <= 255 && q.label_a != q.label_b &&
+           has_labels;
 }
 
 struct RegionPlane {
@@ -50,11 +63,10 @@ static_assert(SDR_RELIEF_NO_PLANE == 4 && SDR_FOOTPRINT_NO_PLANE == 4 && SDR_PDI
 constexpr uint32_t kRegionOutOfRange = 2, kRegionNoPlane = 4;
 
 // 0, or the flag that refuses the query without a read of the maps; the plane of one that runs
-__device__ __forceinline__ uint32_t region_refusal(const sdr_relief_query& q, int W, int H, int F, bool has_labels,
-                                                   const sdr_plane* __restrict__ planes, int NP, RegionPlane* pl) {
-    if (!segment_in_range(region_segment(q), W, H, F) || q.label < -1 || q.label > 255 ||
-        (q.label >= 0 && !has_labels))
-        return kRegionOutOfRange;
+template <typename Query>
+__device__ __forceinline__ uint32_t query_refusal(const RegionDims& d, const sdr_plane* __restrict__ planes, int NP,
+                                                  const Query& q, RegionPlane* pl) {
+    if (!d.holds(region_segment(q)) || !labels_in_range(q, d.has_labels != 0)) return kRegionOutOfRange;
     return query_plane(planes, NP, q.plane, pl) ? 0 : kRegionNoPlane;
 }
 
@@ -64,14 +76,17 @@ struct RegionPix {
     float xyz[3];  // the point (valid pixels)
 };
 
-// Pixel (u, v) of the region whose origin (xs, ys) fd, fc and fl point at: the definition's steps
-// 1 to 5.  Every sweep of every unit repeats it: the same bits in every pass.
-template <typename T>
-__device__ __forceinline__ RegionPix region_pixel(const T* __restrict__ fd, size_t stride,
-                                                  const float* __restrict__ fc, const uint8_t* __restrict__ fl,
-                                                  int W, const Q16& Q, const RegionPlane& pl, float min_disp,
-                                                  float conf_min, int label, int xs, int ys, unsigned u, unsigned v) {
+// Pixel (u, v) of the view's rectangle: the definition's steps 1 to 5.  Every sweep of every unit
+// repeats it: the same bits in every pass.
+template <typename T, typename L>
+__device__ __forceinline__ RegionPix region_pixel(const RegionView<T, L>& vw, const Q16& Q, const RegionPlane& pl,
+                                                  float min_disp, float conf_min, int label, unsigned u, unsigned v) {
 #pragma clang fp contract(off)
+    const T* __restrict__ fd = vw.fd;
+    const float* __restrict__ fc = vw.fc;
+    const uint8_t* __restrict__ fl = vw.fl;
+    const size_t stride = vw.stride;
+    const int W = vw.W, xs = vw.R.xs, ys = vw.R.ys;
     RegionPix r = {false, false, false, 0.f, {0.f, 0.f, 0.f}};
     r.masked = label < 0 || fl[(size_t)v * W + u] == (uint8_t)label;
     if (!r.masked) return r;
@@ -86,16 +101,10 @@ __device__ __forceinline__ RegionPix region_pixel(const T* __restrict__ fd, size
     return r;
 }
 
-// A workgroup's slice of a rectangle: the rectangle, its area, the slice's first pixel, and the
-// disparity, confidence and label maps at the rectangle's origin (L: const uint8_t, or uint8_t for
-// the sweep that writes labels).
-template <typename T, typename L>
-struct RegionSlice {
-    PlaneRect R;
+// A workgroup's slice of a view's rectangle: its area and the slice's first pixel.
+template <typename T, typename L = const uint8_t>
+struct RegionSlice : RegionView<T, L> {
     unsigned area, base;
-    const T* fd;
-    const float* fc;
-    L* fl;
 
     // body(u, v) for each of the slice's pixels the calling thread takes
     template <typename Body>
@@ -104,27 +113,40 @@ struct RegionSlice {
         for (int j = 0; j < kRegionPix; j++) {
             const unsigned p = base + (unsigned)(j * kRegionThreads + (int)threadIdx.x);
             if (p >= area) continue;
-            const unsigned v = p / (unsigned)R.rw, u = p - v * (unsigned)R.rw;
+            const unsigned v = p / (unsigned)this->R.rw, u = p - v * (unsigned)this->R.rw;
             body(u, v);
         }
     }
 };
 
-// The slice blockIdx.x of the rectangle sg (in range) of frame sg.frame; conf: all frames' maps or
-// null; labels: the frame's map or null.  False for a slice past the area (block-uniform).
+// The slice blockIdx.x of a view.  False for a slice past the area (block-uniform).
 template <typename T, typename L>
-__device__ __forceinline__ bool region_slice(const sdr_segment& sg, const T* __restrict__ disp, size_t stride,
-                                             size_t fstride, int W, int H, const float* __restrict__ conf, L* labels,
-                                             RegionSlice<T, L>* s) {
-    s->R = plane_rect(sg);
-    s->area = (unsigned)s->R.rw * (unsigned)s->R.rh;  // <= W * H <= 2^24
+__device__ __forceinline__ bool region_cut(const RegionView<T, L>& vw, RegionSlice<T, L>* s) {
+    static_cast<RegionView<T, L>&>(*s) = vw;
+    s->area = (unsigned)vw.R.rw * (unsigned)vw.R.rh;  // <= W * H <= 2^24
     s->base = blockIdx.x * (unsigned)kRegionSlice;
-    if (s->base >= s->area) return false;
-    const size_t org = (size_t)s->R.ys * W + (size_t)s->R.xs;
-    s->fd = disp + (size_t)sg.frame * fstride + (size_t)s->R.ys * stride + (size_t)s->R.xs;
-    s->fc = conf ? conf + (size_t)sg.frame * H * W + org : nullptr;
-    s->fl = labels ? labels + org : nullptr;
-    return true;
+    return s->base < s->area;
+}
+
+// The prologue of a kernel that applies the rule to a query's rectangle.  query_view: the
+// rectangle with its frame's maps, of a query that is in range.  The other two: the refusal flag
+// first (0: the query runs, *pl its plane), then the view, or the workgroup's slice of it (false: the
+// query is refused or the slice is past the area; block-uniform).
+template <typename T, typename Query>
+__device__ __forceinline__ RegionView<T> query_view(const RegionMaps<T>& m, const Query& q) {
+    return m.view(region_segment(q), m.frame_labels(q.frame));
+}
+template <typename T, typename Query>
+__device__ __forceinline__ uint32_t query_view(const RegionMaps<T>& m, const sdr_plane* __restrict__ planes, int NP,
+                                               const Query& q, RegionPlane* pl, RegionView<T>* vw) {
+    const uint32_t refused = query_refusal(m.dims(), planes, NP, q, pl);
+    if (!refused) *vw = query_view(m, q);
+    return refused;
+}
+template <typename T, typename Query>
+__device__ __forceinline__ bool query_slice(const RegionMaps<T>& m, const sdr_plane* __restrict__ planes, int NP,
+                                            const Query& q, RegionPlane* pl, RegionSlice<T>* s) {
+    return !query_refusal(m.dims(), planes, NP, q, pl) && region_cut(query_view(m, q), s);
 }
 
 }  // namespace sdr

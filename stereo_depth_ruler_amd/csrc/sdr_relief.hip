@@ -40,15 +40,6 @@ struct ReliefState {
 };
 static_assert(sizeof(ReliefState) == 272, "ReliefState is 272 bytes");
 
-// float -> key with the floats' order (no NaN among the members); and back
-__device__ __forceinline__ unsigned relief_key(float hf) {
-    const unsigned b = __float_as_uint(hf);
-    return b ^ ((b & 0x80000000u) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float relief_unkey(unsigned k) {
-    return __uint_as_float(k ^ ((k & 0x80000000u) ? 0x80000000u : 0xffffffffu));
-}
-
 // One sweep over the queries' pixels: grid (slices of a W x H frame, queries), `hist` the pass's
 // histograms of the batch.  Pass 1 sums the counts and the integer sums, takes the extremes on the
 // ordered key and counts the key's top 11 bits; pass 2 counts the next 11 bits of the keys whose
@@ -59,8 +50,7 @@ __device__ __forceinline__ float relief_unkey(unsigned k) {
 // workgroup waits on another.
 template <typename T, int PASS>
 __global__ __launch_bounds__(kRegionThreads) void k_relief_sweep(
-    const T* __restrict__ disp, size_t stride, size_t fstride, int W, int H, int F, const float* __restrict__ conf,
-    const uint8_t* __restrict__ labels, Q16 Q, sdr_relief_params P, const sdr_plane* __restrict__ planes, int NP,
+    RegionMaps<T> maps, Q16 Q, sdr_relief_params P, const sdr_plane* __restrict__ planes, int NP,
     const sdr_relief_query* __restrict__ queries, ReliefState* __restrict__ states, unsigned* __restrict__ hist) {
 #pragma clang fp contract(off)
     extern __shared__ unsigned lh[];
@@ -71,11 +61,8 @@ __global__ __launch_bounds__(kRegionThreads) void k_relief_sweep(
     if (PASS > 1 && S->status) return;  // block-uniform
     const sdr_relief_query q = queries[k];
     RegionPlane pl;
-    if (region_refusal(q, W, H, F, labels != nullptr, planes, NP, &pl)) return;
-    RegionSlice<T, const uint8_t> sl;
-    if (!region_slice(region_segment(q), disp, stride, fstride, W, H, conf,
-                      labels ? labels + (size_t)q.frame * H * W : nullptr, &sl))
-        return;
+    RegionSlice<T> sl;
+    if (!query_slice(maps, planes, NP, q, &pl, &sl)) return;
     const int nslot = PASS == 1 ? 1 : S->nslot[PASS - 2];  // 1..nq
     const int slots = PASS == 1 ? 1 : P.nq;                 // the query's histograms of this pass
     unsigned pre[kReliefQ];
@@ -89,9 +76,8 @@ __global__ __launch_bounds__(kRegionThreads) void k_relief_sweep(
     for (int i = 0; i < kReliefSums; i++) m[i] = 0;
     unsigned kmax = 0, kmin_inv = 0;
     sl.each([&](unsigned u, unsigned v) __attribute__((always_inline)) {
-        const RegionPix px = region_pixel(sl.fd, stride, sl.fc, sl.fl, W, Q, pl, P.min_disp, P.conf_min, q.label,
-                                          sl.R.xs, sl.R.ys, u, v);
-        const unsigned key = relief_key(px.hf);
+        const RegionPix px = region_pixel(sl, Q, pl, P.min_disp, P.conf_min, q.label, u, v);
+        const unsigned key = ordered_key(px.hf);
         if (PASS == 1) {
             m[0] += px.masked ? 1 : 0;
             m[1] += px.valid ? 1 : 0;
@@ -231,8 +217,8 @@ __device__ __forceinline__ void relief_write(sdr_relief* o, const sdr_relief_que
         r.n_rejected = r.n_valid - r.n;
         r.sum256 = S->acc[5];
         r.sum256_above = S->acc[6];
-        r.h_max = relief_unkey(S->kmax);
-        r.h_min = relief_unkey(~S->kmin_inv);
+        r.h_max = ordered_unkey(S->kmax);
+        r.h_min = ordered_unkey(~S->kmin_inv);
         r.mean = ((double)r.sum256 / (double)r.n) / 256.0;
         if (r.n_above > 0) r.mean_above = ((double)r.sum256_above / (double)r.n_above) / 256.0;
     }
@@ -247,8 +233,7 @@ __device__ __forceinline__ void relief_write(sdr_relief* o, const sdr_relief_que
 // Behind sweep 1, a workgroup a query: the record of a query that is refused or has no member
 // (the later kernels then leave it), else for each quantile the bin of the first histogram its
 // rank falls in and the rank inside the bin.
-__global__ __launch_bounds__(kRegionThreads) void k_relief_pick1(int W, int H, int F, int has_labels,
-                                                                 sdr_relief_params P,
+__global__ __launch_bounds__(kRegionThreads) void k_relief_pick1(RegionDims dims, sdr_relief_params P,
                                                                  const sdr_plane* __restrict__ planes, int NP,
                                                                  const sdr_relief_query* __restrict__ queries,
                                                                  ReliefState* __restrict__ states,
@@ -259,7 +244,7 @@ __global__ __launch_bounds__(kRegionThreads) void k_relief_pick1(int W, int H, i
     const sdr_relief_query q = queries[k];
     ReliefState* S = states + k;
     RegionPlane pl;
-    uint32_t flags = region_refusal(q, W, H, F, has_labels != 0, planes, NP, &pl);
+    uint32_t flags = query_refusal(dims, planes, NP, q, &pl);
     const long long n = S->acc[2];
     if (!flags && n == 0) flags = SDR_RELIEF_EMPTY;
     if (flags) {  // block-uniform
@@ -315,7 +300,7 @@ __global__ __launch_bounds__(kRegionThreads) void k_relief_finish(sdr_relief_par
         unsigned bin, rank;
         relief_locate<kReliefLastBins>(hist3 + ((size_t)k * P.nq + s) * kReliefLastBins, S->rank[1][j], sh_wave,
                                        sh_res, &bin, &rank);
-        if (tid == 0) qv[j] = relief_unkey((S->prefix[1][s] << 10) | bin);
+        if (tid == 0) qv[j] = ordered_unkey((S->prefix[1][s] << 10) | bin);
     }
     if (tid != 0) return;
     const sdr_relief_query q = queries[k];
@@ -388,27 +373,27 @@ int sdr_plane_relief_device(const void* d_disp, int disp_type, size_t stride, si
     const size_t lds1 = sdr::kReliefBins * sizeof(unsigned), lds2 = (size_t)nq * lds1,
                  lds3 = (size_t)nq * sdr::kReliefLastBins * sizeof(unsigned);
     hipError_t e = hipSuccess;
-    auto batch = [&](auto* disp, int k0, int kb) {
-        using T = disp_elem_t<decltype(disp)>;
+    auto batch = [&](auto maps, int k0, int kb) {
+        using T = disp_elem_t<decltype(maps)>;
         const sdr_relief_query* qs = d_queries + k0;
         const dim3 sgrid(slices, (unsigned)kb), pgrid((unsigned)kb);
         if ((e = hipMemsetAsync(sc.base, 0, lay.total, st)) != hipSuccess) return;
-        hipLaunchKernelGGL((sdr::k_relief_sweep<T, 1>), sgrid, block, lds1, st, disp, stride, frame_stride, W, H, F,
-                           d_conf, d_labels, q, RP, d_planes, P, qs, states, h1);
-        hipLaunchKernelGGL(sdr::k_relief_pick1, pgrid, block, 0, st, W, H, F, d_labels ? 1 : 0, RP, d_planes, P, qs,
-                           states, (const unsigned*)h1, d_out + k0);
+        hipLaunchKernelGGL((sdr::k_relief_sweep<T, 1>), sgrid, block, lds1, st, maps, q, RP, d_planes, P, qs, states, h1);
+        hipLaunchKernelGGL(sdr::k_relief_pick1, pgrid, block, 0, st, maps.dims(), RP, d_planes, P, qs, states,
+                           (const unsigned*)h1, d_out + k0);
         if (nq > 0) {
-            hipLaunchKernelGGL((sdr::k_relief_sweep<T, 2>), sgrid, block, lds2, st, disp, stride, frame_stride, W, H,
-                               F, d_conf, d_labels, q, RP, d_planes, P, qs, states, h2);
+            hipLaunchKernelGGL((sdr::k_relief_sweep<T, 2>), sgrid, block, lds2, st, maps, q, RP, d_planes, P, qs, states,
+                               h2);
             hipLaunchKernelGGL(sdr::k_relief_pick2, pgrid, block, 0, st, RP, states, (const unsigned*)h2);
-            hipLaunchKernelGGL((sdr::k_relief_sweep<T, 3>), sgrid, block, lds3, st, disp, stride, frame_stride, W, H,
-                               F, d_conf, d_labels, q, RP, d_planes, P, qs, states, h3);
+            hipLaunchKernelGGL((sdr::k_relief_sweep<T, 3>), sgrid, block, lds3, st, maps, q, RP, d_planes, P, qs, states,
+                               h3);
         }
         hipLaunchKernelGGL(sdr::k_relief_finish, pgrid, block, 0, st, RP, qs, (const sdr::ReliefState*)states,
                            (const unsigned*)h3, d_out + k0);
     };
     for (int k0 = 0; k0 < K && e == hipSuccess; k0 += KB)
-        with_disp(disp_type, d_disp, [&](auto* disp) { batch(disp, k0, std::min(K - k0, KB)); });
+        with_maps(d_disp, disp_type, stride, frame_stride, W, H, F, d_conf, d_labels,
+                  [&](auto maps) { batch(maps, k0, std::min(K - k0, KB)); });
     return sc.finish(e);
 }
 

@@ -105,10 +105,7 @@ struct RulerShared {
 };
 
 template <typename T>
-__global__ __launch_bounds__(kRulerThreads) void k_ruler(const T* __restrict__ disp, size_t stride,
-                                                         size_t fstride, int W, int H, int F,
-                                                         const float* __restrict__ conf, Q16 Q,
-                                                         sdr_ruler_params P,
+__global__ __launch_bounds__(kRulerThreads) void k_ruler(RegionMaps<T> maps, Q16 Q, sdr_ruler_params P,
                                                          const sdr_segment* __restrict__ segs,
                                                          sdr_measurement* __restrict__ out,
                                                          float* __restrict__ profile) {
@@ -117,12 +114,11 @@ __global__ __launch_bounds__(kRulerThreads) void k_ruler(const T* __restrict__ d
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const sdr_segment sg = segs[k];
-    if (!segment_in_range(sg, W, H, F)) {  // block-uniform
+    if (!maps.holds(sg)) {  // block-uniform
         if (tid == 0) write_out_of_range(out + k);
         return;
     }
-    const T* fd = disp + (size_t)sg.frame * fstride;
-    const float* fc = conf ? conf + (size_t)sg.frame * W * H : nullptr;
+    const FrameMaps<T> fm = maps.frame(sg.frame);
     const int dx = sg.x1 - sg.x0, dy = sg.y1 - sg.y0;
     const int m = max(abs(dx), abs(dy)), n = m + 1;
     float* prow = (P.profile && profile) ? profile + (size_t)k * P.profile_cap * 4 : nullptr;
@@ -131,7 +127,7 @@ __global__ __launch_bounds__(kRulerThreads) void k_ruler(const T* __restrict__ d
     auto process = [&](int i, int slot) {
         const int x = m ? walk_coord(sg.x0, dx, i, m) : sg.x0;
         const int y = m ? walk_coord(sg.y0, dy, i, m) : sg.y0;
-        const RulerSample s = ruler_sample(fd, stride, fc, W, H, Q, P, x, y, lane);
+        const RulerSample s = ruler_sample(fm, Q, P, x, y, lane);
         if (lane == 0) {
             if (i == 0 || i == m) {
                 const int e0 = i == 0 ? 0 : 1, e1 = i == m ? 1 : 0;  // n == 1: both
@@ -339,9 +335,9 @@ int sdr_measure_disp_device(const void* d_disp, int disp_type, size_t stride, si
     if (params->profile_cap == 0) d_profile = nullptr;  // no rows: not a profile buffer (sdr.h)
     const sdr::Q16 q = make_q16(Q);
     const dim3 grid((unsigned)K), block(params->profile ? sdr::kRulerThreads : sdr::kRulerEndThreads);
-    with_disp(disp_type, d_disp, [&](auto* disp) {
-        hipLaunchKernelGGL(sdr::k_ruler<disp_elem_t<decltype(disp)>>, grid, block, 0, (hipStream_t)stream, disp, stride,
-                           frame_stride, W, H, F, d_conf, q, *params, d_segs, d_out, d_profile);
+    with_maps(d_disp, disp_type, stride, frame_stride, W, H, F, d_conf, nullptr, [&](auto maps) {
+        hipLaunchKernelGGL(sdr::k_ruler<disp_elem_t<decltype(maps)>>, grid, block, 0, (hipStream_t)stream, maps, q,
+                           *params, d_segs, d_out, d_profile);
     });
     SDR_HIP(hipGetLastError());
     return SDR_OK;

@@ -1,9 +1,12 @@
 // sdr_ruler_shared.hpp -- what the ruler's units (sdr_ruler.hip, sdr_plane.hip, sdr_relief.hip,
-// sdr_footprint.hip, sdr_objects.hip, sdr_clearance.hip) share: on the device the disparity loads, the canonical NaN, the wave
-// reductions, a rectangle's range test and the ruler's sample; on the host (ruler_host) the argument
+// sdr_footprint.hip, sdr_objects.hip, sdr_clearance.hip) share: on the device the disparity loads, the canonical NaN, the
+// ordered key of a float, the wave reductions, a rectangle's range test, the maps of a call as its
+// kernels take them (RegionMaps, one argument by value: the frame offsets and a rectangle's origin
+// are its members and written nowhere else; RegionDims for a kernel that reads no map) and the
+// ruler's sample; on the host (ruler_host) the argument
 // guards, the Q and disparity-type plumbing of a launch, the per-thread persistent buffers (held in
 // sdr_host.hpp's ThreadState) and the staged host-pointer call over them (HostCall).  The region
-// rule of the relief and the footprint is in sdr_region.hpp.
+// rule and the prologue of the kernels that apply it are in sdr_region.hpp.
 #pragma once
 #include <string>
 #include <type_traits>
@@ -48,6 +51,87 @@ __device__ __forceinline__ PlaneRect plane_rect(const sdr_segment& s) {
     r.rh = max(s.y0, s.y1) - r.ys + 1;
     return r;
 }
+
+// float -> key with the floats' order (no NaN among the members); and back
+__device__ __forceinline__ unsigned ordered_key(float hf) {
+    const unsigned b = __float_as_uint(hf);
+    return b ^ ((b & 0x80000000u) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float ordered_unkey(unsigned k) {
+    return __uint_as_float(k ^ ((k & 0x80000000u) ? 0x80000000u : 0xffffffffu));
+}
+
+// The size of a call's maps and whether it has label maps: what a kernel takes that reads no map.
+struct RegionDims {
+    int W, H, F, has_labels;
+    __device__ __forceinline__ bool holds(const sdr_segment& s) const { return segment_in_range(s, W, H, F); }
+};
+
+// One frame's maps: the disparity with its row stride, the dense confidence and label maps or null.
+template <typename T>
+struct FrameMaps {
+    const T* fd;
+    const float* fc;
+    const uint8_t* fl;
+    size_t stride;
+    int W, H;
+};
+
+// A rectangle of a frame: the maps at its origin (L: const uint8_t, or uint8_t for the sweep that
+// writes labels), so that pixel (u, v) of the rectangle is fd[v * stride + u], fc[v * W + u],
+// fl[v * W + u].
+template <typename T, typename L = const uint8_t>
+struct RegionView {
+    PlaneRect R;
+    const T* fd;
+    const float* fc;
+    L* fl;
+    size_t stride;
+    int W;
+};
+
+// The maps of a ruler call, as every kernel that reads one takes them (by value): F frames of
+// H x W, the disparity with its strides in elements, the dense confidence and label maps or null.
+// Its members are the only place where a frame index or a rectangle's origin becomes an address.
+template <typename T>
+struct RegionMaps {
+    using elem = T;
+    const T* disp;
+    const float* conf;
+    const uint8_t* labels;
+    size_t stride, fstride;
+    int W, H, F;
+
+    __host__ __device__ RegionDims dims() const { return RegionDims{W, H, F, labels != nullptr}; }
+    __device__ __forceinline__ bool holds(const sdr_segment& s) const { return segment_in_range(s, W, H, F); }
+    __device__ __forceinline__ bool holds(int frame, int x, int y) const {
+        return frame >= 0 && frame < F && x >= 0 && x < W && y >= 0 && y < H;
+    }
+    __device__ __forceinline__ const T* frame_disp(int f) const { return disp + (size_t)f * fstride; }
+    __device__ __forceinline__ const float* frame_conf(int f) const {
+        return conf ? conf + (size_t)f * H * W : nullptr;
+    }
+    __device__ __forceinline__ const uint8_t* frame_labels(int f) const {
+        return labels ? labels + (size_t)f * H * W : nullptr;
+    }
+    __device__ __forceinline__ FrameMaps<T> frame(int f) const {
+        return FrameMaps<T>{frame_disp(f), frame_conf(f), frame_labels(f), stride, W, H};
+    }
+    // the rectangle sg (in range) of frame sg.frame with the label map `fl` of that frame (or null)
+    template <typename L>
+    __device__ __forceinline__ RegionView<T, L> view(const sdr_segment& sg, L* fl) const {
+        RegionView<T, L> v;
+        v.R = plane_rect(sg);
+        const size_t org = (size_t)v.R.ys * W + (size_t)v.R.xs;
+        const float* fc = frame_conf(sg.frame);
+        v.fd = frame_disp(sg.frame) + (size_t)v.R.ys * stride + (size_t)v.R.xs;
+        v.fc = fc ? fc + org : nullptr;
+        v.fl = fl ? fl + org : nullptr;
+        v.stride = stride;
+        v.W = W;
+        return v;
+    }
+};
 
 __device__ __forceinline__ long long wave_sum(long long v) {
 #pragma unroll
@@ -108,10 +192,12 @@ __device__ __forceinline__ int ruler_select(const float (&v)[2], const bool (&ok
 // One sample by one wave (every lane returns the same values): the window's valid values, their
 // selection (above), then the reprojection.
 template <typename T>
-__device__ __forceinline__ RulerSample ruler_sample(const T* __restrict__ disp, size_t stride,
-                                                    const float* __restrict__ conf, int W, int H,
-                                                    const Q16& Q, const sdr_ruler_params& P, int x,
-                                                    int y, int lane) {
+__device__ __forceinline__ RulerSample ruler_sample(const FrameMaps<T>& fm, const Q16& Q, const sdr_ruler_params& P,
+                                                    int x, int y, int lane) {
+    const T* __restrict__ disp = fm.fd;
+    const float* __restrict__ conf = fm.fc;
+    const size_t stride = fm.stride;
+    const int W = fm.W, H = fm.H;
     const int r = P.radius;
     const int xs = max(x - r, 0), xe = min(x + r, W - 1);
     const int ys = max(y - r, 0), ye = min(y + r, H - 1);
@@ -156,17 +242,19 @@ inline sdr::Q16 make_q16(const double* Q) {
     return q;
 }
 
-// f(the map as const float* or const int16_t*): the launches of a checked disp_type
-template <typename F>
-inline void with_disp(int disp_type, const void* disp, F&& f) {
+// f(the call's maps as RegionMaps<float> or RegionMaps<int16_t>): the launches of a checked
+// disp_type; the arguments are an entry's run (labels: null for an entry that takes none)
+template <typename Fn>
+inline void with_maps(const void* disp, int disp_type, size_t stride, size_t fstride, int W, int H, int F,
+                      const float* conf, const uint8_t* labels, Fn&& f) {
     if (disp_type == SDR_DISP_F32)
-        f((const float*)disp);
+        f(sdr::RegionMaps<float>{(const float*)disp, conf, labels, stride, fstride, W, H, F});
     else
-        f((const int16_t*)disp);
+        f(sdr::RegionMaps<int16_t>{(const int16_t*)disp, conf, labels, stride, fstride, W, H, F});
 }
-// the map's element type from with_disp's pointer
-template <typename P>
-using disp_elem_t = std::remove_cv_t<std::remove_pointer_t<P>>;
+// the maps' element type from with_maps' argument
+template <typename M>
+using disp_elem_t = typename std::remove_cv_t<std::remove_reference_t<M>>::elem;
 
 inline int check_planes_arg(const void* planes, int P) {
     if (P < 0 || (P > 0 && !planes)) return rfail(SDR_ERR_ARG, "bad plane count or null planes");
