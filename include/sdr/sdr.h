@@ -1306,6 +1306,36 @@ int sdr_sgbm_plan_query(const sdr_sgbm_params* p, int cost, int width, int heigh
  * frames in one batch); SDR_ERR_ARG before the first call that ran the stages. */
 int sdr_sgbm_last_plan(const sdr_sgbm* h, sdr_sgbm_launches* out);
 
+/* How a call lays the path-cost records out in device memory (sdr_sgbm_debug_stage(4) hands them
+ * out by row whatever the order was).  A pixel's R records are `pix` contiguous int16 elements; the
+ * records of pixel (x, y) of frame f start at element f * frame + x * xs + y * ys.
+ *  - by row, [F][H][W1]: xs = pix, ys = W1 * pix.
+ *  - by column, [F][W1][H]: xs = H * pix, ys = pix.  The default (SDR_PATH_ORDER=row in the
+ *    environment when the handle is created keeps every call by row; col or anything else is the
+ *    default), but only where the fused pass is the one-column k_south_wta fed by k_paths with one chain a wave (south_tc = 0,
+ *    paths_kernel = SDR_SGBM_PATHS_CHAIN), in either record format; MODE_SGBM_3WAY, the sweeps and
+ *    the two-column / two-chain kernels keep the records by row, as does a frame so tall that a
+ *    diagonal chain's 32 steps of column stride would span 2^31 bytes.  The maps a call computes do
+ *    not depend on the order.
+ * reach: elements from a frame's first record to the end of the farthest one the fused pass loads
+ * (its last partial block of 12 rows reads whole; 0 for a sweep).  reach - frame <= slack, the
+ * elements the buffer keeps in front of the first frame's records and behind the last frame's span. */
+enum { SDR_SGBM_RECORDS_BY_ROW = 0, SDR_SGBM_RECORDS_BY_COLUMN = 1 };
+typedef struct sdr_sgbm_records {
+    int32_t order;          /* SDR_SGBM_RECORDS_BY_* */
+    int32_t r12;            /* 12-bit records */
+    int32_t nrec, pix;      /* R; int16 elements of a pixel's R records */
+    int64_t xs, ys;         /* int16 elements a step along x, along y */
+    int64_t frame;          /* int16 elements between frames (R*H*W1*D in either format) */
+    int64_t slack, reach;
+} sdr_sgbm_records;
+/* sdr_sgbm_plan_query's arguments and rules (SDR_PATH_ORDER and SDR_PATH_REC of the environment
+ * are honoured as a new handle would); a frame that matches no column reports all zeros. */
+int sdr_sgbm_records_query(const sdr_sgbm_params* p, int cost, int width, int height, int nframes,
+                           int channels, int cus, sdr_sgbm_records* out);
+/* The records of the handle's last call that ran the stages. */
+int sdr_sgbm_last_records(const sdr_sgbm* h, sdr_sgbm_records* out);
+
 /* Device self-test of the cross-lane primitives the kernels rely on (DPP wave shifts,
  * permlane swaps); fills 4 failure counters, all zero on a healthy gfx950. */
 int sdr_selftest_wave_ops(int* failures4);
@@ -1338,7 +1368,8 @@ int sdr_stream_probe_ex(int device, size_t bytes, int iters, double* gbs3);
  * holds its roles swapped).
  *
  * Stage 4, the path-cost records, pixel-interleaved in the summation order E, W, [N,] SE, SW[, NE,
- * NW] (R = P-1 directions; frames R*H*W1*D*2 bytes apart in either format):
+ * NW] (R = P-1 directions; frames R*H*W1*D*2 bytes apart in either format; always in the row order
+ * below -- a call that kept them by column, sdr_sgbm_last_records, has them turned on the host):
  *  - int16: [F][H][W1][R][D] s16, the path costs L themselves.
  *  - 12-bit (the default where it applies: P2 <= 4095, numDisparities = 128, MODE_SGBM, MODE_HH4 or
  *    unbatched MODE_HH, and launches that run one chain a wave; SDR_PATH_REC=16 in the environment

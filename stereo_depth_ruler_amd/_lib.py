@@ -125,6 +125,28 @@ def sgbm_plan(params, w, h, nframes=1, channels=1, cost=0, cus=0):
     return out.as_dict()
 
 
+class SgbmRecords(ctypes.Structure):
+    """sdr_sgbm_records (sdr_sgbm_records_query, sdr_sgbm_last_records)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("order", "r12", "nrec", "pix")] + \
+               [(n, ctypes.c_int64) for n in ("xs", "ys", "frame", "slack", "reach")]
+
+    def as_dict(self):
+        """{"order": "row" or "col", "r12", "nrec", "pix", "xs", "ys", "frame", "slack", "reach"}
+        (int16 elements; sdr.h)."""
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["order"] = "col" if self.order == 1 else "row"
+        d["r12"] = bool(self.r12)
+        return d
+
+
+def sgbm_records(params, w, h, nframes=1, channels=1, cost=0, cus=0):
+    """The path-cost records' layout of the call sgbm_plan describes, as SgbmRecords.as_dict()."""
+    out = SgbmRecords()
+    check(lib().sdr_sgbm_records_query(ctypes.byref(params), int(cost), int(w), int(h), int(nframes),
+                                       int(channels), int(cus), ctypes.byref(out)))
+    return out.as_dict()
+
+
 class Segment(ctypes.Structure):
     """sdr_segment."""
     _fields_ = [(n, ctypes.c_int32) for n in ("frame", "x0", "y0", "x1", "y1")]
@@ -392,6 +414,8 @@ SIGNATURES = [
     ("sdr_sgbm_debug_knob", _i, [_vp, _i, _i]),
     ("sdr_sgbm_plan_query", _i, [_PP, _i, _i, _i, _i, _i, _i, _c.POINTER(SgbmLaunches)]),
     ("sdr_sgbm_last_plan", _i, [_vp, _c.POINTER(SgbmLaunches)]),
+    ("sdr_sgbm_records_query", _i, [_PP, _i, _i, _i, _i, _i, _i, _c.POINTER(SgbmRecords)]),
+    ("sdr_sgbm_last_records", _i, [_vp, _c.POINTER(SgbmRecords)]),
     ("sdr_ruler_params_default", None, [_c.POINTER(RulerParams)]),
     ("sdr_measure_disp_device", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _c.POINTER(_c.c_double),
                                      _c.POINTER(RulerParams), _vp, _i, _vp, _vp, _vp]),
@@ -452,6 +476,10 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950).")
         L = ctypes.CDLL(_path)
         for name, res, args in SIGNATURES:
+            # an earlier build loaded for an A/B (use_library) may lack an entry this header added
+            # since; lib/libsdr.so itself must export every one
+            if _path != LIB_PATH and not hasattr(L, name):
+                continue
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -47,7 +47,7 @@ struct Io {
 // the call's volumes inside the handle's buffers, behind their front slack
 int16_t* vol_C(const sdr_sgbm* h, const Plan& p) { return (int16_t*)h->C.p + p.slack; }
 int16_t* vol_Caux(const sdr_sgbm* h, const Plan& p) { return (int16_t*)h->Caux.p + p.aux_slack; }
-int16_t* vol_L(const sdr_sgbm* h, const Plan& p) { return (int16_t*)h->Lr.p + p.lslack; }  // [F][H][W1][nrec][D]
+int16_t* vol_L(const sdr_sgbm* h, const Plan& p) { return (int16_t*)h->Lr.p + p.lslack; }  // [F][H][W1][nrec][D], or by column (record_order)
 // the right-view WTA keys; none are built when the LR check is skipped
 uint32_t* keys_of(const sdr_sgbm* h, const Plan& p) { return p.lr_skipped ? nullptr : (uint32_t*)h->keys2.p; }
 
@@ -265,8 +265,42 @@ void record_format(const Volumes& v, Plan& p, sdr::PathLaunch& pls, sdr::PathLau
     for (int i = 0; i < pls.ndirs; i++) pls.d[i].out = at(v.Lr, (size_t)i * recel);
 }
 
+// The order of the records, for both launches, through PathLaunch's two strides.  By column,
+// [F][W1][H][nrec]...: the fused pass's workgroup then reads its column's records -- a block of
+// rows, a consumer wave's four rows -- as one contiguous run instead of pieces a frame row apart.
+// Only where that pass is the one-column k_south_wta fed by one-chain k_paths, without 3WAY's
+// stripes (either record format); the two-column and two-chain kernels, whose second column or
+// chain is a neighbour along x, 3WAY and the sweeps keep row order, [F][H][W1][nrec]....  C stays
+// row-major.  col: the handle's SDR_PATH_ORDER.  A frame so tall that a diagonal chain's stores
+// between two re-basings would span 2^31 bytes by column keeps row order as well.
+void record_order(Plan& p, sdr::PathLaunch& pls, sdr::PathLaunch& plS, const sdr::PathsChoice& pc,
+                  const sdr::SouthChoice& sc, bool col) {
+    const sdr::Geometry& g = p.e.g;
+    auto set = [&](ptrdiff_t xs, ptrdiff_t ys) {
+        pls.l_xs = plS.l_xs = xs;
+        pls.l_ys = plS.l_ys = ys;
+    };
+    col = col && !p.sweep && p.nstr == 0 && pls.nredir == 0 && pc.kernel == SDR_SGBM_PATHS_CHAIN &&
+          sc.kernel == SDR_SGBM_SOUTH_WTA && !sc.tc;
+    if (col) {
+        set((ptrdiff_t)g.H * pls.l_pix, pls.l_pix);
+        col = sdr::paths_store_span(pls) <= (size_t)INT32_MAX;
+    }
+    if (!col) set(pls.l_pix, (ptrdiff_t)g.W1 * pls.l_pix);
+    sdr_sgbm_records& r = p.records;
+    r = sdr_sgbm_records{};
+    r.order = col ? SDR_SGBM_RECORDS_BY_COLUMN : SDR_SGBM_RECORDS_BY_ROW;
+    r.r12 = p.rec12;
+    r.nrec = p.nrec;
+    r.pix = pls.l_pix;
+    r.xs = pls.l_xs, r.ys = pls.l_ys;
+    r.frame = (int64_t)p.lfs;
+    r.slack = (int64_t)p.lslack;
+    r.reach = (int64_t)sdr::south_reach(g, plS, sc);
+}
+
 // The two path launches of a plan whose sweep decision is made (plan_sweep), the record format and
-// the kernel of every launch; p.launches is the record sdr_sgbm_last_plan and sdr_sgbm_plan_query
+// order and the kernel of every launch; p.launches is the record sdr_sgbm_last_plan and sdr_sgbm_plan_query
 // hand out, and pc / sc -- the same values -- are what the launchers switch on.  cus holds for
 // the chain-count thresholds alone (SDR_DEBUG_PLAN_CUS): nothing here sizes a grid.
 struct PathChoices {
@@ -274,13 +308,14 @@ struct PathChoices {
     sdr::SouthChoice sc;
 };
 PathChoices plan_launches(const Volumes& v, Plan& p, sdr::PathLaunch& pls, sdr::PathLaunch& plS, bool rec16,
-                          int cus) {
+                          bool col, int cus) {
     const sdr::Geometry& g = p.e.g;
     path_dirs(v, p, pls, plS);
     record_format(v, p, pls, plS, rec16, cus);
     PathChoices ch;
     ch.pc = sdr::paths_choice(g, pls, p.F, cus);
     ch.sc = sdr::south_choice(g, plS, p.nrec + 1, p.F, cus);
+    record_order(p, pls, plS, ch.pc, ch.sc, col);
     const sdr::CostChoice cc = sdr::cost_choice(g, p.cn, p.census());
     sdr_sgbm_launches& o = p.launches;
     o = sdr_sgbm_launches{};
@@ -432,7 +467,7 @@ int enqueue_compute(sdr_sgbm* h, Plan& planned, const Io& io, int16_t** final_di
     sdr::PathLaunch pls{}, plS{};
     // (the debug knob's compute units reach the two chain-count thresholds, nothing else)
     const int cus = h->plan_cus > 0 ? h->plan_cus : sdr::device_cus();
-    const PathChoices ch = plan_launches({vol_C(h, p), vol_L(h, p), vol_Caux(h, p)}, p, pls, plS, h->rec16, cus);
+    const PathChoices ch = plan_launches({vol_C(h, p), vol_L(h, p), vol_Caux(h, p)}, p, pls, plS, h->rec16, h->rec_col, cus);
     p.launches.cost_rows = cb.rows, p.launches.cost_bands = cb.bands;
     { KTimer kt(h, SDR_KERNEL_PATHS); sdr::launch_paths(p.e.g, pls, ch.pc, p.F, st); }
     if (p.sweep && (rc = stage_sweep(h, p))) return rc;
@@ -475,8 +510,13 @@ size_t sdr_sgbm_scratch_bytes_ex(const sdr_sgbm_params* p, int cost, int width, 
     return sdr::plan_scratch_bytes(pl);
 }
 
-int sdr_sgbm_plan_query(const sdr_sgbm_params* p, int cost, int width, int height, int nframes, int channels,
-                        int cus, sdr_sgbm_launches* out) {
+}  // extern "C"
+
+namespace {
+
+// sdr_sgbm_plan_query and sdr_sgbm_records_query: one plan, the launches and (recs) the records
+int plan_query(const sdr_sgbm_params* p, int cost, int width, int height, int nframes, int channels, int cus,
+               sdr_sgbm_launches* out, sdr_sgbm_records* recs) {
     if (!p || !out) return fail(SDR_ERR_ARG, "null argument");
     if (width <= 0 || height <= 0 || nframes <= 0 || cus < 0) return fail(SDR_ERR_ARG, "bad size, frame count or cus");
     Plan pl = sdr::make_plan(*p, cost, width, height, nframes, channels);
@@ -494,9 +534,33 @@ int sdr_sgbm_plan_query(const sdr_sgbm_params* p, int cost, int width, int heigh
     sdr::plan_sweep(&pl, shp);
     sdr::PathLaunch pls{}, plS{};
     const char* rec = getenv("SDR_PATH_REC");
-    plan_launches({nullptr, nullptr, nullptr}, pl, pls, plS, rec && atoi(rec) == 16, out->cus);
+    plan_launches({nullptr, nullptr, nullptr}, pl, pls, plS, rec && atoi(rec) == 16, sdr::path_order_col(), out->cus);
     *out = pl.launches;
     if (cus) out->sweep_nslots[0] = out->sweep_nslots[1] = 0;  // eligible, shape unknown
+    if (recs) *recs = pl.records;
+    return SDR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdr_sgbm_plan_query(const sdr_sgbm_params* p, int cost, int width, int height, int nframes, int channels,
+                        int cus, sdr_sgbm_launches* out) {
+    return plan_query(p, cost, width, height, nframes, channels, cus, out, nullptr);
+}
+
+int sdr_sgbm_records_query(const sdr_sgbm_params* p, int cost, int width, int height, int nframes, int channels,
+                           int cus, sdr_sgbm_records* out) {
+    sdr_sgbm_launches l;
+    if (out) *out = sdr_sgbm_records{};
+    return plan_query(p, cost, width, height, nframes, channels, cus, out ? &l : nullptr, out);
+}
+
+int sdr_sgbm_last_records(const sdr_sgbm* h, sdr_sgbm_records* out) {
+    if (!h || !out) return fail(SDR_ERR_ARG, "null argument");
+    if (!h->last.launches.cost_kernel) return fail(SDR_ERR_ARG, "no call has run the stages on this handle yet");
+    *out = h->last.records;
     return SDR_OK;
 }
 

@@ -2,8 +2,11 @@
 // debug read-back (the handle's part of include/sdr/sdr.h; the struct: sdr_handle.hpp).
 #include "sdr_handle.hpp"
 
+#include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <string>
+#include <vector>
 
 namespace sdr {
 
@@ -110,6 +113,11 @@ bool ktimer_begin(sdr_sgbm* h, int kind) {
     return true;
 }
 
+bool path_order_col() {
+    const char* o = getenv("SDR_PATH_ORDER");
+    return !(o && std::string(o) == "row");
+}
+
 void ktimer_end(sdr_sgbm* h) {
     (void)hipEventRecord(h->kev[2 * h->kused + 1], h->stream);
     h->kused++;
@@ -134,6 +142,7 @@ int sdr_sgbm_create(const sdr_sgbm_params* p, int device, sdr_sgbm** out) {
     h->device = device;
     const char* rec = getenv("SDR_PATH_REC");
     h->rec16 = rec && atoi(rec) == 16;
+    h->rec_col = sdr::path_order_col();
     if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) {
         delete h;
         return set_error(SDR_ERR_DEVICE, "hipStreamCreate failed");
@@ -314,6 +323,25 @@ int sdr_sgbm_debug_stage(const sdr_sgbm* h, int stage, void* dst, size_t bytes) 
                                  (int16_t*)h->dlr.p, pl.px, pl.e.disp12MaxDiff, pl.F, h->stream);
     }
     SDR_HIP(hipStreamSynchronize(h->stream));
+    const sdr_sgbm_records& rc = pl.records;
+    if (stage == 4 && rc.order == SDR_SGBM_RECORDS_BY_COLUMN) {
+        // the stage's documented layout is by row: copy the frames the request touches whole and
+        // turn each frame's [W1][H] records to [H][W1] here; the rest of a frame's span (unused by
+        // 12-bit records) goes out as it is
+        const size_t fb = (size_t)rc.frame * 2, rb = (size_t)rc.pix * 2;
+        const size_t W1 = pl.e.g.W1, H = pl.e.g.H;
+        const size_t nf = std::min((bytes + fb - 1) / fb, (size_t)pl.F);
+        if (bytes > nf * fb) return set_error(SDR_ERR_ARG, "stage buffer smaller than requested");
+        std::vector<char> dev(nf * fb), out(nf * fb);
+        SDR_HIP(hipMemcpy(dev.data(), (const char*)b->p + skip, nf * fb, hipMemcpyDeviceToHost));
+        out = dev;
+        for (size_t f = 0; f < nf; f++)
+            for (size_t y = 0; y < H; y++)
+                for (size_t x = 0; x < W1; x++)
+                    memcpy(&out[f * fb + (y * W1 + x) * rb], &dev[f * fb + (x * H + y) * rb], rb);
+        memcpy(dst, out.data(), bytes);
+        return SDR_OK;
+    }
     SDR_HIP(hipMemcpy(dst, (const char*)b->p + skip, bytes, hipMemcpyDeviceToHost));
     return SDR_OK;
 }

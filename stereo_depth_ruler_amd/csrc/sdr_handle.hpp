@@ -36,6 +36,9 @@ struct sdr_sgbm {
     // SDR_PATH_REC=16 in the environment when the handle was created: int16 path-cost records
     // always (A/B and tests; the default takes 12-bit records where enqueue_compute can)
     bool rec16 = false;
+    // SDR_PATH_ORDER in the environment when the handle was created (path_order_col): the records
+    // by column where record_order() can (the default), or by row always (=row: A/B and tests)
+    bool rec_col = true;
     sdr::HostXfer hx;  // pinned staging of the host-pointer entry points
     sdr::Buf cls_bgr, cls_gray, cls_small, cls_dl, cls_wls, cls_f, cls_conf, cls_filt;
     int timing = 0;  // 0 off, 1 stage events, 2 stage + per-kernel events
@@ -81,6 +84,9 @@ hipError_t relay(sdr_sgbm* h, hipStream_t from);
 hipError_t retire(sdr_sgbm* h);
 hipError_t begin_call(sdr_sgbm* h);
 int use_stream(sdr_sgbm* h, hipStream_t s, bool persistent);
+// SDR_PATH_ORDER of the environment now: false for "row", true for anything else (by column is
+// the default: k_south_wta 173 -> 160 us on C2, profiles/rec_order/README.md)
+bool path_order_col();
 
 // RAII event pair around one kernel launch when per-kernel timing is on.
 using KTimer = KScope;

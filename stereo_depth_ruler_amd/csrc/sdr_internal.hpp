@@ -137,6 +137,10 @@ struct PathLaunch {
     size_t cs_fstride;   // elements per frame of C
     size_t l_fstride;    // elements per frame of L
     int l_pix;           // int16 elements per pixel record of L ((P-1) * D; rec12: (P-1) * D * 3/4)
+    // int16 elements from a pixel's record to its right (x + 1) and lower (y + 1) neighbour's: row
+    // order [H][W1] {l_pix, W1 * l_pix}, column order [W1][H] {H * l_pix, l_pix} (record_order(),
+    // sdr_engine.hip).  Every address the two launches form on the record side goes through them.
+    ptrdiff_t l_xs, l_ys;
     // Record format, one decision per call for the producer (k_paths) and the consumer
     // (k_south_wta), made by the engine: 0 = int16 L; 1 = e = C - L in 12 bits a value (sdr_device.hpp
     // rec12_pack), D * 3/2 bytes a direction, when path_rec12_supported() and P2 <= 4095
@@ -226,6 +230,11 @@ PathsChoice paths_choice(const Geometry& g, const PathLaunch& pl, int F, int cus
 SouthChoice south_choice(const Geometry& g, const PathLaunch& pl, int npaths, int F, int cus);
 void launch_south_wta(const Geometry& g, const PathLaunch& pl, const SouthWtaArgs& a, const SouthChoice& c,
                       int F, hipStream_t st);
+// int16 elements from a frame's first record to the end of the farthest one the fused pass loads
+// (0: no fused pass); past the frame's span it lies in the next frame's span or the buffer's slack
+size_t south_reach(const Geometry& g, const PathLaunch& pl, const SouthChoice& c);
+// bytes a k_paths chain's stores span between two re-basings of their resource: below 2^31
+size_t paths_store_span(const PathLaunch& pl);
 // The choices' two thresholds -- a two-chain k_paths / two-column k_south_wta (both keep int16
 // records) -- and whether the kernels launch_paths(pls) and launch_south_wta(plS, npaths) would
 // dispatch both implement the 12-bit record format: D = 128 exactly, one chain or column a wave,

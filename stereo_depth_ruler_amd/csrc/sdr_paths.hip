@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256) void k_paths(Geometry g, PathLaunch pl) {
     // neither the addresses nor the stores need a clamp or a branch.
     const uint32_t lofs = (uint32_t)((PAD ? min(lane, D / DPL - 1) : lane) * DPL * 2);
     const ptrdiff_t rowb = (ptrdiff_t)(ch.dy * W1 + ch.dx) * D * 2;          // C, per step
-    const ptrdiff_t rowl = (ptrdiff_t)(ch.dy * W1 + ch.dx) * pl.l_pix * 2;   // L records, per step
+    const ptrdiff_t rowl = (ch.dy * pl.l_ys + ch.dx * pl.l_xs) * 2;          // L records, per step
     const char* cp = (const char*)(pl.C + (size_t)f * pl.cs_fstride + ((size_t)ch.y0 * W1 + ch.x0) * D);
     if (pd.dir == DIR_E || pd.dir == DIR_W) {
         // a short last 3WAY stripe's output rows: its own cost rows (RowRedirect)
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256) void k_paths(Geometry g, PathLaunch pl) {
                 cp = (const char*)(pl.redir[i].aux + (size_t)f * pl.aux_fstride +
                                    ((size_t)(ch.y0 - pl.redir[i].s0) * W1 + ch.x0) * D);
     }
-    char* op = (char*)(pd.out + (size_t)f * pl.l_fstride + ((size_t)ch.y0 * W1 + ch.x0) * pl.l_pix);
+    char* op = (char*)(pd.out + (size_t)f * pl.l_fstride + ch.y0 * pl.l_ys + ch.x0 * pl.l_xs);
 
     Regs<K> Lp;
 #pragma unroll
@@ -290,11 +290,12 @@ __global__ __launch_bounds__(256) void k_paths_tc(Geometry g, PathLaunch pl) {
     const uint32_t lofs = (uint32_t)((PAD ? min(hl, D / DPL - 1) : hl) * DPL * 2);
     const ptrdiff_t pixB = (ptrdiff_t)(chB.y0 - ch.y0) * W1 + (chB.x0 - ch.x0);  // >= 0
     const ptrdiff_t rowb = (ptrdiff_t)(ch.dy * W1 + ch.dx) * D * 2;
-    const ptrdiff_t rowl = (ptrdiff_t)(ch.dy * W1 + ch.dx) * pl.l_pix * 2;
+    const ptrdiff_t recB = (chB.y0 - ch.y0) * pl.l_ys + (chB.x0 - ch.x0) * pl.l_xs;  // >= 0 too
+    const ptrdiff_t rowl = (ch.dy * pl.l_ys + ch.dx * pl.l_xs) * 2;
     const uint32_t vld = lofs + (half ? (uint32_t)(pixB * D * 2) : 0u);
-    const uint32_t vst = active ? lofs + (half ? (uint32_t)(pixB * pl.l_pix * 2) : 0u) : 0x80000000u;
+    const uint32_t vst = active ? lofs + (half ? (uint32_t)(recB * 2) : 0u) : 0x80000000u;
     const char* cp = (const char*)(pl.C + (size_t)f * pl.cs_fstride + ((size_t)ch.y0 * W1 + ch.x0) * D);
-    char* op = (char*)(pd.out + (size_t)f * pl.l_fstride + ((size_t)ch.y0 * W1 + ch.x0) * pl.l_pix);
+    char* op = (char*)(pd.out + (size_t)f * pl.l_fstride + ch.y0 * pl.l_ys + ch.x0 * pl.l_xs);
     Regs<K> Lp;
 #pragma unroll
     for (int i = 0; i < K; i++) Lp.r[i] = active ? 0u : kMaxPair;
@@ -542,17 +543,18 @@ __global__ __launch_bounds__(64 * (1 + kSouthConsumers)) void k_south_wta(Geomet
     const bool wactive = !PAD || gl * WDPL < D;
     const int wd0 = (PAD ? min(gl, (D - 1) / WDPL) : gl) * WDPL;
     // row blk*RB + r of the chain: wave-uniform block base + lane byte offset; the NP
-    // directions of a pixel are one contiguous record (q*D*2 folds into the instruction offset)
-    const ptrdiff_t bstepb = (ptrdiff_t)RB * W1 * pl.l_pix * 2;
+    // directions of a pixel are one contiguous record (q*D*2 folds into the instruction offset).
+    // By column (PathLaunch::l_ys = l_pix) a block's rows, and the chain's blocks, are contiguous
+    const ptrdiff_t bstepb = RB * pl.l_ys * 2;
     int rr[NPASS];          // this lane group's row within a block, per pass
     uint32_t lofs[NPASS];
 #pragma unroll
     for (int ps = 0; ps < NPASS; ps++) {
         const int col = ps / RPASS;  // TC: passes of the second column are one pixel further on
         rr[ps] = (wv - 1) * kSouthRPW + (ps % RPASS) * 4 + grp;
-        lofs[ps] = (uint32_t)(((size_t)rr[ps] * W1 + col) * pl.l_pix * 2 + (R12 ? gl * 12 : wd0 * 2));
+        lofs[ps] = (uint32_t)((rr[ps] * pl.l_ys + col * pl.l_xs) * 2 + (R12 ? gl * 12 : wd0 * 2));
     }
-    const char* lbase = (const char*)(a.L + (size_t)f * pl.l_fstride + ((size_t)ch.y0 * W1 + ch.x0) * pl.l_pix);
+    const char* lbase = (const char*)(a.L + (size_t)f * pl.l_fstride + ch.y0 * pl.l_ys + ch.x0 * pl.l_xs);
     // blocks past the chain's last one re-read that block (L2 hits), not the buffers' slack
     // a block whose rows all lie before the chain's first output row (a 3WAY stripe's overlap
     // rows: recurred through by the producer, never output) reads its records from an empty
@@ -730,6 +732,28 @@ SouthChoice south_choice(const Geometry& g, const PathLaunch& pl, int npaths, in
     c.r12 = c.dpl == 2 && !c.pad && pl.rec12;
     c.tc = !c.r12 && c.dpl == 2 && south_two_col(g, pl, npaths, F, cus);  // at most 5 paths: np 2, 3, 4
     return c;
+}
+
+// The consumers load whole blocks of kSouthRB rows (blocks past a chain's last one re-read that
+// one), so a last partial block reaches up to kSouthRB - 1 records past the chain's end along y;
+// the two-column form's second column reaches one record past an odd W1 along x.
+size_t south_reach(const Geometry& g, const PathLaunch& pl, const SouthChoice& c) {
+    if (c.kernel != SDR_SGBM_SOUTH_WTA) return 0;
+    const int xmax = c.tc ? g.W1 - 1 + (g.W1 & 1) : g.W1 - 1;
+    size_t reach = 0;
+    for (int i = 0; i < pl.ndirs; i++) {
+        const int len = pl.d[i].yend - pl.d[i].ybeg;
+        if (len <= 0) continue;
+        const int ymax = pl.d[i].ybeg + (len + kSouthRB - 1) / kSouthRB * kSouthRB - 1;
+        reach = std::max(reach, (size_t)(ymax * pl.l_ys + xmax * pl.l_xs + pl.l_pix));
+    }
+    return reach;
+}
+
+// k_paths re-bases its store resource every 2 * paths_la() steps and carries the steps between in a
+// 32-bit offset below 2^31 (walk_chain): the longest such run of a diagonal chain, in bytes
+size_t paths_store_span(const PathLaunch& pl) {
+    return (size_t)(2 * paths_la<2>()) * (size_t)(pl.l_xs + pl.l_ys) * 2 + (size_t)pl.l_pix * 2;
 }
 
 template <int DPL, bool PAD>

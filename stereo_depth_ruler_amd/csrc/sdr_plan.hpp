@@ -62,11 +62,16 @@ struct Plan {
     SweepShape shp[2] = {};  // [0]: down (S, SE, SW + WTA), [1]: up (N, NE, NW)
     bool sweep = false;
     int nrec = 0;            // L records per pixel
-    size_t lslack = 0;       // elements of slack in front of the L records
-    size_t lfs = 0;          // L elements per frame, [H][W1][nrec][D]
+    // elements of slack in front of the L records and behind them: kSouthPad records a column in the
+    // larger of the two orders' y strides (W1 * nrec * D; by column a y step is one record)
+    size_t lslack = 0;
+    size_t lfs = 0;          // L elements per frame, [H][W1][nrec][D] or [W1][H][nrec][D] (records)
     // [pass][slots][tiles][2] counters, then the edge ring (sized for either pass)
     size_t flags_n[2] = {0, 0}, sweep_flags = 0, edge_bytes = 0;
     bool rec12 = false;      // 12-bit path-cost records (PathLaunch::rec12)
+    // the records' order (PathLaunch::l_xs, l_ys): by column, [F][W1][H][nrec]..., where the fused
+    // pass is the one-column k_south_wta fed by one-chain k_paths; by row, [F][H][W1][nrec]..., else
+    sdr_sgbm_records records{};
     // the kernel of every launch, as the launchers switch on it (sdr_sgbm_last_plan)
     sdr_sgbm_launches launches{};
 

@@ -21,7 +21,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import SDRError, SgbmLaunches, SgbmParams, check, lib
+from ._lib import SDRError, SgbmLaunches, SgbmParams, SgbmRecords, check, lib
 
 try:  # torch is plumbing (device memory / streams); numpy-only use needs no torch
     import torch
@@ -306,6 +306,13 @@ class StereoSGBM:
         """The kernels the last compute launched (sdr_sgbm_last_plan), as _lib.sgbm_plan's dict."""
         out = SgbmLaunches()
         check(lib().sdr_sgbm_last_plan(self._h, ctypes.byref(out)))
+        return out.as_dict()
+
+    def last_records(self) -> dict:
+        """The path-cost records' layout of the last compute (sdr_sgbm_last_records), as
+        _lib.sgbm_records' dict."""
+        out = SgbmRecords()
+        check(lib().sdr_sgbm_last_records(self._h, ctypes.byref(out)))
         return out.as_dict()
 
     def enable_timing(self, level=1):
