@@ -1188,6 +1188,83 @@ int sdr_clearance(const void* disp, int disp_type, size_t stride, size_t frame_s
                   const double Q[16], const sdr_clearance_params* params, const sdr_plane* planes,
                   int P, const sdr_clearance_query* queries, int K, struct sdr_clearance* out);
 
+/* ---- the ruler over time: one disparity map from a still scene's last frames ----
+ * The reference measures on a frozen frame (the `f` key, stereo_displayer.cpp:191-196): camera and
+ * scene are still, and the frames before the freeze saw the same surfaces.  sdr_fuse_disp* makes one
+ * map of a stack of F frames, pixel by pixel: the valid values of a pixel vote, the ones within
+ * `tol` of their median are averaged, and a pixel whose frames are too few or disagree is a hole.
+ * The result is float [H][W] in px and goes into every sdr_measure_disp / sdr_fit_planes / ... call
+ * as a one-frame SDR_DISP_F32 map WITHOUT a confidence map (the gate was applied frame by frame).
+ * Every output is defined to the bit.  For pixel (x, y), v_k its value in frame k, k = 0..F-1
+ * (int16 disparities are read as (float)v * 0.0625f):
+ *   1. v_k is VALID by the ruler's rule: finite, v_k > min_disp (strict) and, with a confidence
+ *      map, conf_k >= conf_min (a NaN confidence is invalid).  n is the number of valid values.
+ *   2. n == 0: the pixel is EMPTY.
+ *   3. m is the LOWER median: element (n-1)/2 of the valid values in ascending order by < on floats,
+ *      equal values in frame order (-0.0 and +0.0 are equal: the earlier frame's bits win).  m is a
+ *      value of the stack, never an average.
+ *   4. v_k AGREES iff it is valid and fabsf(v_k - m) <= tol (one float subtraction, no contraction).
+ *      n_in counts the agreeing values; m agrees, so n_in >= 1.
+ *   5. n_in < min_count: the pixel is SPARSE if n < min_count, otherwise UNSTABLE (the frames
+ *      disagree: something moved, or the matcher flickers between two surfaces).
+ *   6. Otherwise the pixel is FUSED.  SDR_FUSE_MEDIAN writes m.  SDR_FUSE_MEAN writes
+ *      (float)(s / (double)n_in), s the double sum of (double)v_k over the agreeing k in ascending k
+ *      from +0.0 (exact for int16 input; for float input the order defines it), the division the
+ *      correctly rounded IEEE one.
+ *   - d_out (required, float [H][W], dense, not overlapping an input): the fused value, or `fill`
+ *     on an EMPTY, SPARSE or UNSTABLE pixel.
+ *   - d_support (nullable, uint8 [H][W]): n_in on a FUSED pixel, 0 elsewhere.
+ *   - d_spread (nullable, float [H][W]): on a FUSED pixel hi - lo (one float subtraction), lo the
+ *     smallest and hi the largest agreeing value by <, of equal ones the earliest frame's; on any
+ *     other pixel the canonical quiet NaN (0x7fc00000).
+ *   - d_rec (nullable): one sdr_fusion, every field an exact count, complete when the stream
+ *     reaches the end of the call.
+ * F == 1 is allowed (the validity gate, with min_count's rule). */
+enum { SDR_FUSE_MEAN = 0, SDR_FUSE_MEDIAN = 1 };
+enum { SDR_FUSE_MAX_FRAMES = 32 };
+
+typedef struct sdr_fuse_params { /* 32 bytes */
+    float min_disp, conf_min;      /* the ruler's validity rule */
+    float tol;                     /* px: a value agrees with the pixel's median iff |v - m| <= tol */
+    float fill;                    /* written where the stack has no consensus; not a valid value */
+    int32_t min_count;             /* agreeing values a pixel needs, 1..32 */
+    int32_t mode;                  /* SDR_FUSE_MEAN / SDR_FUSE_MEDIAN */
+    int32_t reserved[2];           /* 0 */
+} sdr_fuse_params;
+
+typedef struct sdr_fusion { /* 64 bytes */
+    int32_t frames, width, height, mode;             /* the call's */
+    int32_t n_fused, n_empty, n_sparse, n_unstable;  /* sum = width * height */
+    int32_t n_filled;    /* FUSED pixels whose LAST frame (F-1) was invalid: holes the stack filled */
+    int32_t n_replaced;  /* FUSED pixels whose last frame was valid but does not agree: outliers removed */
+    int64_t sum_support; /* sum of n_in over FUSED pixels */
+    int64_t n_disagree;  /* valid values, over FUSED pixels, that do not agree */
+    int64_t reserved;    /* 0 */
+} sdr_fusion;
+
+/* {-1.0f, 0.0f, 1.0f, -1.0f, 2, SDR_FUSE_MEAN, {0, 0}}: fill = min_disp */
+void sdr_fuse_params_default(sdr_fuse_params* p);
+/* One stack on device maps, asynchronous on `stream` (the maps arguments are
+ * sdr_measure_disp_device's): one launch, no host
+ * synchronisation; with d_rec a second short launch adds up the workgroups' partial records, which
+ * live in the stream-ordered scratch of the other device calls (4 KB).  A thread reads its pixels
+ * (two float, four int16; two int16 with more than 16 frames) with one 8-byte (4-byte) access where
+ * d_disp, stride and frame_stride keep that alignment, one by one otherwise; the results do not
+ * depend on it.
+ * The host refuses, before any device call: with SDR_ERR_ARG a null d_disp, d_out or params; width,
+ * height or nframes < 1; stride < width; frame_stride < stride * height when nframes > 1; an unknown
+ * disp_type or mode; tol not finite or < 0; min_count outside 1..32; a non-zero reserved field; a
+ * `fill` that is itself valid (finite and > min_disp: the result must never make a hole look
+ * measured).  With SDR_ERR_LIMIT: nframes > SDR_FUSE_MAX_FRAMES, width * height > INT32_MAX. */
+int sdr_fuse_disp_device(const void* d_disp, int disp_type, size_t stride, size_t frame_stride,
+                         int width, int height, int nframes, const float* d_conf,
+                         const sdr_fuse_params* params, float* d_out, uint8_t* d_support,
+                         float* d_spread, sdr_fusion* d_rec, void* stream);
+/* Host-pointer version (synchronous; per-thread persistent device buffers as sdr_measure_disp). */
+int sdr_fuse_disp(const void* disp, int disp_type, size_t stride, size_t frame_stride, int width,
+                  int height, int nframes, const float* conf, const sdr_fuse_params* params,
+                  float* out, uint8_t* support, float* spread, sdr_fusion* rec);
+
 /* Bytes of device scratch the handle holds for the given frame shape (for capacity planning);
  * 0 when compute would refuse the shape or parameters.  sdr_sgbm_scratch_bytes is the CV_8UC1
  * figure, sdr_sgbm_scratch_bytes_cn takes the channel count (1 or 3: colour input holds three

@@ -715,6 +715,56 @@ public:
         return clearance(disparity, std::vector<Plane>{plane},
                          {sdr_clearance_query{0, a.x, a.y, b.x, b.y, 0, label_a, label_b}}, labels, conf)[0];
     }
+    // One map of a still scene's last frames (sdr.h, "the ruler over time"; the frames before the `f`
+    // freeze of stereo_displayer.cpp:191-196): `frames` 1..32 disparity maps of one size and type,
+    // oldest first, `confs` none or as many continuous CV_32F confidence maps.  map is CV_32F in px
+    // and goes into every call above WITHOUT a confidence map (the gate was applied frame by frame);
+    // fill: the value of a pixel without a consensus, null for the ruler's min_disp.
+    struct Fused {
+        Mat map;            // CV_32F: the fused value, `fill` without a consensus
+        sdr_fusion record;  // the pixels of each class, the holes filled, the outliers replaced
+        Mat support;        // CV_8U: the agreeing values of a fused pixel (with_maps only)
+        Mat spread;         // CV_32F: their range, NaN where the pixel is not fused (with_maps only)
+    };
+    Fused fuse(const std::vector<Mat>& frames, const std::vector<Mat>& confs = {}, float tol = 1.0f, int min_count = 2,
+               int mode = SDR_FUSE_MEAN, const float* fill = nullptr, bool with_maps = false) const {
+        if (frames.empty()) throw Exception(SDR_ERR_ARG, "fuse needs at least one frame");
+        if (!confs.empty() && confs.size() != frames.size())
+            throw Exception(SDR_ERR_ARG, "fuse takes no confidence maps or one a frame");
+        const Mat& f0 = frames[0];
+        const size_t es = elem_size(f0.type), row = (size_t)f0.cols * es, frame = row * f0.rows;
+        // the entry takes one stack: the frames' rows behind one another
+        std::vector<uint8_t> stack(frames.size() * frame);
+        std::vector<float> cstack(confs.size() * (size_t)f0.cols * f0.rows);
+        for (size_t k = 0; k < frames.size(); k++) {
+            const Mat& f = frames[k];
+            check_maps(f, confs.empty() ? nullptr : &confs[k], "fuse");
+            if (f.type != f0.type || f.rows != f0.rows || f.cols != f0.cols)
+                throw Exception(SDR_ERR_ARG, "fuse takes frames of one size and type");
+            for (int y = 0; y < f.rows; y++) std::memcpy(stack.data() + k * frame + y * row, f.ptr<uint8_t>(y), row);
+            if (!confs.empty()) std::memcpy(cstack.data() + k * (frame / es), confs[k].data, frame / es * 4);
+        }
+        sdr_fuse_params fp;
+        sdr_fuse_params_default(&fp);
+        fp.min_disp = p_.min_disp;
+        fp.conf_min = p_.conf_min;
+        fp.tol = tol;
+        fp.fill = fill ? *fill : p_.min_disp;
+        fp.min_count = min_count;
+        fp.mode = mode;
+        Fused out;
+        out.map = Mat(f0.rows, f0.cols, CV_32FC1);
+        if (with_maps) {
+            out.support = Mat::pageable(f0.rows, f0.cols, CV_8UC1);
+            out.spread = Mat::pageable(f0.rows, f0.cols, CV_32FC1);
+        }
+        check(sdr_fuse_disp(stack.data(), f0.type == CV_32FC1 ? SDR_DISP_F32 : SDR_DISP_S16, (size_t)f0.cols,
+                            (size_t)f0.cols * f0.rows, f0.cols, f0.rows, (int)frames.size(),
+                            confs.empty() ? nullptr : cstack.data(), &fp, out.map.ptr<float>(0),
+                            with_maps ? out.support.data : nullptr, with_maps ? out.spread.ptr<float>(0) : nullptr,
+                            &out.record));
+        return out;
+    }
 
 private:
     static void check_labels(const Mat& disparity, const Mat* labels) {

@@ -25,6 +25,7 @@ from .ruler import (  # noqa: F401
     OBJECTS_TRUNCATED, OBJECTS_VALID,
     CLEARANCE_DTYPE, CLEARANCE_EMPTY, CLEARANCE_NO_PLANE, CLEARANCE_OUT_OF_RANGE, CLEARANCE_VALID,
     as_clearance_queries,
+    FUSE_MEAN, FUSE_MEDIAN, FUSION_DTYPE, FuseParams,
 )
 from .stereo_disparity import StereoDisparity  # noqa: F401
 
@@ -45,4 +46,5 @@ __all__ = [
     "OBJECTS_NO_PLANE", "OBJECTS_EMPTY", "OBJECTS_TRUNCATED",
     "CLEARANCE_DTYPE", "CLEARANCE_VALID", "CLEARANCE_OUT_OF_RANGE", "CLEARANCE_NO_PLANE", "CLEARANCE_EMPTY",
     "as_clearance_queries",
+    "FUSE_MEAN", "FUSE_MEDIAN", "FUSION_DTYPE", "FuseParams",
 ]

@@ -298,6 +298,23 @@ CLEARANCE_MAX_QUERIES = 64  # SDR_CLEARANCE_MAX_QUERIES
 DEBUG_CLEARANCE_PRUNE = 1   # SDR_DEBUG_CLEARANCE_PRUNE (sdr_clearance_debug_knob)
 
 
+class FuseParams(ctypes.Structure):
+    """sdr_fuse_params (32 bytes)."""
+    _fields_ = [(n, ctypes.c_float) for n in ("min_disp", "conf_min", "tol", "fill")] + \
+               [("min_count", ctypes.c_int32), ("mode", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
+
+
+class Fusion(ctypes.Structure):
+    """sdr_fusion (64 bytes)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("frames", "width", "height", "mode", "n_fused", "n_empty", "n_sparse",
+                                              "n_unstable", "n_filled", "n_replaced")] + \
+               [(n, ctypes.c_int64) for n in ("sum_support", "n_disagree", "reserved")]
+
+
+FUSE_MEAN, FUSE_MEDIAN = 0, 1  # SDR_FUSE_*
+FUSE_MAX_FRAMES = 32           # SDR_FUSE_MAX_FRAMES
+
+
 _lib = None
 _path = LIB_PATH
 
@@ -460,6 +477,10 @@ SIGNATURES = [
     ("sdr_clearance", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _vp, _c.POINTER(_c.c_double),
                            _c.POINTER(ClearanceParams), _vp, _i, _vp, _i, _vp]),
     ("sdr_clearance_debug_knob", _i, [_i, _i]),
+    ("sdr_fuse_params_default", None, [_c.POINTER(FuseParams)]),
+    ("sdr_fuse_disp_device", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _c.POINTER(FuseParams), _vp, _vp, _vp, _vp,
+                                  _vp]),
+    ("sdr_fuse_disp", _i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _c.POINTER(FuseParams), _vp, _vp, _vp, _vp]),
     ("sdr_build_id", _c.c_char_p, []),
     ("sdr_last_error", _c.c_char_p, []),
     ("sdr_abi_version", _i, []),

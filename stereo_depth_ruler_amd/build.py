@@ -15,7 +15,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libsdr.so")
 SOURCES = ["sdr_cost.hip", "sdr_cost3.hip", "sdr_cost3k2.hip", "sdr_cost_generic.hip", "sdr_census.hip", "sdr_paths.hip", "sdr_sweep.hip", "sdr_post.hip", "sdr_wls.hip", "sdr_fgs_seq.hip", "sdr_fgs_pcr.hip", "sdr_wls_plan.hip", "sdr_wls_entries.hip", "sdr_rectify.hip",
-           "sdr_cloud.hip", "sdr_display.hip", "sdr_ruler.hip", "sdr_plane.hip", "sdr_relief.hip", "sdr_footprint.hip", "sdr_objects.hip", "sdr_clearance.hip",
+           "sdr_cloud.hip", "sdr_display.hip", "sdr_ruler.hip", "sdr_plane.hip", "sdr_relief.hip", "sdr_footprint.hip", "sdr_objects.hip", "sdr_clearance.hip", "sdr_fuse.hip",
            "sdr_plan.hip", "sdr_staging.hip", "sdr_handle.hip", "sdr_engine.hip", "sdr_entries.hip"]
 HEADERS = ["sdr_device.hpp", "sdr_internal.hpp", "sdr_sgbm_rules.hpp", "sdr_cost_kernel.hpp", "sdr_fgs.hpp", "sdr_wls_plan.hpp", "sdr_ruler_shared.hpp", "sdr_region.hpp", "sdr_unionfind.hpp",
            "sdr_host.hpp", "sdr_plan.hpp", "sdr_staging.hpp", "sdr_handle.hpp", "sdr_voxel_plan.hpp", "sdr_layout.hpp"]

@@ -20,7 +20,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import check, lib
+from ._lib import FUSE_MEAN, check, lib
 from .display import Display
 from .ruler import Ruler
 from .sgbm import MODE_SGBM_3WAY, StereoSGBM, _Q, createRightMatcher, set_handle_stream, torch
@@ -189,6 +189,20 @@ class LiveLoop:
             raise RuntimeError("LiveLoop was built without ruler=")
         return self.ruler.clearance_device(self.disp, planes, pairs, labels, conf=self.conf, h_range=h_range,
                                            stream=stream)
+
+    def fuse(self, stream, tol: float = 1.0, min_count: int = 2, mode: int = FUSE_MEAN, support: bool = False,
+             spread: bool = False):
+        """Ruler.fuse_device on the `batch` frames the last enqueue left in `disp`, with their
+        confidence maps, enqueued on `stream` like measure(), no synchronise in between: one map of a
+        still scene's last frames (the reference measures after the `f` freeze,
+        stereo_displayer.cpp:191-196), as the (fused, record[, support][, spread]) tensors.  Pass the
+        result to `loop.ruler.<call>_device(fused, ..., conf=None, stream=stream)`: the confidence
+        gate has been applied frame by frame, and the per-frame `conf` tensor must not be passed
+        again (it has `batch` frames, the fused map one).  The other methods keep reading `disp`."""
+        if self.ruler is None:
+            raise RuntimeError("LiveLoop was built without ruler=")
+        return self.ruler.fuse_device(self.disp, conf=self.conf, tol=tol, min_count=min_count, mode=mode,
+                                      support=support, spread=spread, stream=stream)
 
     def close(self):
         for o in (self.left, self.right, self.wls, self.display):

@@ -35,6 +35,10 @@ the definition is in include/sdr/sdr.h).
   the ruler's sample taken over its own label's pixels (``radius``, ``min_count``), found by all pairs
   block against block with an exact prune on the blocks' bounds (csrc/sdr_clearance.hip), with the two
   pixels and points where it is attained and its parts along and across the floor's normal.
+* ``Ruler.fuse(stack)`` makes one map of a still scene's last frames (the frames before the
+  reference's ``f`` freeze): per pixel the valid values within ``tol`` of their median, averaged, and
+  a hole where the frames are too few or disagree (csrc/sdr_fuse.hip).  Every call above takes the
+  result as its disparity.
 * ``Ruler.find_planes(disparity, region=None)`` finds a region's dominant planes without a prior (a
   box on a table in front of a wall): rounds of seeded three-point hypotheses scored in exact
   integer arithmetic on the pixels no earlier plane has claimed, the winner refitted as
@@ -55,8 +59,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (DISP_F32, DISP_S16, ClearanceParams, FootprintParams, ObjectParams, PlaneParams, PlaneSearchParams, ReliefParams,
-                   RulerParams, SDRError, check, lib)
+from ._lib import (DISP_F32, DISP_S16, FUSE_MEAN, FUSE_MEDIAN, ClearanceParams, FootprintParams, FuseParams, ObjectParams,
+                   PlaneParams, PlaneSearchParams, ReliefParams, RulerParams, SDRError, check, lib)
 from .sgbm import _Q, _is_cuda, torch
 
 MEASUREMENT_DTYPE = np.dtype([
@@ -133,6 +137,14 @@ CLEARANCE_DTYPE = np.dtype([
     ("label_a", "<i4"), ("label_b", "<i4"), ("flags", "<u4"), ("reserved", "<i4", (4,))])
 assert CLEARANCE_DTYPE.itemsize == 128
 CLEARANCE_VALID, CLEARANCE_OUT_OF_RANGE, CLEARANCE_NO_PLANE, CLEARANCE_EMPTY = 1, 2, 4, 8
+
+
+# sdr_fusion: the record of a fused stack (its modes: FUSE_MEAN, FUSE_MEDIAN)
+FUSION_DTYPE = np.dtype([
+    ("frames", "<i4"), ("width", "<i4"), ("height", "<i4"), ("mode", "<i4"), ("n_fused", "<i4"), ("n_empty", "<i4"),
+    ("n_sparse", "<i4"), ("n_unstable", "<i4"), ("n_filled", "<i4"), ("n_replaced", "<i4"), ("sum_support", "<i8"),
+    ("n_disagree", "<i8"), ("reserved", "<i8")])
+assert FUSION_DTYPE.itemsize == 64
 
 
 def footprint_length_width(records):
@@ -890,6 +902,73 @@ class Ruler:
         return self._plane_queries_device("clearance_device", lib().sdr_clearance_device,
                                           lambda: self._clearance_params(h_range), 128, disparity, planes, pairs,
                                           _PAIRS, conf, stream, labels)
+
+    # ---- the ruler over time (sdr.h, "the ruler over time") ----
+    def _fuse_params(self, tol, min_count, mode, fill) -> FuseParams:
+        fill = self.min_disp if fill is None else float(fill)
+        return FuseParams(self.min_disp, self.conf_min, float(tol), fill, int(min_count), int(mode))
+
+    def fuse(self, disparity, conf=None, tol: float = 1.0, min_count: int = 2, mode: int = FUSE_MEAN, fill=None,
+             support: bool = False, spread: bool = False):
+        """One disparity map from the (F, H, W) stack of a still scene's last frames (F <= 32): a
+        pixel's valid values vote, those within `tol` px of their lower median agree, and with at
+        least min_count of them the pixel is their ordered mean (FUSE_MEAN) or the median itself
+        (FUSE_MEDIAN); any other pixel is `fill` (None: the ruler's min_disp, an invalid value).
+        conf: the frames' confidence maps, gated by the ruler's conf_min frame by frame.  Returns
+        (fused, record[, support][, spread]): fused float32 (1, H, W) in px, which every other
+        call takes as its disparity (without conf: the gate has been applied), one FUSION_DTYPE
+        record (the pixels fused, empty, sparse and unstable; the holes filled and the outliers
+        replaced against the last frame), support uint8 (H, W) the agreeing values a pixel, spread
+        float32 (H, W) their range (NaN where the pixel is not fused)."""
+        if _is_cuda(disparity):
+            outs = self.fuse_device(disparity, conf, tol, min_count, mode, fill, support, spread)
+            rec = outs[1].cpu().numpy().view(FUSION_DTYPE)[0]
+            return (outs[0].cpu().numpy(), rec) + tuple(o.cpu().numpy() for o in outs[2:])
+        d, c, a = self._host_maps(disparity, conf)
+        F, H, W = d.shape
+        p = self._fuse_params(tol, min_count, mode, fill)
+        out = np.empty((1, H, W), np.float32)
+        rec = np.zeros(1, FUSION_DTYPE)
+        sup = np.empty((H, W), np.uint8) if support else None
+        spr = np.empty((H, W), np.float32) if spread else None
+        with _on_device(self.device):
+            rc = lib().sdr_fuse_disp(*a, ctypes.byref(p), out.ctypes.data, sup.ctypes.data if support else None,
+                                     spr.ctypes.data if spread else None, rec.ctypes.data)
+        check(rc)
+        return (out, rec[0]) + ((sup,) if support else ()) + ((spr,) if spread else ())
+
+    def fuse_device(self, disparity, conf=None, tol: float = 1.0, min_count: int = 2, mode: int = FUSE_MEAN,
+                    fill=None, support: bool = False, spread: bool = False, stream=None, out=None):
+        """Enqueues the fusion of a CUDA stack (F, H, W), float32 or int16, on `stream` (default: the
+        current stream) and returns (fused, record[, support][, spread]) without synchronising:
+        fused a float32 tensor (1, H, W) that goes straight into any *_device call of the ruler on
+        the same stream (with conf=None), record a uint8 tensor (64,) (view its host copy as
+        FUSION_DTYPE).  out: a contiguous CUDA float32 tensor of H * W elements to write the map
+        into (not the stack)."""
+        if not _is_cuda(disparity):
+            raise SDRError(-5, "fuse_device expects a CUDA float32 or int16 tensor")
+        dev = disparity.device
+        s = stream if stream is not None else torch.cuda.current_stream(dev.index)
+        with torch.cuda.stream(s):
+            d, conf, a = self._device_maps(disparity, conf)
+            F, H, W = d.shape
+            if F > 1 and d.stride(0) < d.stride(1) * H:  # frames that interleave: the entry takes whole frames
+                d, conf, a = self._device_maps(d.contiguous(), conf)
+            p = self._fuse_params(tol, min_count, mode, fill)
+            if out is not None:
+                if (not _is_cuda(out) or out.dtype != torch.float32 or not out.is_contiguous()
+                        or out.numel() != H * W or out.device != dev):
+                    raise SDRError(-5, "out must be a contiguous CUDA float32 tensor of H * W elements")
+                fused = out.view(1, H, W)
+            else:
+                fused = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+            rec = torch.empty((64,), dtype=torch.uint8, device=dev)
+            sup = torch.empty((H, W), dtype=torch.uint8, device=dev) if support else None
+            spr = torch.empty((H, W), dtype=torch.float32, device=dev) if spread else None
+            check(lib().sdr_fuse_disp_device(*a, ctypes.byref(p), fused.data_ptr(), sup.data_ptr() if support else None,
+                                             spr.data_ptr() if spread else None, rec.data_ptr(),
+                                             ctypes.c_void_p(s.cuda_stream)))
+        return (fused, rec) + ((sup,) if support else ()) + ((spr,) if spread else ())
 
     # ---- XYZ-map mode (the reference's measurement) ----
     def measure_xyz(self, depth_map, segments):
